@@ -9,8 +9,15 @@ Workload = BASELINE.json configs[1]: NuScenes-shaped scenes (34,880 points, 5 cm
 8 target scenes per GPU (run/train.yaml: batch 16 on 2 GPUs = 8/GPU per loader).  value = 2*B*N / step time.
 Weak scaling: every rank processes its own 2*B scenes; the only collective is the gradient all-reduce.
 
-Extra legs (rank 0, N=1): `roofline` = sparse-conv engine kernels timed with HIP events against SURVEY.md 8d's
-algorithmic bytes; `cpu_baseline` = the CPU oracle timed on a bounded sample (2 source + 2 target scenes).
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds everything else it can measure:
+the host's enqueue time of a step into an empty queue (3 more steps after the timed ones) and, unless ``--no-extras``, the
+extra legs (rank 0, N=1): `roofline` = sparse-conv engine kernels timed with HIP events against SURVEY.md 8d's
+algorithmic bytes; `roofline_2d`, branch rates, the metadata build; `cpu_baseline` = the CPU oracle timed on a bounded sample
+(2 source + 2 target scenes).
+
+``--dump-outputs DIR`` writes what the last timed step computed, as float32 / float64 ``.npy`` files (at most 64 MB): the loss it
+returned, the parameters and floating-point buffers of both networks after its optimiser step (the 2D network's parameters as a
+fixed, seeded sample).  Weights and scenes are seeded, so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -476,6 +483,35 @@ def cpu_baseline():
             "seconds": round(sum(dts) + sum(c1) + sum(t3), 2)}
 
 
+DUMP_SAMPLE = 6 * 2**20  # elements kept of a network's parameters larger than this (a seeded sample): 24 MB in float32
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(tm, loss, out_dir):
+    """What a caller of the timed path holds after its last step: the returned loss and the two networks' parameters and floating
+    buffers as updated by that step.  Parameters in ``named_parameters()`` order, flattened; above DUMP_SAMPLE elements a sample
+    at sorted positions drawn with a fixed seed, so that two builds of the project are compared at the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray([float(loss.detach())], dtype=np.float64)}
+    for name in tm.modules_name:
+        net = tm.model[name]
+        flat = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            arrays[f"params_{name}_sample"] = flat[idx.to(flat.device)].cpu().numpy()
+        else:
+            arrays[f"params_{name}"] = flat.cpu().numpy()
+        bufs = [b.detach().reshape(-1).float() for b in net.buffers() if b.dtype.is_floating_point]
+        if bufs:
+            arrays[f"buffers_{name}"] = torch.cat(bufs).cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget"
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def launch_ranks(a, argv):
     """``python bench.py --gpus N`` without a launcher around it (no WORLD_SIZE in the environment): start the N ranks as CHILD
     processes through torch.distributed.run - one process per GPU, as the reference's Lightning DDP strategy spawns them
@@ -512,7 +548,11 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scenes", type=int, default=8, help="scenes per domain per GPU")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline / cpu_baseline legs")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline does not need: the "
+                    "empty-queue host enqueue time and the roofline / roofline_2d / branch / metadata / cpu_baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the roofline / cpu_baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, parameters and buffers of the last timed step to DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--workload", default="c2", choices=["c2", "c4", "c5"],
                     help="c2 = BASELINE.json configs[1] (headline); c4 = configs[3]: KITTI-shaped 121,600-pt scans, 4/GPU, 10 classes; "
                          "c5 = configs[4]: 10k-pt vKITTI-shaped source + KITTI-shaped target, 8/GPU, 16-bit sparse activations")
@@ -636,17 +676,20 @@ def main(argv=None):
     sync()
     dt = time.perf_counter() - t0
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
-    # host time of one step issued into an EMPTY queue (synchronised before each): what the host needs to enqueue a step when the
-    # GPU never pushes back.  host_enqueue_ms_per_step above is taken inside the timed loop, where a full queue throttles the host.
+    final_loss = float(loss.detach())
+    dumped = dump_outputs(tm, loss, a.dump_outputs) if a.dump_outputs and rank == 0 else None
     idle_host = []
-    for _ in range(3):
-        cur, nxt = nxt, next_batch()
+    if a.full:
+        # host time of one step issued into an EMPTY queue (synchronised before each): what the host needs to enqueue a step when
+        # the GPU never pushes back.  host_enqueue_ms_per_step is taken inside the timed loop, where a full queue throttles the host.
+        for _ in range(3):
+            cur, nxt = nxt, next_batch()
+            sync()
+            h0 = time.perf_counter()
+            tm.fit_step(cur, next_batch=nxt if pipeline else None)
+            idle_host.append((time.perf_counter() - h0) * 1e3)
         sync()
-        h0 = time.perf_counter()
-        tm.fit_step(cur, next_batch=nxt if pipeline else None)
-        idle_host.append((time.perf_counter() - h0) * 1e3)
-    sync()
-    idle_host.sort()
+        idle_host.sort()
     rank_ms = [dt / a.steps * 1e3]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -671,11 +714,15 @@ def main(argv=None):
                    "points_per_gpu_per_step": int(n_pts),
                    "distinct_batches_rotated": nb, "points_per_step_by_batch": [int(v) for v in n_pts_each],
                    "host_enqueue_ms_per_step": round(host_s / a.steps * 1e3, 3),
-                   "host_enqueue_ms_empty_queue": round(idle_host[1], 3), "parallelism": f"dp{world}", "final_loss": float(loss.detach()),
+                   "parallelism": f"dp{world}", "final_loss": final_loss,
                    "step_ms_p10_p50_p90": [round(per_step[int(q * (len(per_step) - 1))], 3) for q in (0.1, 0.5, 0.9)],
                    "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
                    "hip_graph_2d_trunk": _graph_state(tm)},
     }
+    if idle_host:
+        out["config"]["host_enqueue_ms_empty_queue"] = round(idle_host[1], 3)
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if world > 1 or forced:
         st = tm.reducer.stats
         out["config"].update({
@@ -702,13 +749,13 @@ def main(argv=None):
         out["dtype"] = (f"{a.precision} MFMA, fp32 accumulate (2D branch) + {a.sparse_act} sparse activations / fp32 accumulate and statistics "
                         "(3D branch)" + (", loss scale 65536 on the device (GradScaler semantics)" if a.sparse_act == "fp16" else ""))
         out["config"]["workload"] = out["config"]["workload"].replace("sparse rows bf16", f"sparse rows {a.sparse_act}")
-    if rank == 0 and world == 1 and not a.no_extras and a.workload in ("c4", "c5"):
+    if rank == 0 and world == 1 and a.full and not a.no_extras and a.workload in ("c4", "c5"):
         # configs[3] "stresses rulebook/hash build", configs[4] is the mixed-precision gather/scatter: the sparse-engine roofline of
         # THIS workload (same accounting as the headline's; 16-bit rows are charged 2 bytes per element) and what one batch's
         # sparse metadata build (voxel hash, rulebooks, tile tables) costs on the GPU
         out["roofline"] = conv_roofline(tm, batch, dev)
         out["config"]["metadata_build"] = metadata_build_ms(tm, batch, dev)
-    if rank == 0 and world == 1 and not a.no_extras and a.workload == "c2":
+    if rank == 0 and world == 1 and a.full and not a.no_extras and a.workload == "c2":
         print(f"[bench] timed region done: {ms:.2f} ms/step; roofline leg ...", file=sys.stderr, flush=True)
         out["roofline"] = conv_roofline(tm, batch, dev)
         out["roofline_2d"] = conv2d_roofline(tm, batch, dev)

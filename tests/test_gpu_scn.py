@@ -282,7 +282,12 @@ def test_net3d_forward_backward_vs_oracle(residual, engine):
     gradients are only conditioned to ~1e-2: the fp32 oracle differs from the fp64 oracle by that much, and a 1-ulp
     perturbation of the input features moves the oracle's own gradients by as much (ReLU masks and BN statistics amplify
     it, most in the residual variant).  Each HIP gradient must therefore be as close to the fp64 oracle as the fp32
-    oracle is, or as close as the oracle is to its own 1-ulp-perturbed self (factor 4), floor 1e-3."""
+    oracle is, or as close as the oracle is to its own 1-ulp-perturbed self (factor 4), floor 1e-3.
+    The fp32 oracle's rounding follows its summation order, which torch's CPU thread count sets: for this network the
+    gradient of one 3^3 layer of the plain variant lies 1.2e-3 .. 6e-3 from the fp64 oracle with 4-16 threads and 2.4e-2
+    with 1-2 threads, while the fp64 oracle moves by 1e-13.  So that the yardstick does not depend on the machine, the fp32
+    oracle runs both with the default thread count and with one thread, and the farther of the two from the fp64 oracle is
+    the one the HIP gradients are held to."""
     import copy
 
     from mm2d3d_amd.net3d import Net3DSeg
@@ -313,13 +318,25 @@ def test_net3d_forward_backward_vs_oracle(residual, engine):
     (p64["seg_logit"] * w.double()).sum().add((a64["seg_logit_point"] * w.double()).sum()).backward()
     g32 = dict(ref.named_parameters())
     g64 = dict(ref64.named_parameters())
+
+    def oracle_again(f):
+        """The fp32 oracle's gradients of the same loss once more, with the same weights, on features ``f``."""
+        net = copy.deepcopy(ref)
+        for q in net.parameters():
+            q.grad = None
+        pp, _, ap = net({"x": [coords, f.clone()]})
+        (pp["seg_logit"] * w).sum().add((ap["seg_logit_point"] * w).sum()).backward()
+        return dict(net.named_parameters())
+
     # conditioning probe: the fp32 oracle on features perturbed by ~1 ulp
-    refp = copy.deepcopy(ref)
-    for q in refp.parameters():
-        q.grad = None
-    pp, _, ap = refp({"x": [coords, (feats * (1.0 + 2.0 ** -23)).clone()]})
-    (pp["seg_logit"] * w).sum().add((ap["seg_logit_point"] * w).sum()).backward()
-    gpert = dict(refp.named_parameters())
+    gpert = oracle_again(feats * (1.0 + 2.0 ** -23))
+    # the fp32 oracle in a second, fixed summation order: one CPU thread
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        g32_1 = oracle_again(feats)
+    finally:
+        torch.set_num_threads(threads)
     errs = {}
     for name, p in hip.named_parameters():
         if "linear_global" in name:
@@ -329,7 +346,7 @@ def test_net3d_forward_backward_vs_oracle(residual, engine):
         t = g64[name].grad
         scale = max(1.0, t.abs().max().item())
         errs[name] = ((p.grad.detach().cpu().double() - t).abs().max().item() / scale,
-                      (g32[name].grad.double() - t).abs().max().item() / scale,
+                      max((g[name].grad.double() - t).abs().max().item() for g in (g32, g32_1)) / scale,
                       (gpert[name].grad.double() - g32[name].grad.double()).abs().max().item() / scale)
     noise = float(np.median([e[1] for e in errs.values()]))  # typical fp32 rounding noise of this network's gradients
     # A single ReLU-mask flip (pre-activation within a few ulp of 0) moves a weight gradient of this random linear loss by
@@ -347,13 +364,13 @@ def test_net3d_forward_backward_vs_oracle(residual, engine):
             continue
         t = g64[name].grad.double().flatten()
         h = p.grad.detach().cpu().double().flatten()
-        r = g32[name].grad.double().flatten()
+        rs = [g[name].grad.double().flatten() for g in (g32, g32_1)]
         if float(t.norm()) < 1e-9:
             assert float(h.norm()) < 1e-6, name
             continue
         cos_h = float((h @ t) / (h.norm() * t.norm()).clamp_min(1e-300))
-        cos_r = float((r @ t) / (r.norm() * t.norm()).clamp_min(1e-300))
-        l2_h, l2_r = float((h - t).norm() / t.norm()), float((r - t).norm() / t.norm())
+        cos_r = min(float((r @ t) / (r.norm() * t.norm()).clamp_min(1e-300)) for r in rs)
+        l2_h, l2_r = float((h - t).norm() / t.norm()), max(float((r - t).norm() / t.norm()) for r in rs)
         assert cos_h >= min(1.0 - 1e-4, 1.0 - 16.0 * (1.0 - cos_r)) - (2e-3 if residual else 0.0), (name, cos_h, cos_r)
         assert l2_h <= max(8.0 * l2_r, 2e-3) + (5e-2 if residual else 0.0), (name, l2_h, l2_r)
     for (n1, b1), (n2, b2) in zip(sorted(hip.named_buffers()), sorted(ref.named_buffers())):

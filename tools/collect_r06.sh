@@ -35,24 +35,24 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o w --output-format c
 ALG=$(grep algorithmic_bytes_per_step $O/prof3d_fetch.log | awk '{print $2}')
 python tools/pmc_traffic.py $O/pmc_fetch/f_counter_collection.csv $O/pmc_write/w_counter_collection.csv 5 16 $ALG "$1" > $O/traffic_3d.json 2> $O/traffic.err; echo "traffic rc=$?" | tee -a $O/summary_$PART.txt
 rm -rf $O/pmc_fetch $O/pmc_write   # raw counter files: tens of MB each, gpurun merges at most 64 MiB back
-MM_GRAPH2D=0 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O/pmc_sq -- python3 bench.py --steps 3 --warmup 2 --no-extras > $O/pmc_sq_bench.json 2> $O/pmc_sq.err; echo "pmc sq rc=$?" | tee -a $O/summary_$PART.txt
+MM_GRAPH2D=0 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O/pmc_sq -- python3 bench.py --full --steps 3 --warmup 2 --no-extras > $O/pmc_sq_bench.json 2> $O/pmc_sq.err; echo "pmc sq rc=$?" | tee -a $O/summary_$PART.txt
 python tools/pmc_sq.py $O/pmc_sq fp16 > $O/pmc_sq_step.json 2>> $O/pmc_sq.err; echo "pmc_sq reduce rc=$?" | tee -a $O/summary_$PART.txt
 rm -rf $O/pmc_sq
 # the counter records go to profiles/ BEFORE the bench (bench.py reads them from there), and are checked again at the end
 cp $O/traffic_3d.json $P/traffic_3d.json; cp $O/pmc_sq_step.json $P/pmc_sq_step.json
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?" | tee -a $O/summary_$PART.txt
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?" | tee -a $O/summary_$PART.txt
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_cmd.json 2> $O/bench_n1_driver_cmd.err; echo "bench (driver command) rc=$?" | tee -a $O/summary_$PART.txt
 export MM_BENCH_NO_CPU=1
-rocprofv3 --kernel-trace --stats -d $O/kstats -o ks --output-format csv -- python3 bench.py --steps 20 --warmup 5 > $O/bench_n1_profiled.json 2> $O/bench_n1_profiled.err; echo "rocprof rc=$?" | tee -a $O/summary_$PART.txt
+rocprofv3 --kernel-trace --stats -d $O/kstats -o ks --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 > $O/bench_n1_profiled.json 2> $O/bench_n1_profiled.err; echo "rocprof rc=$?" | tee -a $O/summary_$PART.txt
 cp $O/kstats/ks_kernel_stats.csv $O/bench_n1_kernel_stats.csv 2>/dev/null; rm -rf $O/kstats
 # the same with everything on ONE stream (no dW side stream, no rulebook side stream): per-kernel durations that the roofline leg's
 # per-call event times must agree with
-MM_SPCONV_BWD_OVERLAP=0 MM_META_SIDE=0 rocprofv3 --kernel-trace --stats -d $O/kstats_serial -o ks --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-extras > $O/bench_n1_serial_profiled.json 2> $O/bench_n1_serial_profiled.err; echo "rocprof serial rc=$?" | tee -a $O/summary_$PART.txt
+MM_SPCONV_BWD_OVERLAP=0 MM_META_SIDE=0 rocprofv3 --kernel-trace --stats -d $O/kstats_serial -o ks --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-extras > $O/bench_n1_serial_profiled.json 2> $O/bench_n1_serial_profiled.err; echo "rocprof serial rc=$?" | tee -a $O/summary_$PART.txt
 cp $O/kstats_serial/ks_kernel_stats.csv $O/bench_n1_serial_kernel_stats.csv 2>/dev/null; rm -rf $O/kstats_serial
 python tools/kstats_categories.py $O/bench_n1_serial_kernel_stats.csv 16 --top 45 > $O/kernel_families_serial.txt 2>&1
-python bench.py --workload c4 --steps 10 --warmup 3 > $O/bench_c4.json 2>/dev/null; python bench.py --workload c5 --steps 10 --warmup 3 > $O/bench_c5.json 2>/dev/null
-python bench.py --precision bf16 --steps 20 --warmup 5 --no-extras > $O/bench_n1_bf16.json 2>/dev/null
-MM_BN2D_FUSED=1 MM_BN_FUSED=1 MM_GRAPH2D=0 MM_META_SIDE=0 python bench.py --steps 20 --warmup 5 --no-extras > $O/bench_n1_as_under_ddp.json 2>/dev/null
+python bench.py --full --workload c4 --steps 10 --warmup 3 > $O/bench_c4.json 2>/dev/null; python bench.py --full --workload c5 --steps 10 --warmup 3 > $O/bench_c5.json 2>/dev/null
+python bench.py --full --precision bf16 --steps 20 --warmup 5 --no-extras > $O/bench_n1_bf16.json 2>/dev/null
+MM_BN2D_FUSED=1 MM_BN_FUSED=1 MM_GRAPH2D=0 MM_META_SIDE=0 python bench.py --full --steps 20 --warmup 5 --no-extras > $O/bench_n1_as_under_ddp.json 2>/dev/null
 summarise $O/bench_summary.txt
 fi
 if [[ "$PART" == *b* ]]; then
@@ -68,20 +68,20 @@ timeout -k 10 300 python tools/dw16_ab.py > $O/dw16_ab.txt 2>&1
 python tools/bench_bn2d.py --no-shapes > $O/bn2d_layer_set.txt 2>&1
 # A/B records of the round's switches (same box, back to back)
 for i in 1 2 3; do
-  python bench.py --steps 20 --warmup 5 --no-extras > $O/ab_default_$i.json 2>/dev/null
-  MM_CONV3X3_LEGACY=1 python bench.py --steps 20 --warmup 5 --no-extras > $O/ab_conv3x3_round2_kernel_$i.json 2>/dev/null
-  MM_CONV3X3_LEGACY=2 python bench.py --steps 20 --warmup 5 --no-extras > $O/ab_conv3x3_v_32x32x16_$i.json 2>/dev/null
-  MM_GRAPH2D=0 python bench.py --steps 20 --warmup 5 --no-extras > $O/ab_graph2d_off_$i.json 2>/dev/null
+  python bench.py --full --steps 20 --warmup 5 --no-extras > $O/ab_default_$i.json 2>/dev/null
+  MM_CONV3X3_LEGACY=1 python bench.py --full --steps 20 --warmup 5 --no-extras > $O/ab_conv3x3_round2_kernel_$i.json 2>/dev/null
+  MM_CONV3X3_LEGACY=2 python bench.py --full --steps 20 --warmup 5 --no-extras > $O/ab_conv3x3_v_32x32x16_$i.json 2>/dev/null
+  MM_GRAPH2D=0 python bench.py --full --steps 20 --warmup 5 --no-extras > $O/ab_graph2d_off_$i.json 2>/dev/null
 done
 # the data-parallel step on the one GPU of this box: a one-rank RCCL group with the reducer forced on (no xGMI; buckets, hooks, stream
 # ordering are the real ones) - default (eager trunk + "tail" + rulebook side stream), with the trunk's graphs, and round 5's form
 for i in 1 2; do
-  MM_DDP_FORCE=1 python bench.py --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_default_$i.json 2>/dev/null
-  MM_DDP_FORCE=1 MM_DDP_GRAPH=1 python bench.py --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_graphs_$i.json 2>/dev/null
-  MM_DDP_FORCE=1 MM_DDP_META_SIDE=0 python bench.py --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_round5_form_$i.json 2>/dev/null
-  python bench.py --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_none_$i.json 2>/dev/null
+  MM_DDP_FORCE=1 python bench.py --full --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_default_$i.json 2>/dev/null
+  MM_DDP_FORCE=1 MM_DDP_GRAPH=1 python bench.py --full --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_graphs_$i.json 2>/dev/null
+  MM_DDP_FORCE=1 MM_DDP_META_SIDE=0 python bench.py --full --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_round5_form_$i.json 2>/dev/null
+  python bench.py --full --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_none_$i.json 2>/dev/null
   # init_process_group(device_id=) as in rounds 2-5: the eager communicator alone costs every step ~1.5 ms (reducer on / off)
-  MM_DDP_FORCE=1 MM_BENCH_PG_EAGER=1 python bench.py --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_eager_init_$i.json 2>/dev/null
+  MM_DDP_FORCE=1 MM_BENCH_PG_EAGER=1 python bench.py --full --steps 40 --warmup 10 --no-extras > $O/ab_ddp1rank_eager_init_$i.json 2>/dev/null
 done
 summarise $O/ab_summary.txt
 fi
