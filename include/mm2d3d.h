@@ -132,6 +132,29 @@ int mm_collect_points(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_
                       const int64_t* labels, const float* image, int C, int H, int W, const float* points, int64_t* img_indices_out,
                       int64_t* labels_out, float* feats_out, float* points_out, mm_stream_t stream);
 
+/* ---------------------------------------------------------------- camera-image preparation (csrc/imageprep.hip)
+ * The image half of the loaders' per-sample code for a whole batch, bit-exact with PIL + numpy: the crop and the
+ * Image.resize(size, BILINEAR) of the front ends (semantic_kitti.py:321-392, a2d2.py:268-276, nuscenes_dataloader.py:257-262),
+ * the ColorJitter of the PIL image (nuscenes_dataloader.py:286-287), float conversion, fliplr and normalisation.  Decoding and
+ * every random draw stay on the host (mm2d3d_amd/imageprep.py builds the tables).
+ *   src        device uint8, the decoded RGB images back to back ([H_i][W_i][3] each), src_bytes long
+ *   desc       int64 [B][16] per scene, device copy and host copy (the host copy is checked against the buffer sizes):
+ *              MM_IMG_SRC_OFF 0 byte offset of the window's first pixel in src   MM_IMG_SRC_PITCH 1 bytes per source row
+ *              MM_IMG_WIN_W 2, MM_IMG_WIN_H 3 window size          MM_IMG_TMP_ROWS 4, MM_IMG_YBOX_FIRST 5 source rows of the
+ *              horizontal pass                                     MM_IMG_KX 6, MM_IMG_KY 7 taps per output column / row
+ *              MM_IMG_HCOEF 8, MM_IMG_VCOEF 9 int32 index into coef of bounds [W][2] (first tap, tap count) then Q22 weights
+ *              [W][KX] (vertical: [H][2], [H][KY], first taps relative to YBOX_FIRST)   MM_IMG_TMP_OFF 10 byte offset into tmp
+ *              MM_IMG_OPS 11 jitter operations in drawn order, 4 bits each (0 brightness, 1 contrast, 2 saturation, 3 hue)
+ *              MM_IMG_NOPS 12 count, MM_IMG_NPRE 13 operations before contrast (= NOPS without contrast)
+ *              MM_IMG_HUE 14 hue shift 0..255                      MM_IMG_FLIP 15 fliplr
+ *   factors    device fp32 [B][4] jitter factors by operation; lut device fp32 [B][3][256] = normalise(u8 / 255.0)
+ *   tmp        device uint8 scratch, tmp_bytes >= sum of TMP_ROWS * W * 3; mid device uint8 scratch [B][H][W][3];
+ *   sums       device int64 [B] scratch (sums of L before contrast)
+ * -> img fp32 [B][3][H][W], already flipped where FLIP is set.  Three launches. */
+int mm_image_prepare(const uint8_t* src, int64_t src_bytes, const int64_t* desc_dev, const int64_t* desc_host, int B, int H, int W,
+                     const int32_t* coef, int64_t coef_len, const float* factors, const float* lut, uint8_t* tmp, int64_t tmp_bytes,
+                     uint8_t* mid, int64_t* sums, float* img, mm_stream_t stream);
+
 /* ---------------------------------------------------------------- sparse convolution engines (csrc/spconv.hip)
  * scn.SubmanifoldConvolution / Convolution / Deconvolution forward and backward. */
 size_t mm_spconv_ws_bytes(int64_t n_rules, int Cin, int Cout, int K);

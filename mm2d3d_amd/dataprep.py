@@ -10,9 +10,11 @@ device, bit-identical to the host restatement (mm2d3d_amd/projection.py + synthe
     host (O(1) per scene, the reference's numpy RNG order)     device (per point / per pixel)
     -----------------------------------------------------     -------------------------------------------------------
     fliplr draw, rotation matrix, rand(3) translation draws     points.rot, *scale, -min, +offset, int cast, range mask,
-    image decode / resize / normalise (caller)                  order-preserving compaction + batch index column (a1, a2)
-                                                                pixel indices, fliplr remap, last-write-wins depth and
+    image decode / resize / normalise (caller), or the          order-preserving compaction + batch index column (a1, a2)
+    decode only (prepare_images)                                pixel indices, fliplr remap, last-write-wins depth and
                                                                 2D label maps, RGB features under the points (a16)
+                                                                prepare_images: crop, resize, jitter, float, fliplr,
+                                                                normalisation (csrc/imageprep.hip)
 """
 from __future__ import annotations
 
@@ -106,7 +108,45 @@ def project_batch(points_img, depth_vals, labels, lengths, H, W, flips=None, wan
     return idx, depth, seg2d, err
 
 
-def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0.0, want_seg2d=False, device="cuda", use_rgb=True):
+def prepare_images(plans, draws, flips, luts, device="cuda", decode_threads=4, timing=None):
+    """The image half of a batch on the GPU (csrc/imageprep.hip): ``plans`` = :class:`imageprep.ImagePlan` per scene (window +
+    target size), ``draws`` = ``ColorJitter.draw()`` per scene (or None), ``flips`` = fliplr per scene, ``luts`` = fp32
+    [3][256] per scene (:func:`imageprep.lut`).  Decodes every image with ``decode_threads`` threads into one pinned buffer,
+    copies it to the device in one H2D copy and runs the three kernels.  Returns img fp32 [B,3,H,W] on ``device``, already
+    flipped.  ``timing``: a dict that receives the GPU ms of the three kernels (``"kernels_ms"``, from events; synchronises)."""
+    from . import imageprep
+
+    L = _lib.lib()
+    dev = torch.device(device)
+    B = len(plans)
+    W, H = plans[0].size
+    nbytes = sum(p.image.size[0] * p.image.size[1] * 3 for p in plans)
+    staging = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    offs = imageprep.decode_into(plans, staging.numpy(), decode_threads)
+    desc, coef, factors, lut, tmp_bytes = imageprep.build_tables(plans, draws, flips, luts, offs)
+    src = staging.to(dev, non_blocking=True)
+    desc_d = torch.from_numpy(desc).to(dev)
+    coef_d = torch.from_numpy(coef).to(dev)
+    fac_d = torch.from_numpy(factors).to(dev)
+    lut_d = torch.from_numpy(lut).to(dev)
+    tmp = torch.empty(max(tmp_bytes, 1), dtype=torch.uint8, device=dev)
+    mid = torch.empty(B * H * W * 3, dtype=torch.uint8, device=dev)
+    sums = torch.empty(B, dtype=torch.int64, device=dev)
+    img = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    if timing is not None:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+    check(L.mm_image_prepare(ptr(src), nbytes, ptr(desc_d), desc.ctypes.data, B, H, W, ptr(coef_d), coef.size, ptr(fac_d), ptr(lut_d),
+                             ptr(tmp), tmp.numel(), ptr(mid), ptr(sums), ptr(img), stream()), "image_prepare")
+    if timing is not None:
+        ev[1].record()
+        ev[1].synchronize()
+        timing["kernels_ms"] = ev[0].elapsed_time(ev[1])
+    return img
+
+
+def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0.0, want_seg2d=False, device="cuda", use_rgb=True,
+                  img=None):
     """The reference's ``__getitem__`` (per scene) + ``collate_scn_base`` for a list of decoded scenes, on the GPU.
 
     Each scene: dict(points [n,3] f32 = the coordinates that are voxelised (camera or LiDAR frame, as the dataset is
@@ -116,7 +156,8 @@ def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0
     a scene that carries ``draws = (flip, rot, u)`` was drawn by the caller (datasets.gpu_batch draws scene by scene, between
     each scene's crop draws, as the reference's ``__getitem__`` sequence does).  ``use_rgb=False``: the constant feature of
     nuscenes_dataloader.py:365-368, ones [n, 1] with n = the scene's point count BEFORE the range mask (as in the reference).
-    Returns the batch dict of lib/dataset/__init__.py:95-121 with every tensor on ``device`` (img_indices: list of
+    ``img``: a device fp32 [B,3,H,W] batch image that is ALREADY flipped per the scenes' draws (:func:`prepare_images`); the
+    scenes then carry no "img".  Returns the batch dict of lib/dataset/__init__.py:95-121 with every tensor on ``device`` (img_indices: list of
     device int64 [n_i,2]; use ``[t.cpu().numpy() for t in ...]`` where numpy arrays are required)."""
     L = _lib.lib()
     dev = torch.device(device)
@@ -138,9 +179,12 @@ def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0
     pimg = cat("points_img", np.float32)
     dvals = cat("depth", np.float32)
     labels = cat("seg_label", np.int64)
-    img = torch.stack([torch.as_tensor(s["img"]) for s in scenes]).to(dev, torch.float32)
-    if any(flips):
-        img = torch.stack([im.flip(-1) if f else im for im, f in zip(img, flips)])
+    if img is None:
+        img = torch.stack([torch.as_tensor(s["img"]) for s in scenes]).to(dev, torch.float32)
+        if any(flips):
+            img = torch.stack([im.flip(-1) if f else im for im, f in zip(img, flips)])
+    elif img.device.type != dev.type or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B:
+        raise ValueError("prepare_batch: img must be a float32 [B,3,H,W] tensor on the batch's device")
     H, W = img.shape[-2:]
     vox = voxelize_batch(pts, lengths, rots, us, scale, full_scale)
     idx_all, depth, seg2d, err = project_batch(pimg, dvals, labels, lengths, H, W, flips, want_seg2d, vox["scene_off"])

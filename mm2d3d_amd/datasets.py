@@ -20,6 +20,8 @@ with every numpy RNG draw in the reference's order, so a seeded run picks the sa
 (tests/test_loader_golden.py compares with fixtures produced by the reference's own classes, tests/golden/loader_*.npz).
 ``gpu_batch(indices)`` runs the front end on the host and hands the per-point work of the whole batch to the HIP chain
 (mm2d3d_amd/dataprep.prepare_batch -> csrc/dataprep.hip); it returns the same batch dict with device tensors.
+``gpu_batch(indices, image="gpu")`` also moves the image half (crop, resize, colour jitter, float conversion, fliplr,
+normalisation) to the GPU (mm2d3d_amd/imageprep.py -> csrc/imageprep.hip); only the decode stays on the host.
 
 File formats (written by the reference's offline preprocessing, lib/dataset/preprocess_nuscenes_lidarseg.py:229-239,
 preprocces_virtual_kitti.py:81-87): ``<split>.pkl`` = pickled list of dicts with ``points [n,3]``, ``pts_cam_coord [n,3]``,
@@ -38,7 +40,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import label_maps, projection
+from . import imageprep, label_maps, projection
 from .color_jitter import ColorJitter
 from .voxelize import augment_and_scale_3d, voxelize_points
 
@@ -181,10 +183,22 @@ class _Scenes:
         return dict(noisy_rot=self.noisy_rot, flip_x=self.flip_x, transl=self.transl,
                     rot_z=self.rot if not self.camera_coords else 0, rot_y=self.rot if self.camera_coords else 0)
 
+    def _open(self, path):
+        """The camera image of a scene: PIL's lazily opened file, or (inside ``gpu_batch(image="gpu")``) an
+        :class:`imageprep.ImagePlan` over it that records the crop / resize of the front end instead of applying it."""
+        from PIL import Image
+
+        img = Image.open(path)
+        return imageprep.ImagePlan(img) if getattr(self, "_plan_images", False) else img
+
+    @staticmethod
+    def _to_float(image):
+        return np.array(image, dtype=np.float32) / 255.0
+
     def _float_image(self, image):
         if self.color_jitter is not None:
             image = self.color_jitter(image)
-        return np.array(image, dtype=np.float32) / 255.0
+        return self._to_float(image)
 
     def _normalise(self, image):
         if self.image_normalizer:
@@ -223,36 +237,61 @@ class _Scenes:
     sample = __getitem__
 
     # ------------------------------------------------------------------ second half on the GPU, whole batch
-    def gpu_batch(self, indices, device="cuda", want_seg2d=False):
+    def gpu_batch(self, indices, device="cuda", want_seg2d=False, image="host", decode_threads=4):
         """``collate_scn_base([self[i] for i in indices])`` with the per-point work on the GPU (csrc/dataprep.hip).  Scene by
-        scene the host runs the front end, the colour jitter / float conversion / normalisation of the image and draws the
-        flip and the 3D augmentation in the reference's order; pixel indices, depth / label maps, flip remap, rotation,
-        voxelisation, range mask, point features and the concatenation run as kernels over the whole batch."""
+        scene the host runs the front end and draws the colour jitter, the flip and the 3D augmentation in the reference's
+        order; pixel indices, depth / label maps, flip remap, rotation, voxelisation, range mask, point features and the
+        concatenation run as kernels over the whole batch.
+
+        ``image="host"``: the crop / resize / colour jitter / float conversion / normalisation of the camera image run on the
+        host with PIL and numpy, scene by scene.  ``image="gpu"``: the front end only records the crop window and the target
+        size (:class:`imageprep.ImagePlan`); after the scene loop the images are decoded on ``decode_threads`` threads, copied
+        to the device at once and prepared by csrc/imageprep.hip - the same batch, bit for bit, and the same numpy / torch
+        RNG states afterwards.  RGB images only."""
         from . import dataprep
 
-        scenes, intrinsics, works = [], [], []
-        for i in indices:
-            w = self._front(i)
-            image = self._float_image(w.image)
-            flip = bool(np.random.rand() < self.fliplr)
-            rot, u = dataprep.augmentation_draws(**self._augmentation())
-            image = self._normalise(image)  # commutes with the flip the GPU applies
-            intr = w.intr
-            if flip:
-                intr = intr.copy()
-                intr[0, 2] = image.shape[1] - intr[0, 2]
-                intr[1, 2] = image.shape[0] - intr[0, 1]
-            if w.label is None:
-                raise ValueError("gpu_batch needs labelled scenes (the 2D label map and seg_label are part of the batch)")
-            if w.points.dtype != np.float32:
-                raise NotImplementedError("gpu_batch voxelises float32 points; this configuration (VirtualKITTI with camera_coords) "
-                                          "produces float64 points in the reference: use the host path")
-            # the kernel truncates float32 pixel coordinates; truncating here first keeps float64 inputs (VirtualKITTI) exact
-            scenes.append(dict(points=np.ascontiguousarray(w.points), points_img=np.trunc(w.pimg), depth=w.cam[:, 2], seg_label=w.label,
-                               img=np.ascontiguousarray(np.moveaxis(image, -1, 0)), draws=(flip, rot, u)))
-            intrinsics.append(intr)
-            works.append(w)
-        batch = dataprep.prepare_batch(scenes, self.scale, self.full_scale, None, 0.0, want_seg2d, device, use_rgb=self.use_rgb)
+        if image not in ("host", "gpu"):
+            raise ValueError(f"gpu_batch: image must be 'host' or 'gpu', not {image!r}")
+        on_gpu = image == "gpu"
+        scenes, intrinsics, works, jitter, flips = [], [], [], [], []
+        self._plan_images = on_gpu
+        try:
+            for i in indices:
+                w = self._front(i)
+                if on_gpu:
+                    jitter.append(self.color_jitter.draw() if self.color_jitter is not None else None)  # where _float_image draws
+                    W, H = w.image.size
+                else:
+                    arr = self._float_image(w.image)
+                    H, W = arr.shape[:2]
+                flip = bool(np.random.rand() < self.fliplr)
+                rot, u = dataprep.augmentation_draws(**self._augmentation())
+                intr = w.intr
+                if flip:
+                    intr = intr.copy()
+                    intr[0, 2] = W - intr[0, 2]
+                    intr[1, 2] = H - intr[0, 1]
+                if w.label is None:
+                    raise ValueError("gpu_batch needs labelled scenes (the 2D label map and seg_label are part of the batch)")
+                if w.points.dtype != np.float32:
+                    raise NotImplementedError("gpu_batch voxelises float32 points; this configuration (VirtualKITTI with camera_coords) "
+                                              "produces float64 points in the reference: use the host path")
+                # the kernel truncates float32 pixel coordinates; truncating here first keeps float64 inputs (VirtualKITTI) exact
+                sc = dict(points=np.ascontiguousarray(w.points), points_img=np.trunc(w.pimg), depth=w.cam[:, 2], seg_label=w.label,
+                          draws=(flip, rot, u))
+                if not on_gpu:
+                    sc["img"] = np.ascontiguousarray(np.moveaxis(self._normalise(arr), -1, 0))  # commutes with the flip the GPU applies
+                scenes.append(sc)
+                intrinsics.append(intr)
+                works.append(w)
+                flips.append(flip)
+        finally:
+            self._plan_images = False
+        img = None
+        if on_gpu:
+            lut = imageprep.lut(self._to_float, self._normalise)
+            img = dataprep.prepare_images([w.image for w in works], jitter, flips, [lut] * len(works), device, decode_threads)
+        batch = dataprep.prepare_batch(scenes, self.scale, self.full_scale, None, 0.0, want_seg2d, device, use_rgb=self.use_rgb, img=img)
         batch["intrinsics"] = torch.from_numpy(np.stack(intrinsics))
         batch["points"] = torch.cat(batch["points"], 0) if batch["points"] else batch["points"]
         batch["coords"] = batch["x"][0][:, :3]
@@ -303,8 +342,6 @@ class NuScenesLidarSegSCN(_Scenes):
                      output_orig)
 
     def _front(self, index):
-        from PIL import Image
-
         d = self.data[index]
         cam = d["pts_cam_coord"].copy()
         points = cam.copy() if self.camera_coords else d["points"].copy()
@@ -312,7 +349,7 @@ class NuScenesLidarSegSCN(_Scenes):
         if self.label_mapping is not None:
             label = self.label_mapping[label]
         w = _Work(points, cam, d["points_img"].copy(), label, d["calib"]["cam_intrinsic"].copy(),
-                  Image.open(os.path.join(self.nuscenes_dir, d["camera_path"])))
+                  self._open(os.path.join(self.nuscenes_dir, d["camera_path"])))
         if self.resize and tuple(w.image.size) != self.resize:
             if not w.image.size[0] > self.resize[0]:
                 raise AssertionError("resize must not enlarge the image")  # :260
@@ -347,8 +384,6 @@ class SemanticKITTISCN(_Scenes):
                      output_orig)
 
     def _front(self, index):
-        from PIL import Image
-
         d = self.data[index]
         cam = d["pts_cam_coord"].copy()
         points = cam.copy() if self.camera_coords else d["points"].copy()
@@ -356,7 +391,7 @@ class SemanticKITTISCN(_Scenes):
         if label is not None:
             label = self.label_mapping[label.astype(np.int64)]
         w = _Work(points, cam, d["points_img"].copy(), label, d["intrinsics"].copy(),
-                  Image.open(os.path.join(self.semantic_kitti_dir, d["camera_path"])))
+                  self._open(os.path.join(self.semantic_kitti_dir, d["camera_path"])))
         _crop(w, self.crop_size, self.bottom_crop, self.rand_crop, d.get("camera_path"))
         return w
 
@@ -423,8 +458,6 @@ class A2D2SCN(_Scenes):
         self._common(scale, full_scale, noisy_rot, flip_x, rot, transl, fliplr, color_jitter, image_normalizer, camera_coords, use_rgb)
 
     def _front(self, index):
-        from PIL import Image
-
         d = self.data[index]
         cam = d["pts_cam_coord"].copy()
         points = cam.copy() if self.camera_coords else d["points"].copy()
@@ -432,7 +465,7 @@ class A2D2SCN(_Scenes):
         if self.label_mapping is not None:
             label = self.label_mapping[label]
         w = _Work(points, cam, d["points_img"].copy(), label, np.array(self.INTRINSICS),
-                  Image.open(os.path.join(self.preprocess_dir, d["camera_path"])))
+                  self._open(os.path.join(self.preprocess_dir, d["camera_path"])))
         if np.random.rand() < self.crop_prob:  # drawn even when cropping is off (a2d2.py:266)
             W, H = w.image.size
             window, mask = _find_window(w, partial(_random_window, self.crop_dims, W, H))
@@ -470,8 +503,6 @@ class VirtualKITTISCN(_Scenes):
         self._common(scale, full_scale, noisy_rot, flip_x, rot, transl, fliplr, color_jitter, image_normalizer, camera_coords, use_rgb)
 
     def _front(self, index):
-        from PIL import Image
-
         d = self.data[index]
         points = d["points"].copy()
         label = d["seg_labels"].astype(np.int64)
@@ -495,7 +526,7 @@ class VirtualKITTISCN(_Scenes):
         if self.random_weather:
             weather = self.random_weather[np.random.randint(len(self.random_weather))]
         path = os.path.join(self.virtual_kitti_dir, "vkitti_1.3.1_rgb", d["scene_id"], weather, d["frame_id"] + ".png")
-        w = _Work(points, cam, pimg, label, self.proj_matrix.copy(), Image.open(path))
+        w = _Work(points, cam, pimg, label, self.proj_matrix.copy(), self._open(path))
         _crop(w, self.crop_size, self.bottom_crop, self.rand_crop, path)
         return w
 

@@ -1,0 +1,119 @@
+"""Host time of ``gpu_batch`` per batch with the image half on the host (PIL + numpy) and on the GPU (csrc/imageprep.hip).
+
+Writes temporary full-size datasets from the miniature ones of tests/golden/mini_ds: nuScenes-shaped (the train_usa pkl with
+``points_img`` scaled to 1600x900, JPEGs re-encoded at 1600x900 q90, resize (400, 225)) and A2D2-shaped (1920x1208 ->
+480x302), and prints one JSON line per dataset: ms per 16-scene ``gpu_batch`` (wall clock, synchronised) for
+``image="host"`` and for ``image="gpu"`` with 1 and 4 decode threads, and the GPU ms of the three image kernels (events).
+
+    python tools/bench_imageprep.py [--scenes 16] [--reps 5] [--kind nuscenes a2d2]
+"""
+import argparse
+import json
+import os
+import pickle
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+MINI = os.path.join(ROOT, "tests", "golden", "mini_ds")
+NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
+KINDS = {  # source size of the miniature images -> full size, network size
+    "nuscenes": dict(full=(1600, 900), resize=(400, 225)),
+    "a2d2": dict(full=(1920, 1208), resize=(480, 302)),
+}
+
+
+def _upscale(src, dst, size, seed):
+    """The miniature image upscaled to ``size`` with some per-pixel noise (texture for the JPEG coder), JPEG q90."""
+    from PIL import Image
+
+    a = np.asarray(Image.open(src).convert("RGB").resize(size, Image.BICUBIC)).astype(np.int16)
+    a = a + np.random.default_rng(seed).integers(-12, 13, a.shape)
+    Image.fromarray(np.clip(a, 0, 255).astype(np.uint8), "RGB").save(dst, quality=90)
+
+
+def make_dataset(root, kind):
+    """Writes the full-size variant of mini_ds/<kind> under ``root``; returns the dataset's constructor keywords."""
+    full = KINDS[kind]["full"]
+    if kind == "nuscenes":
+        src_dir, pkl_rel = os.path.join(MINI, "nuscenes"), "train_usa.pkl"
+    else:
+        src_dir, pkl_rel = os.path.join(MINI, "a2d2"), os.path.join("preprocess", "train.pkl")
+        for f in ("cams_lidars.json", "class_list.json"):
+            shutil.copy(os.path.join(src_dir, f), os.path.join(root, f))
+    with open(os.path.join(src_dir, pkl_rel), "rb") as f:
+        data = pickle.load(f)
+    for k, d in enumerate(data):
+        src = os.path.join(src_dir, d["camera_path"])
+        w0, h0 = __import__("PIL.Image").Image.open(src).size
+        d["points_img"] = (d["points_img"] * np.array([full[1] / h0, full[0] / w0])).astype(d["points_img"].dtype)
+        dst = os.path.join(root, d["camera_path"])
+        os.makedirs(os.path.dirname(dst), exist_ok=True)
+        _upscale(src, dst, full, k)
+    os.makedirs(os.path.dirname(os.path.join(root, pkl_rel)), exist_ok=True)
+    with open(os.path.join(root, pkl_rel), "wb") as f:
+        pickle.dump(data, f)
+    common = dict(resize=KINDS[kind]["resize"], image_normalizer=NORM, fliplr=0.5, color_jitter=(0.4, 0.4, 0.4), use_rgb=True,
+                  noisy_rot=0.1, flip_x=0.5, rot=6.2831, transl=True)
+    if kind == "nuscenes":
+        return "NuScenesLidarSegSCN", dict(split=("train_usa",), preprocess_dir=root, nuscenes_dir=root, merge_classes=True, **common)
+    return "A2D2SCN", dict(split=("train",), preprocess_dir=root, merge_classes=True, **common)
+
+
+def _kernel_ms(ds, indices, device):
+    """GPU ms of the three image kernels for the plans and draws of one batch (events around mm_image_prepare)."""
+    from mm2d3d_amd import dataprep, imageprep
+
+    ds._plan_images = True
+    try:
+        works = [ds._front(i) for i in indices]
+    finally:
+        ds._plan_images = False
+    draws = [ds.color_jitter.draw() for _ in works]
+    flips = [bool(np.random.rand() < ds.fliplr) for _ in works]
+    lut = imageprep.lut(ds._to_float, ds._normalise)
+    timing = {}
+    dataprep.prepare_images([w.image for w in works], draws, flips, [lut] * len(works), device, 4, timing=timing)
+    return timing["kernels_ms"]
+
+
+def main():
+    import torch
+
+    from mm2d3d_amd import datasets
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kind", nargs="+", default=list(KINDS))
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    for kind in args.kind:
+        with tempfile.TemporaryDirectory() as root:
+            cls, kw = make_dataset(root, kind)
+            ds = getattr(datasets, cls)(**kw)
+            indices = [i % len(ds) for i in range(args.scenes)]
+            res = {"kind": kind, "scenes": args.scenes, "full": KINDS[kind]["full"], "resize": KINDS[kind]["resize"]}
+            for name, image, threads in (("host", "host", 1), ("gpu_1thread", "gpu", 1), ("gpu_4threads", "gpu", 4)):
+                times = []
+                for r in range(args.reps + 1):  # the first call warms up
+                    np.random.seed(r)
+                    torch.manual_seed(r)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    ds.gpu_batch(indices, device=dev, want_seg2d=True, image=image, decode_threads=threads)
+                    torch.cuda.synchronize()
+                    if r:
+                        times.append((time.perf_counter() - t0) * 1e3)
+                res[f"{name}_ms"] = round(float(np.median(times)), 2)
+            res["kernels_ms"] = round(float(np.median([_kernel_ms(ds, indices, dev) for _ in range(args.reps + 1)][1:])), 3)
+            print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
