@@ -122,6 +122,13 @@ size_t mm_voxelize_ws_bytes(int64_t n_total, int B);
 int mm_voxelize_batch(const float* points, const int32_t* scene_off_dev, const int32_t* scene_off_host, int B, const float* rot,
                       const double* u, int transl, float scale, int full_scale, int64_t* locs, int32_t* keep, int32_t* counts,
                       float* min_value, double* offset, void* ws, size_t ws_bytes, mm_stream_t stream);
+/* the same for fp64 points (VirtualKITTI with camera_coords: the reference's points are float64 there): the arithmetic of
+ * numpy on float64 arrays (rot fp32, widened exactly; points.rot, * scale, min, translation and + offset in fp64);
+ * scale and min_value fp64; workspace of mm_voxelize_ws_bytes_f64 */
+size_t mm_voxelize_ws_bytes_f64(int64_t n_total, int B);
+int mm_voxelize_batch_f64(const double* points, const int32_t* scene_off_dev, const int32_t* scene_off_host, int B, const float* rot,
+                          const double* u, int transl, double scale, int full_scale, int64_t* locs, int32_t* keep, int32_t* counts,
+                          double* min_value, double* offset, void* ws, size_t ws_bytes, mm_stream_t stream);
 /* points_img [n_total][2] fp32 (row, col), depth_vals [n_total] -> img_indices int64 [n_total][2], depth fp32 [B][H][W],
  * seg2d fp64 [B][H][W] (optional, needs labels); flip [B] bytes (optional); winner int32 [B*H*W] scratch; err: 1 = outside */
 int mm_project_batch(const float* points_img, const float* depth_vals, const int64_t* labels, const int32_t* scene_off_dev,
@@ -131,6 +138,10 @@ int mm_project_batch(const float* points_img, const float* depth_vals, const int
 int mm_collect_points(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bound, const int64_t* locs, const int64_t* img_indices,
                       const int64_t* labels, const float* image, int C, int H, int W, const float* points, int64_t* img_indices_out,
                       int64_t* labels_out, float* feats_out, float* points_out, mm_stream_t stream);
+/* the same with fp64 points and points_out (the kept rows of mm_voxelize_batch_f64) */
+int mm_collect_points_f64(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bound, const int64_t* locs, const int64_t* img_indices,
+                          const int64_t* labels, const float* image, int C, int H, int W, const double* points, int64_t* img_indices_out,
+                          int64_t* labels_out, float* feats_out, double* points_out, mm_stream_t stream);
 
 /* ---------------------------------------------------------------- camera-image preparation (csrc/imageprep.hip)
  * The image half of the loaders' per-sample code for a whole batch, bit-exact with PIL + numpy: the crop and the

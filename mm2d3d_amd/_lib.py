@@ -49,7 +49,10 @@ _PROTOS = {
     "mm_voxelize_ws_bytes": (sz, [i64, i32]),
     "mm_voxelize_batch": (i32, [vp, vp, vp, i32, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mm_project_batch": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mm_voxelize_ws_bytes_f64": (sz, [i64, i32]),
+    "mm_voxelize_batch_f64": (i32, [vp, vp, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mm_collect_points": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "mm_collect_points_f64": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mm_image_prepare": (i32, [vp, i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
     "mm_up_neighbors": (i32, [vp, i64, vp, vp, vp]),
     "mm_os_table_ws_bytes": (sz, [i64, i32]),

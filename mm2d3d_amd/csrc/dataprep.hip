@@ -15,6 +15,11 @@
 // (checked against numpy on 35k points: every bit; the unfused left-to-right sum differs on 26 % of the elements).  The
 // rest follows numpy's dtype rules: float32 for coords, `full_scale - max - 0.001` in float32, the translation in
 // float64 (`clip(..) * rand(3)`), `coords += offset` as float32(double(c) + offset), astype(int64) = truncation.
+// Float64 points (VirtualKITTI with camera_coords: `np.array([-1, -1, 1]) * points` promotes to float64) take the same
+// kernels instantiated for double (the _f64 entries): numpy promotes the float32 rotation to float64 (exact) and runs
+// OpenBLAS dgemm, whose kernels use the same k-order fma form in double; coords, min, `full_scale - max - 0.001`, the
+// translation and `coords += offset` are all float64 (VirtualKITTI's points hold float32 values, so each product is exact
+// in double and only the k order of the sums decides).  The float32 instantiation is the arithmetic described above.
 #pragma clang fp contract(off)
 #include "common.h"
 
@@ -42,26 +47,55 @@ __device__ inline float fatomic_max(float* addr, float v) {
   return __int_as_float(old);
 }
 
-// blockIdx.y = scene; cf = (points . rot) * scale; per-scene min / max of cf
-__global__ __launch_bounds__(T) void k_vox_transform(const float* __restrict__ pts, const int32_t* __restrict__ scene_off,
-                                                      const float* __restrict__ rot, float scale, float* __restrict__ cf,
-                                                      float* __restrict__ minv, float* __restrict__ maxv) {
+__device__ inline double fatomic_min(double* addr, double v) {
+  unsigned long long* a = (unsigned long long*)addr;
+  unsigned long long old = *a;
+  while (__longlong_as_double(old) > v) {
+    unsigned long long assumed = old;
+    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
+    if (old == assumed) break;
+  }
+  return __longlong_as_double(old);
+}
+__device__ inline double fatomic_max(double* addr, double v) {
+  unsigned long long* a = (unsigned long long*)addr;
+  unsigned long long old = *a;
+  while (__longlong_as_double(old) < v) {
+    unsigned long long assumed = old;
+    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
+    if (old == assumed) break;
+  }
+  return __longlong_as_double(old);
+}
+__device__ inline float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ inline double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ inline float min_(float a, float b) { return fminf(a, b); }
+__device__ inline double min_(double a, double b) { return fmin(a, b); }
+__device__ inline float max_(float a, float b) { return fmaxf(a, b); }
+__device__ inline double max_(double a, double b) { return fmax(a, b); }
+
+// blockIdx.y = scene; cf = (points . rot) * scale; per-scene min / max of cf.  P = the points' type (float or double);
+// the float32 rotation is widened exactly to P, as numpy promotes it
+template <typename P>
+__global__ __launch_bounds__(T) void k_vox_transform(const P* __restrict__ pts, const int32_t* __restrict__ scene_off,
+                                                      const float* __restrict__ rot, P scale, P* __restrict__ cf,
+                                                      P* __restrict__ minv, P* __restrict__ maxv) {
   const int b = blockIdx.y;
   const int64_t lo = scene_off[b], hi = scene_off[b + 1];
   const float* r = rot + b * 9;
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  P mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int64_t i = lo + (int64_t)blockIdx.x * T + threadIdx.x; i < hi; i += (int64_t)gridDim.x * T) {
-    const float p0 = pts[i * 3 + 0], p1 = pts[i * 3 + 1], p2 = pts[i * 3 + 2];
+    const P p0 = pts[i * 3 + 0], p1 = pts[i * 3 + 1], p2 = pts[i * 3 + 2];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-      const float y = __builtin_fmaf(p2, r[6 + j], __builtin_fmaf(p1, r[3 + j], p0 * r[j]));
-      const float c = y * scale;
+      const P y = fma_(p2, (P)r[6 + j], fma_(p1, (P)r[3 + j], p0 * (P)r[j]));
+      const P c = y * scale;
       cf[i * 3 + j] = c;
-      mn[j] = fminf(mn[j], c);
-      mx[j] = fmaxf(mx[j], c);
+      mn[j] = min_(mn[j], c);
+      mx[j] = max_(mx[j], c);
     }
   }
-  __shared__ float smn[3][T], smx[3][T];
+  __shared__ P smn[3][T], smx[3][T];
 #pragma unroll
   for (int j = 0; j < 3; j++) smn[j][threadIdx.x] = mn[j], smx[j][threadIdx.x] = mx[j];
   __syncthreads();
@@ -69,8 +103,8 @@ __global__ __launch_bounds__(T) void k_vox_transform(const float* __restrict__ p
     if ((int)threadIdx.x < s) {
 #pragma unroll
       for (int j = 0; j < 3; j++) {
-        smn[j][threadIdx.x] = fminf(smn[j][threadIdx.x], smn[j][threadIdx.x + s]);
-        smx[j][threadIdx.x] = fmaxf(smx[j][threadIdx.x], smx[j][threadIdx.x + s]);
+        smn[j][threadIdx.x] = min_(smn[j][threadIdx.x], smn[j][threadIdx.x + s]);
+        smx[j][threadIdx.x] = max_(smx[j][threadIdx.x], smx[j][threadIdx.x + s]);
       }
     }
     __syncthreads();
@@ -81,25 +115,27 @@ __global__ __launch_bounds__(T) void k_vox_transform(const float* __restrict__ p
   }
 }
 
-// offset[b][j] = transl ? clip(float32(full_scale - (max - min)) - float32(0.001), 0) * u[b][j] : 0   (float64)
-__global__ void k_vox_offset(const float* __restrict__ minv, const float* __restrict__ maxv, const double* __restrict__ u, int transl,
+// offset[b][j] = transl ? clip(P(full_scale - (max - min)) - P(0.001), 0) * u[b][j] : 0   (float64)
+template <typename P>
+__global__ void k_vox_offset(const P* __restrict__ minv, const P* __restrict__ maxv, const double* __restrict__ u, int transl,
                              int full_scale, int B, double* __restrict__ offset) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 3 * B) return;
   double off = 0.0;
   if (transl) {
-    const float mxs = maxv[i] - minv[i];          // (coords - min).max(0): the subtraction is monotone
-    float t = (float)full_scale - mxs;             // python int with a float32 array: float32
-    t = t - 0.001f;                                // python float with a float32 array: float32
-    t = t > 0.f ? t : 0.f;                         // np.clip(a_min=0); NaN cannot occur
+    const P mxs = maxv[i] - minv[i];              // (coords - min).max(0): the subtraction is monotone
+    P t = (P)full_scale - mxs;                     // python int with a P array: P
+    t = t - (P)0.001;                              // python float with a P array: P (float(0.001) == 0.001f)
+    t = t > (P)0 ? t : (P)0;                       // np.clip(a_min=0); NaN cannot occur
     off = (double)t * u[i];
   }
   offset[i] = off;
 }
 
 // integer voxel coordinates + in-range flag of every point (blockIdx.y = scene)
-__global__ __launch_bounds__(T) void k_vox_flags(const float* __restrict__ cf, const int32_t* __restrict__ scene_off,
-                                                  const float* __restrict__ minv, const double* __restrict__ offset, int transl,
+template <typename P>
+__global__ __launch_bounds__(T) void k_vox_flags(const P* __restrict__ cf, const int32_t* __restrict__ scene_off,
+                                                  const P* __restrict__ minv, const double* __restrict__ offset, int transl,
                                                   int full_scale, int32_t* __restrict__ ic, int32_t* __restrict__ flag) {
   const int b = blockIdx.y;
   const int64_t lo = scene_off[b], hi = scene_off[b + 1];
@@ -107,8 +143,8 @@ __global__ __launch_bounds__(T) void k_vox_flags(const float* __restrict__ cf, c
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-      float c = cf[i * 3 + j] - minv[b * 3 + j];
-      if (transl) c = (float)((double)c + offset[b * 3 + j]);
+      P c = cf[i * 3 + j] - minv[b * 3 + j];
+      if (transl) c = (P)((double)c + offset[b * 3 + j]);  // float32: float32(double(c) + offset); float64: c + offset
       const long long v = (long long)c;  // astype(int64): truncation toward zero
       ok = ok && v >= 0 && v < full_scale;
       ic[i * 3 + j] = (int32_t)(v < -2147483647LL ? -2147483647LL : v > 2147483647LL ? 2147483647LL : v);
@@ -174,12 +210,13 @@ __global__ __launch_bounds__(T) void k_proj_fill(const int32_t* __restrict__ win
   if (seg2d) seg2d[p] = w >= 0 ? (double)labels[w] : -100.0;
 }
 
-// the per-point arrays of the kept rows: image indices, labels, RGB features img[b, :, r, c]
+// the per-point arrays of the kept rows: image indices, labels, RGB features img[b, :, r, c], points (P = their type)
+template <typename P>
 __global__ __launch_bounds__(T) void k_collect(const int32_t* __restrict__ keep, const int32_t* __restrict__ n_keep, int64_t n_bound,
                                                 const int64_t* __restrict__ locs, const int64_t* __restrict__ img_indices,
                                                 const int64_t* __restrict__ labels, const float* __restrict__ image, int C, int H, int W,
-                                                const float* __restrict__ points, int64_t* __restrict__ idx_out,
-                                                int64_t* __restrict__ lab_out, float* __restrict__ feats, float* __restrict__ pts_out) {
+                                                const P* __restrict__ points, int64_t* __restrict__ idx_out,
+                                                int64_t* __restrict__ lab_out, float* __restrict__ feats, P* __restrict__ pts_out) {
   const int64_t p = (int64_t)blockIdx.x * T + threadIdx.x;
   if (p >= n_bound || p >= (int64_t)*n_keep) return;
   const int i = keep[p];
@@ -204,13 +241,83 @@ inline unsigned scene_blocks(const int32_t* off_host, int B) {
   int64_t g = mm_cdiv(mx, (int64_t)T * 4);
   return (unsigned)(g < 1 ? 1 : g > 1024 ? 1024 : g);
 }
+
+__global__ void k_minmax_init(double* __restrict__ minv, double* __restrict__ maxv, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) minv[i] = INFINITY, maxv[i] = -INFINITY;
+}
+
+// +inf / -inf as the identities of min / max
+inline int minmax_init(float* minv, float* maxv, int B, hipStream_t s) {
+  MM_HIP(hipMemsetD32Async((hipDeviceptr_t)minv, 0x7F800000, (size_t)B * 3, s));
+  MM_HIP(hipMemsetD32Async((hipDeviceptr_t)maxv, 0xFF800000, (size_t)B * 3, s));
+  return MM_OK;
+}
+inline int minmax_init(double* minv, double* maxv, int B, hipStream_t s) {
+  hipLaunchKernelGGL(k_minmax_init, dim3((unsigned)mm_cdiv(3 * B, 64)), dim3(64), 0, s, minv, maxv, 3 * B);
+  return MM_OK;
+}
+
+template <typename P>
+size_t voxelize_ws_bytes(int64_t n_total, int B) {
+  return mm_align((size_t)n_total * 3 * sizeof(P)) + mm_align((size_t)n_total * 3 * 4) + mm_align((size_t)(n_total + 1) * 4) * 2 +
+         mm_align((size_t)B * 3 * sizeof(P)) + mm_scan_ws_bytes(n_total + 1) + 1024;
+}
+
+template <typename P>
+int voxelize_batch(const P* points, const int32_t* scene_off_dev, const int32_t* scene_off_host, int B, const float* rot, const double* u,
+                   int transl, P scale, int full_scale, int64_t* locs, int32_t* keep, int32_t* counts, P* min_value, double* offset,
+                   void* ws, size_t ws_bytes, hipStream_t s) {
+  MM_CHECK_ARG(B > 0 && B <= 65535 && full_scale > 0 && points && rot && locs && keep && counts && min_value && offset,
+               "voxelize_batch: bad arguments");
+  const int64_t n = scene_off_host[B];
+  MMArena ar(ws, ws_bytes);
+  P* cf = ar.take<P>(n * 3 + 1);
+  int32_t* ic = ar.take<int32_t>(n * 3 + 1);
+  int32_t* flag = ar.take<int32_t>(n + 1);
+  int32_t* pos = ar.take<int32_t>(n + 1);
+  P* maxv = ar.take<P>(B * 3);
+  const size_t sws = mm_scan_ws_bytes(n + 1);
+  char* scan_ws = ar.take<char>(sws);
+  if (!cf || !ic || !flag || !pos || !maxv || !scan_ws) {
+    mm_set_error("voxelize_batch: workspace too small (%zu < %zu)", ws_bytes, voxelize_ws_bytes<P>(n, B));
+    return MM_ERR_WORKSPACE;
+  }
+  int rc = minmax_init(min_value, maxv, B, s);
+  if (rc) return rc;
+  const unsigned g = scene_blocks(scene_off_host, B);
+  if (n > 0)
+    hipLaunchKernelGGL(k_vox_transform<P>, dim3(g, B), dim3(T), 0, s, points, scene_off_dev, rot, scale, cf, min_value, maxv);
+  hipLaunchKernelGGL(k_vox_offset<P>, dim3((unsigned)mm_cdiv(3 * B, 64)), dim3(64), 0, s, min_value, maxv, u, transl, full_scale, B, offset);
+  if (n > 0)
+    hipLaunchKernelGGL(k_vox_flags<P>, dim3(g, B), dim3(T), 0, s, cf, scene_off_dev, min_value, offset, transl, full_scale, ic, flag);
+  rc = mm_exclusive_scan_i32(flag, pos, n, pos + n, scan_ws, sws, s);
+  if (rc) return rc;
+  const int64_t nthreads = n > B ? n : B;
+  hipLaunchKernelGGL(k_vox_emit, dim3((unsigned)mm_cdiv(nthreads, T)), dim3(T), 0, s, ic, flag, pos, scene_off_dev, B, n, locs, keep, counts);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+template <typename P>
+int collect_points(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bound, const int64_t* locs, const int64_t* img_indices,
+                   const int64_t* labels, const float* image, int C, int H, int W, const P* points, int64_t* img_indices_out,
+                   int64_t* labels_out, float* feats_out, P* points_out, hipStream_t s) {
+  MM_CHECK_ARG(keep && n_keep_dev && locs && img_indices && img_indices_out, "collect_points: bad arguments");
+  MM_CHECK_ARG(!feats_out || image, "collect_points: feats need the image");
+  MM_CHECK_ARG(!points_out || points, "collect_points: points_out needs the points");
+  if (n_bound == 0) return MM_OK;
+  hipLaunchKernelGGL(k_collect<P>, dim3((unsigned)mm_cdiv(n_bound, T)), dim3(T), 0, s, keep, n_keep_dev, n_bound, locs, img_indices, labels,
+                     image, C, H, W, points, img_indices_out, labels_out, feats_out, points_out);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
 }  // namespace
 
 extern "C" {
 
-size_t mm_voxelize_ws_bytes(int64_t n_total, int B) {
-  return mm_align((size_t)n_total * 3 * 4) * 2 + mm_align((size_t)(n_total + 1) * 4) * 2 + mm_align((size_t)B * 3 * 4) + mm_scan_ws_bytes(n_total + 1) + 1024;
-}
+size_t mm_voxelize_ws_bytes(int64_t n_total, int B) { return voxelize_ws_bytes<float>(n_total, B); }
+size_t mm_voxelize_ws_bytes_f64(int64_t n_total, int B) { return voxelize_ws_bytes<double>(n_total, B); }
 
 // points [n_total][3] fp32 (the scenes of a batch back to back, scene b = rows scene_off[b] .. scene_off[b+1]),
 // rot [B][9] fp32 row-major, u [B][3] fp64 = the np.random.rand(3) draw of each scene (ignored unless transl)
@@ -219,36 +326,16 @@ size_t mm_voxelize_ws_bytes(int64_t n_total, int B) {
 int mm_voxelize_batch(const float* points, const int32_t* scene_off_dev, const int32_t* scene_off_host, int B, const float* rot,
                       const double* u, int transl, float scale, int full_scale, int64_t* locs, int32_t* keep, int32_t* counts,
                       float* min_value, double* offset, void* ws, size_t ws_bytes, hipStream_t s) {
-  MM_CHECK_ARG(B > 0 && B <= 65535 && full_scale > 0 && points && rot && locs && keep && counts && min_value && offset,
-               "voxelize_batch: bad arguments");
-  const int64_t n = scene_off_host[B];
-  MMArena ar(ws, ws_bytes);
-  float* cf = ar.take<float>(n * 3 + 1);
-  int32_t* ic = ar.take<int32_t>(n * 3 + 1);
-  int32_t* flag = ar.take<int32_t>(n + 1);
-  int32_t* pos = ar.take<int32_t>(n + 1);
-  float* maxv = ar.take<float>(B * 3);
-  const size_t sws = mm_scan_ws_bytes(n + 1);
-  char* scan_ws = ar.take<char>(sws);
-  if (!cf || !ic || !flag || !pos || !maxv || !scan_ws) {
-    mm_set_error("voxelize_batch: workspace too small (%zu < %zu)", ws_bytes, mm_voxelize_ws_bytes(n, B));
-    return MM_ERR_WORKSPACE;
-  }
-  // +inf / -inf as the identities of min / max
-  MM_HIP(hipMemsetD32Async((hipDeviceptr_t)min_value, 0x7F800000, (size_t)B * 3, s));
-  MM_HIP(hipMemsetD32Async((hipDeviceptr_t)maxv, 0xFF800000, (size_t)B * 3, s));
-  const unsigned g = scene_blocks(scene_off_host, B);
-  if (n > 0)
-    hipLaunchKernelGGL(k_vox_transform, dim3(g, B), dim3(T), 0, s, points, scene_off_dev, rot, scale, cf, min_value, maxv);
-  hipLaunchKernelGGL(k_vox_offset, dim3((unsigned)mm_cdiv(3 * B, 64)), dim3(64), 0, s, min_value, maxv, u, transl, full_scale, B, offset);
-  if (n > 0)
-    hipLaunchKernelGGL(k_vox_flags, dim3(g, B), dim3(T), 0, s, cf, scene_off_dev, min_value, offset, transl, full_scale, ic, flag);
-  int rc = mm_exclusive_scan_i32(flag, pos, n, pos + n, scan_ws, sws, s);
-  if (rc) return rc;
-  const int64_t nthreads = n > B ? n : B;
-  hipLaunchKernelGGL(k_vox_emit, dim3((unsigned)mm_cdiv(nthreads, T)), dim3(T), 0, s, ic, flag, pos, scene_off_dev, B, n, locs, keep, counts);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
+  return voxelize_batch<float>(points, scene_off_dev, scene_off_host, B, rot, u, transl, scale, full_scale, locs, keep, counts, min_value,
+                               offset, ws, ws_bytes, s);
+}
+
+// the same for fp64 points: scale and min_value fp64, rot still fp32 (widened exactly), ws of mm_voxelize_ws_bytes_f64
+int mm_voxelize_batch_f64(const double* points, const int32_t* scene_off_dev, const int32_t* scene_off_host, int B, const float* rot,
+                          const double* u, int transl, double scale, int full_scale, int64_t* locs, int32_t* keep, int32_t* counts,
+                          double* min_value, double* offset, void* ws, size_t ws_bytes, hipStream_t s) {
+  return voxelize_batch<double>(points, scene_off_dev, scene_off_host, B, rot, u, transl, scale, full_scale, locs, keep, counts, min_value,
+                                offset, ws, ws_bytes, s);
 }
 
 // points_img [n_total][2] fp32 (row, col) already scaled to the network image, depth_vals [n_total] (camera z), labels may be
@@ -275,13 +362,16 @@ int mm_project_batch(const float* points_img, const float* depth_vals, const int
 int mm_collect_points(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bound, const int64_t* locs, const int64_t* img_indices,
                       const int64_t* labels, const float* image, int C, int H, int W, const float* points, int64_t* img_indices_out,
                       int64_t* labels_out, float* feats_out, float* points_out, hipStream_t s) {
-  MM_CHECK_ARG(keep && n_keep_dev && locs && img_indices && img_indices_out, "collect_points: bad arguments");
-  MM_CHECK_ARG(!feats_out || image, "collect_points: feats need the image");
-  if (n_bound == 0) return MM_OK;
-  hipLaunchKernelGGL(k_collect, dim3((unsigned)mm_cdiv(n_bound, T)), dim3(T), 0, s, keep, n_keep_dev, n_bound, locs, img_indices, labels,
-                     image, C, H, W, points, img_indices_out, labels_out, feats_out, points_out);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
+  return collect_points<float>(keep, n_keep_dev, n_bound, locs, img_indices, labels, image, C, H, W, points, img_indices_out, labels_out,
+                               feats_out, points_out, s);
+}
+
+// the same with fp64 points (and fp64 points_out)
+int mm_collect_points_f64(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bound, const int64_t* locs, const int64_t* img_indices,
+                          const int64_t* labels, const float* image, int C, int H, int W, const double* points, int64_t* img_indices_out,
+                          int64_t* labels_out, float* feats_out, double* points_out, hipStream_t s) {
+  return collect_points<double>(keep, n_keep_dev, n_bound, locs, img_indices, labels, image, C, H, W, points, img_indices_out, labels_out,
+                                feats_out, points_out, s);
 }
 
 }  // extern "C"

@@ -54,12 +54,15 @@ def _offsets(lengths, dev):
 
 
 def voxelize_batch(points, lengths, rots, us, scale=20, full_scale=4096):
-    """points fp32 [n_total,3] on the GPU (scenes back to back), lengths = points per scene, rots / us = the per-scene
-    draws of :func:`augmentation_draws`.  Returns dict(locs int64 [kept,4], keep int32 [kept], counts list, min_value
-    fp32 [B,3], offset fp64 [B,3]); one small device->host copy (the kept counts) sizes the outputs."""
+    """points fp32 or fp64 [n_total,3] on the GPU (scenes back to back), lengths = points per scene, rots / us = the
+    per-scene draws of :func:`augmentation_draws`.  Returns dict(locs int64 [kept,4], keep int32 [kept], counts list,
+    min_value [B,3] of the points' dtype, offset fp64 [B,3]); one small device->host copy (the kept counts) sizes the
+    outputs.  fp64 points (VirtualKITTI with camera_coords) follow numpy's float64 arithmetic (mm_voxelize_batch_f64)."""
     _lib.require_cuda(points, "points")
-    if points.dtype != torch.float32:
-        raise TypeError("voxelize_batch: points must be float32 (the dtype the reference's pickles hold)")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError("voxelize_batch: points must be float32 (the dtype the reference's pickles hold) or float64 (VirtualKITTI "
+                        "with camera_coords)")
+    f64 = points.dtype == torch.float64
     L = _lib.lib()
     dev = points.device
     points = points.contiguous()
@@ -74,12 +77,12 @@ def voxelize_batch(points, lengths, rots, us, scale=20, full_scale=4096):
     locs = torch.empty((n, 4), dtype=torch.int64, device=dev)
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     counts = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    minv = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    minv = torch.empty((B, 3), dtype=points.dtype, device=dev)
     offset = torch.empty((B, 3), dtype=torch.float64, device=dev)
-    ws = _lib.workspace.get(int(L.mm_voxelize_ws_bytes(n, B)), dev)
-    check(L.mm_voxelize_batch(ptr(points), ptr(off_d), off_h.ctypes.data, B, ptr(rot_d), ptr(u_d), 1 if transl else 0, float(scale),
-                              int(full_scale), ptr(locs), ptr(keep), ptr(counts), ptr(minv), ptr(offset), ptr(ws), ws.numel(), stream()),
-          "voxelize_batch")
+    ws_bytes, run = (L.mm_voxelize_ws_bytes_f64, L.mm_voxelize_batch_f64) if f64 else (L.mm_voxelize_ws_bytes, L.mm_voxelize_batch)
+    ws = _lib.workspace.get(int(ws_bytes(n, B)), dev)
+    check(run(ptr(points), ptr(off_d), off_h.ctypes.data, B, ptr(rot_d), ptr(u_d), 1 if transl else 0, float(scale), int(full_scale),
+              ptr(locs), ptr(keep), ptr(counts), ptr(minv), ptr(offset), ptr(ws), ws.numel(), stream()), "voxelize_batch")
     ch = counts.cpu().tolist()  # the only read-back: how many points survived the range mask
     kept = ch[B]
     return dict(locs=locs[:kept], keep=keep[:kept], counts=ch[:B], counts_dev=counts, min_value=minv, offset=offset,
@@ -149,8 +152,8 @@ def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0
                   img=None):
     """The reference's ``__getitem__`` (per scene) + ``collate_scn_base`` for a list of decoded scenes, on the GPU.
 
-    Each scene: dict(points [n,3] f32 = the coordinates that are voxelised (camera or LiDAR frame, as the dataset is
-    configured), points_img [n,2] (row, col) scaled to the network image, depth [n] = camera z, seg_label [n] int64,
+    Each scene: dict(points [n,3] f32 (or f64 in every scene of the batch) = the coordinates that are voxelised (camera or
+    LiDAR frame, as the dataset is configured), points_img [n,2] (row, col) scaled to the network image, depth [n] = camera z, seg_label [n] int64,
     img [3,H,W] f32 already normalised and, when this scene's fliplr draw says so, NOT yet flipped).  RNG draws per
     scene in the reference's order: fliplr ``rand()`` first (nuscenes_dataloader.py:291), then ``augment_and_scale_3d``'s;
     a scene that carries ``draws = (flip, rot, u)`` was drawn by the caller (datasets.gpu_batch draws scene by scene, between
@@ -175,7 +178,13 @@ def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0
         rots.append(r)
         us.append(u)
     cat = lambda key, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(s[key]) for s in scenes], 0).astype(dt))).to(dev)
-    pts = cat("points", np.float32)
+    # float64 points (VirtualKITTI with camera_coords) stay float64 and take the fp64 kernels; any other dtype is voxelised as float32
+    f64 = [np.asarray(s["points"]).dtype == np.float64 for s in scenes]
+    if any(f64) and not all(f64):
+        raise ValueError("prepare_batch: the scenes of one batch must all have float64 points or none (the reference voxelises "
+                         "float64 and float32 points with different arithmetic)")
+    pdt = np.float64 if any(f64) else np.float32
+    pts = cat("points", pdt)
     pimg = cat("points_img", np.float32)
     dvals = cat("depth", np.float32)
     labels = cat("seg_label", np.int64)
@@ -192,9 +201,10 @@ def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0
     idx = torch.empty((kept, 2), dtype=torch.int64, device=dev)
     lab = torch.empty(kept, dtype=torch.int64, device=dev)
     feats = torch.empty((kept, img.shape[1]), dtype=torch.float32, device=dev) if use_rgb else None
-    pkept = torch.empty((kept, 3), dtype=torch.float32, device=dev)
-    check(L.mm_collect_points(ptr(vox["keep"]), ptr(vox["counts_dev"][B:]), kept, ptr(vox["locs"]), ptr(idx_all), ptr(labels), ptr(img.contiguous()),
-                              img.shape[1], H, W, ptr(pts), ptr(idx), ptr(lab), ptr(feats), ptr(pkept), stream()), "collect_points")
+    pkept = torch.empty((kept, 3), dtype=pts.dtype, device=dev)
+    collect = L.mm_collect_points_f64 if pts.dtype == torch.float64 else L.mm_collect_points
+    check(collect(ptr(vox["keep"]), ptr(vox["counts_dev"][B:]), kept, ptr(vox["locs"]), ptr(idx_all), ptr(labels), ptr(img.contiguous()),
+                  img.shape[1], H, W, ptr(pts), ptr(idx), ptr(lab), ptr(feats), ptr(pkept), stream()), "collect_points")
     if int(err.item()) != 0:
         raise AssertionError("projected point outside the image (nuscenes_dataloader.py:279-283)")
     bounds = np.concatenate([[0], np.cumsum(vox["counts"])])

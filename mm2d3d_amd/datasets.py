@@ -247,7 +247,11 @@ class _Scenes:
         host with PIL and numpy, scene by scene.  ``image="gpu"``: the front end only records the crop window and the target
         size (:class:`imageprep.ImagePlan`); after the scene loop the images are decoded on ``decode_threads`` threads, copied
         to the device at once and prepared by csrc/imageprep.hip - the same batch, bit for bit, and the same numpy / torch
-        RNG states afterwards.  RGB images only."""
+        RNG states afterwards.  RGB images only.
+
+        Float64 points (VirtualKITTI with ``camera_coords``: the reference's camera-frame points are float64) are voxelised
+        with numpy's float64 arithmetic by the fp64 kernels; the batch's ``points`` and ``min_values`` are then float64,
+        as in the host path."""
         from . import dataprep
 
         if image not in ("host", "gpu"):
@@ -273,9 +277,6 @@ class _Scenes:
                     intr[1, 2] = H - intr[0, 1]
                 if w.label is None:
                     raise ValueError("gpu_batch needs labelled scenes (the 2D label map and seg_label are part of the batch)")
-                if w.points.dtype != np.float32:
-                    raise NotImplementedError("gpu_batch voxelises float32 points; this configuration (VirtualKITTI with camera_coords) "
-                                              "produces float64 points in the reference: use the host path")
                 # the kernel truncates float32 pixel coordinates; truncating here first keeps float64 inputs (VirtualKITTI) exact
                 sc = dict(points=np.ascontiguousarray(w.points), points_img=np.trunc(w.pimg), depth=w.cam[:, 2], seg_label=w.label,
                           draws=(flip, rot, u))

@@ -5,7 +5,13 @@ Writes temporary full-size datasets from the miniature ones of tests/golden/mini
 480x302), and prints one JSON line per dataset: ms per 16-scene ``gpu_batch`` (wall clock, synchronised) for
 ``image="host"`` and for ``image="gpu"`` with 1 and 4 decode threads, and the GPU ms of the three image kernels (events).
 
-    python tools/bench_imageprep.py [--scenes 16] [--reps 5] [--kind nuscenes a2d2]
+``vkitti``: the source domain of the vkitti -> skitti experiment (VirtualKITTISCN with camera_coords, so float64 points;
+downsample 10000, 1242x375 PNGs, bottom crop (480, 302), fliplr, colour jitter, the 3D augmentation, use_rgb=False) on
+synthetic scenes of 20-40k points inside the camera's frustum.  Its line adds ``loader_ms``, the host loader plus
+``collate_scn_base`` (``[ds[i] for i in indices]``), and ``voxelize_ms``, the GPU ms of ``dataprep.voxelize_batch`` on the
+batch's float64 points (events; the fp64 voxeliser kernels and the read-back of the kept counts) in place of ``kernels_ms``.
+
+    python tools/bench_imageprep.py [--scenes 16] [--reps 5] [--kind nuscenes a2d2 vkitti]
 """
 import argparse
 import json
@@ -25,7 +31,9 @@ NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 KINDS = {  # source size of the miniature images -> full size, network size
     "nuscenes": dict(full=(1600, 900), resize=(400, 225)),
     "a2d2": dict(full=(1920, 1208), resize=(480, 302)),
+    "vkitti": dict(full=(1242, 375), resize=(480, 302)),  # resize = the bottom crop
 }
+VKITTI_PROJ = ((725.0, 0.0, 620.5), (0.0, 725.0, 187.0))  # VirtualKITTISCN.proj_matrix
 
 
 def _upscale(src, dst, size, seed):
@@ -37,8 +45,44 @@ def _upscale(src, dst, size, seed):
     Image.fromarray(np.clip(a, 0, 255).astype(np.uint8), "RGB").save(dst, quality=90)
 
 
+def make_vkitti(root, n_scenes=16, seed=0):
+    """A VirtualKITTI-format dataset of ``n_scenes`` synthetic scenes: 20-40k LiDAR points each, placed by drawing a pixel
+    and a depth and back-projecting through the fixed camera (so every point projects inside the 1242x375 image; most land
+    in the rows a bottom crop keeps), labels with some 99s, and one noisy PNG per scene and weather."""
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    W, H = KINDS["vkitti"]["full"]
+    (fx, _, cx), (_, fy, cy) = VKITTI_PROJ
+    data = []
+    for i in range(n_scenes):
+        n = int(rng.integers(20000, 40001))
+        u = rng.uniform(1.0, W - 1.0, n)
+        v = np.where(rng.random(n) < 0.9, rng.uniform(H - 300.0, H - 1.0, n), rng.uniform(1.0, H - 1.0, n))
+        x = rng.uniform(4.0, 80.0, n)
+        pts = np.stack([x, -(u - cx) / fx * x, -(v - cy) / fy * x], 1).astype(np.float32)
+        labels = rng.integers(0, 14, n).astype(np.uint8)
+        labels[rng.random(n) < 0.03] = 99
+        scene, frame = f"{i // 4 + 1:04d}", f"{i:05d}"
+        base = np.kron(rng.integers(0, 256, (-(-H // 25), -(-W // 25), 3)), np.ones((25, 25, 1), np.int16))[:H, :W]
+        for weather in ("clone", "fog"):
+            d = os.path.join(root, "vkitti_1.3.1_rgb", scene, weather)
+            os.makedirs(d, exist_ok=True)
+            img = np.clip(base + rng.integers(-10, 11, base.shape), 0, 255).astype(np.uint8)
+            Image.fromarray(img, "RGB").save(os.path.join(d, frame + ".png"), compress_level=1)
+        data.append({"points": pts, "seg_labels": labels, "scene_id": scene, "frame_id": frame})
+    with open(os.path.join(root, "train.pkl"), "wb") as f:
+        pickle.dump(data, f)
+    return "VirtualKITTISCN", dict(split=("train",), preprocess_dir=root, virtual_kitti_dir=root, merge_classes=True,
+                                   merge_classes_style="VirtualKITTI", downsample=(10000,), crop_size=KINDS["vkitti"]["resize"],
+                                   bottom_crop=True, fliplr=0.5, color_jitter=(0.4, 0.4, 0.4), random_weather=("clone", "fog"),
+                                   camera_coords=True, use_rgb=False, noisy_rot=0.1, flip_x=0.5, rot=6.2831, transl=True)
+
+
 def make_dataset(root, kind):
     """Writes the full-size variant of mini_ds/<kind> under ``root``; returns the dataset's constructor keywords."""
+    if kind == "vkitti":
+        return make_vkitti(root)
     full = KINDS[kind]["full"]
     if kind == "nuscenes":
         src_dir, pkl_rel = os.path.join(MINI, "nuscenes"), "train_usa.pkl"
@@ -82,6 +126,38 @@ def _kernel_ms(ds, indices, device):
     return timing["kernels_ms"]
 
 
+def _voxelize_ms(ds, indices, device):
+    """GPU ms of ``dataprep.voxelize_batch`` on the points of one batch (host front end and draws as gpu_batch makes them)."""
+    import torch
+
+    from mm2d3d_amd import dataprep
+
+    works = [ds._front(i) for i in indices]
+    draws = [dataprep.augmentation_draws(**ds._augmentation()) for _ in works]
+    pts = torch.from_numpy(np.concatenate([w.points for w in works])).to(device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    torch.cuda.synchronize()
+    ev[0].record()
+    dataprep.voxelize_batch(pts, [len(w.points) for w in works], [r for r, _ in draws], [u for _, u in draws], ds.scale, ds.full_scale)
+    ev[1].record()
+    ev[1].synchronize()
+    return ev[0].elapsed_time(ev[1])
+
+
+def _loader_ms(ds, indices, reps):
+    """Host loader plus collate (the reference's DataLoader work for one batch, in one process)."""
+    from mm2d3d_amd.datasets import collate_scn_base
+
+    times = []
+    for r in range(reps + 1):
+        np.random.seed(r)
+        t0 = time.perf_counter()
+        collate_scn_base([ds[i] for i in indices], output_orig=False)
+        if r:
+            times.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(times)), 2)
+
+
 def main():
     import torch
 
@@ -99,6 +175,8 @@ def main():
             ds = getattr(datasets, cls)(**kw)
             indices = [i % len(ds) for i in range(args.scenes)]
             res = {"kind": kind, "scenes": args.scenes, "full": KINDS[kind]["full"], "resize": KINDS[kind]["resize"]}
+            if kind == "vkitti":
+                res["loader_ms"] = _loader_ms(ds, indices, args.reps)
             for name, image, threads in (("host", "host", 1), ("gpu_1thread", "gpu", 1), ("gpu_4threads", "gpu", 4)):
                 times = []
                 for r in range(args.reps + 1):  # the first call warms up
@@ -111,7 +189,9 @@ def main():
                     if r:
                         times.append((time.perf_counter() - t0) * 1e3)
                 res[f"{name}_ms"] = round(float(np.median(times)), 2)
-            res["kernels_ms"] = round(float(np.median([_kernel_ms(ds, indices, dev) for _ in range(args.reps + 1)][1:])), 3)
+            gpu_ms = _voxelize_ms if kind == "vkitti" else _kernel_ms
+            key = "voxelize_ms" if kind == "vkitti" else "kernels_ms"
+            res[key] = round(float(np.median([gpu_ms(ds, indices, dev) for _ in range(args.reps + 1)][1:])), 3)
             print(json.dumps(res), flush=True)
 
 
