@@ -166,6 +166,37 @@ int mm_image_prepare(const uint8_t* src, int64_t src_bytes, const int64_t* desc_
                      const int32_t* coef, int64_t coef_len, const float* factors, const float* lut, uint8_t* tmp, int64_t tmp_bytes,
                      uint8_t* mid, int64_t* sums, float* img, mm_stream_t stream);
 
+/* ---------------------------------------------------------------- baseline-JPEG decode (csrc/jpeg.hip)
+ * The camera JPEGs of a batch decoded on the GPU into the source buffer mm_image_prepare reads, bit-exact with Pillow's
+ * libjpeg-turbo (np.asarray(Image.open(path))): jdhuff.c Huffman decode, DC prediction, jidctint.c jpeg_idct_islow,
+ * jdsample.c fancy upsampling, jdcolor.c ycc_rgb_convert.  Eligible files only (mm2d3d_amd/jpeg.py parse): SOF0/SOF1, 8-bit,
+ * Huffman, three YCbCr components in one interleaved scan, luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1, any restart interval.
+ *   data       device uint8, the files' bytes (headers included), data_bytes long (< 2^31)
+ *   desc       int64 [B][32] per image, device copy and host copy (the host copy is checked against the buffer sizes):
+ *              MM_JPG_SEG_OFF 0, MM_JPG_SEG_LEN 1 byte range of the entropy-coded segment in data (SOS end .. EOI)
+ *              MM_JPG_W 2, MM_JPG_H 3 image size        MM_JPG_HS 4, MM_JPG_VS 5 luma sampling factors
+ *              MM_JPG_MCUS_X 6, MM_JPG_MCUS_Y 7 MCUs per row / column        MM_JPG_RESTART 8 MCUs per restart interval (0: none)
+ *              MM_JPG_N_IV 9 restart intervals, MM_JPG_IV0 10 the first one's index in the batch
+ *              MM_JPG_SUB0 11, MM_JPG_SUB_CAP 12 decoding lanes (>= ceil(SEG_LEN * 8 / 2048) + N_IV)
+ *              MM_JPG_BLK0 13 first block (8x8 coefficients) in the batch  MM_JPG_PLANE_OFF 14 byte offset of the component planes
+ *              MM_JPG_OUT_OFF 15 byte offset of the [H][W][3] RGB image in out
+ *              MM_JPG_QT0..2 16-18 quantisation table (qt row), MM_JPG_DC0..2 19-21, MM_JPG_AC0..2 22-24 Huffman table (huff
+ *              row) of Y, Cb, Cr; words 25-31 reserved (0).  Images share no interval, lane, block, plane or data range.
+ *   huff       device int32 [n_huff][1024]: fast[512] = length << 8 | symbol for codes of at most 9 bits, libjpeg's maxcode[18]
+ *              and valoffset[18], huffval[256]       qt device int32 [n_qt][64], natural order
+ *   out        device uint8, out_bytes long          status device int32 [B], written by the kernels:
+ *              MM_JPG_ST_* bits, 0 = decoded; read it after the stream has run.  No kernel reads or writes outside the buffers.
+ *   ws         device scratch of mm_jpeg_ws_bytes(B, data_bytes, total intervals, total lanes, total blocks, plane bytes)
+ *              (totals = max over images of IV0 + N_IV, SUB0 + SUB_CAP, BLK0 + blocks, PLANE_OFF + plane bytes) */
+#define MM_JPG_ST_MARKER 1     /* a marker other than RST0-7 inside the entropy-coded segment */
+#define MM_JPG_ST_RESTART 2    /* restart markers missing, extra or out of sequence */
+#define MM_JPG_ST_HUFFMAN 4    /* a bit pattern that is no code of the Huffman table */
+#define MM_JPG_ST_INCOMPLETE 8 /* an interval's data ended before its blocks were complete */
+size_t mm_jpeg_ws_bytes(int B, int64_t data_bytes, int64_t n_intervals, int64_t n_lanes, int64_t n_blocks, int64_t plane_bytes);
+int mm_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* desc_dev, const int64_t* desc_host, int B, const int32_t* huff,
+                   int64_t n_huff, const int32_t* qt, int64_t n_qt, uint8_t* out, int64_t out_bytes, int32_t* status, void* ws,
+                   size_t ws_bytes, mm_stream_t stream);
+
 /* ---------------------------------------------------------------- sparse convolution engines (csrc/spconv.hip)
  * scn.SubmanifoldConvolution / Convolution / Deconvolution forward and backward. */
 size_t mm_spconv_ws_bytes(int64_t n_rules, int Cin, int Cout, int K);

@@ -54,6 +54,8 @@ _PROTOS = {
     "mm_collect_points": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mm_collect_points_f64": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mm_image_prepare": (i32, [vp, i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "mm_jpeg_ws_bytes": (sz, [i32, i64, i64, i64, i64, i64]),
+    "mm_jpeg_decode": (i32, [vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, i64, vp, vp, sz, vp]),
     "mm_up_neighbors": (i32, [vp, i64, vp, vp, vp]),
     "mm_os_table_ws_bytes": (sz, [i64, i32]),
     "mm_os_table_build": (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, sz, vp]),

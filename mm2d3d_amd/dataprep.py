@@ -18,6 +18,8 @@ device, bit-identical to the host restatement (mm2d3d_amd/projection.py + synthe
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -111,12 +113,78 @@ def project_batch(points_img, depth_vals, labels, lengths, H, W, flips=None, wan
     return idx, depth, seg2d, err
 
 
-def prepare_images(plans, draws, flips, luts, device="cuda", decode_threads=4, timing=None):
+GPU_JPEG = True  # eligible JPEG files decode on the GPU (csrc/jpeg.hip); False: every image on the host (the benchmark's A/B lever)
+
+
+def source_offsets(plans):
+    """Byte offset of each plan's decoded [H][W][3] image in the source buffer: the images back to back in batch order."""
+    sizes = [p.image.size[0] * p.image.size[1] * 3 for p in plans]
+    return np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+
+
+def read_jpegs(plans):
+    """The files of the plans whose image is a JPEG file, read into one pinned buffer, and their headers.  Returns (pinned
+    uint8 tensor, byte offset per plan, :class:`jpeg.JpegHeader` or None per plan).  A file whose header :func:`jpeg.parse`
+    rejects (truncated or inconsistent) gets a header whose ``reason`` says why: it goes to the host decode, where PIL
+    decides as it did before, and never reaches a kernel."""
+    from . import jpeg
+
+    paths = [jpeg.jpeg_file(p.image) for p in plans]
+    sizes = [os.path.getsize(f) if f is not None else 0 for f in paths]
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    data = torch.empty(max(int(offs[-1]), 1), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    view = data.numpy()
+    headers = []
+    for i, f in enumerate(paths):
+        if f is None:
+            headers.append(None)
+            continue
+        buf = view[offs[i] : offs[i + 1]]
+        jpeg.read_into(f, buf)
+        try:
+            headers.append(jpeg.parse(buf, f))
+        except ValueError as e:
+            h = jpeg.JpegHeader()
+            h.reason = f"header: {e}"
+            headers.append(h)
+    return data, offs[:-1], headers
+
+
+def _decode_jpegs(plans, idx, headers, data, data_offs, src, src_offs, dev, timing):
+    """Queues csrc/jpeg.hip for the plans ``idx``; returns the device status words."""
+    from . import jpeg
+
+    L = _lib.lib()
+    hdrs = [headers[i] for i in idx]
+    desc, huff, qt, (n_iv, n_sub, n_blk, n_plane) = jpeg.build_tables(hdrs, [data_offs[i] for i in idx], [src_offs[i] for i in idx])
+    data_d = data.to(dev, non_blocking=True)
+    desc_d = torch.from_numpy(desc).to(dev)
+    huff_d = torch.from_numpy(huff).to(dev)
+    qt_d = torch.from_numpy(qt).to(dev)
+    status = torch.empty(len(idx), dtype=torch.int32, device=dev)
+    ws = _lib.workspace.get(int(L.mm_jpeg_ws_bytes(len(idx), data.numel(), n_iv, n_sub, n_blk, n_plane)), dev, "jpeg")
+    if timing is not None:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+    check(L.mm_jpeg_decode(ptr(data_d), data.numel(), ptr(desc_d), desc.ctypes.data, len(idx), ptr(huff_d), huff.shape[0], ptr(qt_d),
+                           qt.shape[0], ptr(src), src.numel(), ptr(status), ptr(ws), ws.numel(), stream()), "jpeg_decode")
+    if timing is not None:
+        ev[1].record()
+        timing["_decode_events"] = ev
+    return status
+
+
+def prepare_images(plans, draws, flips, luts, device="cuda", decode_threads=4, timing=None, checks=None):
     """The image half of a batch on the GPU (csrc/imageprep.hip): ``plans`` = :class:`imageprep.ImagePlan` per scene (window +
     target size), ``draws`` = ``ColorJitter.draw()`` per scene (or None), ``flips`` = fliplr per scene, ``luts`` = fp32
-    [3][256] per scene (:func:`imageprep.lut`).  Decodes every image with ``decode_threads`` threads into one pinned buffer,
-    copies it to the device in one H2D copy and runs the three kernels.  Returns img fp32 [B,3,H,W] on ``device``, already
-    flipped.  ``timing``: a dict that receives the GPU ms of the three kernels (``"kernels_ms"``, from events; synchronises)."""
+    [3][256] per scene (:func:`imageprep.lut`).  Baseline JPEG files (:mod:`jpeg`) are read into one pinned buffer, copied to
+    the device in one H2D copy and decoded there (csrc/jpeg.hip); every other image is decoded with ``decode_threads``
+    threads into a second pinned buffer and copied.  Both kinds land in one device source buffer, then the three kernels run.
+    Returns img fp32 [B,3,H,W] on ``device``, already flipped.  ``timing``: a dict that receives the GPU ms of the three
+    kernels (``"kernels_ms"``) and of the JPEG decode (``"decode_ms"``, events; synchronises) and the number of images decoded
+    each way (``"gpu_decoded"``, ``"host_decoded"``).  A JPEG whose entropy-coded data the GPU decoder cannot decode raises
+    ``RuntimeError`` naming the file: here, which waits for the stream, or - when ``checks`` is a list - in a callable
+    appended to it, for a caller that reads back from the stream anyway (``gpu_batch`` calls it after its own read-back)."""
     from . import imageprep
 
     L = _lib.lib()
@@ -124,10 +192,27 @@ def prepare_images(plans, draws, flips, luts, device="cuda", decode_threads=4, t
     B = len(plans)
     W, H = plans[0].size
     nbytes = sum(p.image.size[0] * p.image.size[1] * 3 for p in plans)
-    staging = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-    offs = imageprep.decode_into(plans, staging.numpy(), decode_threads)
-    desc, coef, factors, lut, tmp_bytes = imageprep.build_tables(plans, draws, flips, luts, offs)
-    src = staging.to(dev, non_blocking=True)
+    src_offs = source_offsets(plans)
+    gpu_idx, status = [], None
+    if GPU_JPEG:
+        data, data_offs, headers = read_jpegs(plans)
+        gpu_idx = [i for i, h in enumerate(headers) if h is not None and h.reason is None]
+    on_gpu = set(gpu_idx)
+    host_idx = [i for i in range(B) if i not in on_gpu]
+    src = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if gpu_idx:
+        status = _decode_jpegs(plans, gpu_idx, headers, data, data_offs, src, src_offs, dev, timing)
+    if host_idx:
+        hplans = [plans[i] for i in host_idx]
+        staging = torch.empty(sum(p.image.size[0] * p.image.size[1] * 3 for p in hplans), dtype=torch.uint8, pin_memory=True)
+        hoffs = imageprep.decode_into(hplans, staging.numpy(), decode_threads)
+        if not gpu_idx:
+            src[: staging.numel()].copy_(staging, non_blocking=True)  # same layout: one copy
+        else:
+            for j, i in enumerate(host_idx):
+                n = plans[i].image.size[0] * plans[i].image.size[1] * 3
+                src[src_offs[i] : src_offs[i] + n].copy_(staging[hoffs[j] : hoffs[j] + n], non_blocking=True)
+    desc, coef, factors, lut, tmp_bytes = imageprep.build_tables(plans, draws, flips, luts, src_offs)
     desc_d = torch.from_numpy(desc).to(dev)
     coef_d = torch.from_numpy(coef).to(dev)
     fac_d = torch.from_numpy(factors).to(dev)
@@ -145,7 +230,32 @@ def prepare_images(plans, draws, flips, luts, device="cuda", decode_threads=4, t
         ev[1].record()
         ev[1].synchronize()
         timing["kernels_ms"] = ev[0].elapsed_time(ev[1])
+        dec = timing.pop("_decode_events", None)
+        timing["decode_ms"] = dec[0].elapsed_time(dec[1]) if dec else 0.0
+        timing["gpu_decoded"], timing["host_decoded"] = len(gpu_idx), len(host_idx)
+    if status is not None:  # the one read-back of the decoder, queued after every image kernel
+        st_h = torch.empty(status.numel(), dtype=torch.int32, pin_memory=True)
+        st_h.copy_(status, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        paths = [jpeg_path(plans[i]) for i in gpu_idx]
+
+        def check_status():
+            done.synchronize()
+            bad = [(p, s) for p, s in zip(paths, st_h.tolist()) if s]
+            if bad:
+                raise RuntimeError("JPEG decode failed (entropy-coded data; include/mm2d3d.h MM_JPG_ST_* bits): " +
+                                   ", ".join(f"{p} (status {s})" for p, s in bad))
+
+        if checks is None:
+            check_status()
+        else:
+            checks.append(check_status)
     return img
+
+
+def jpeg_path(plan):
+    return getattr(plan.image, "filename", "<image>")
 
 
 def prepare_batch(scenes, scale=20, full_scale=4096, augmentation=None, fliplr=0.0, want_seg2d=False, device="cuda", use_rgb=True,

@@ -237,7 +237,7 @@ class _Scenes:
     sample = __getitem__
 
     # ------------------------------------------------------------------ second half on the GPU, whole batch
-    def gpu_batch(self, indices, device="cuda", want_seg2d=False, image="host", decode_threads=4):
+    def gpu_batch(self, indices, device="cuda", want_seg2d=False, image="host", decode_threads=4, timing=None):
         """``collate_scn_base([self[i] for i in indices])`` with the per-point work on the GPU (csrc/dataprep.hip).  Scene by
         scene the host runs the front end and draws the colour jitter, the flip and the 3D augmentation in the reference's
         order; pixel indices, depth / label maps, flip remap, rotation, voxelisation, range mask, point features and the
@@ -247,7 +247,9 @@ class _Scenes:
         host with PIL and numpy, scene by scene.  ``image="gpu"``: the front end only records the crop window and the target
         size (:class:`imageprep.ImagePlan`); after the scene loop the images are decoded on ``decode_threads`` threads, copied
         to the device at once and prepared by csrc/imageprep.hip - the same batch, bit for bit, and the same numpy / torch
-        RNG states afterwards.  RGB images only.
+        RNG states afterwards.  RGB images only.  Baseline JPEG files are decoded on the GPU (csrc/jpeg.hip, bit-exact with
+        Pillow); ``decode_threads`` decode the other images.  ``timing``: a dict for :func:`dataprep.prepare_images`'s GPU
+        times and decode counts (``image="gpu"``).
 
         Float64 points (VirtualKITTI with ``camera_coords``: the reference's camera-frame points are float64) are voxelised
         with numpy's float64 arithmetic by the fp64 kernels; the batch's ``points`` and ``min_values`` are then float64,
@@ -288,11 +290,14 @@ class _Scenes:
                 flips.append(flip)
         finally:
             self._plan_images = False
-        img = None
+        img, checks = None, []
         if on_gpu:
             lut = imageprep.lut(self._to_float, self._normalise)
-            img = dataprep.prepare_images([w.image for w in works], jitter, flips, [lut] * len(works), device, decode_threads)
+            img = dataprep.prepare_images([w.image for w in works], jitter, flips, [lut] * len(works), device, decode_threads, timing,
+                                          checks)
         batch = dataprep.prepare_batch(scenes, self.scale, self.full_scale, None, 0.0, want_seg2d, device, use_rgb=self.use_rgb, img=img)
+        for check in checks:  # the JPEG decoder's status words, after prepare_batch's own read-back has waited for the stream
+            check()
         batch["intrinsics"] = torch.from_numpy(np.stack(intrinsics))
         batch["points"] = torch.cat(batch["points"], 0) if batch["points"] else batch["points"]
         batch["coords"] = batch["x"][0][:, :3]

@@ -3,7 +3,9 @@
 Writes temporary full-size datasets from the miniature ones of tests/golden/mini_ds: nuScenes-shaped (the train_usa pkl with
 ``points_img`` scaled to 1600x900, JPEGs re-encoded at 1600x900 q90, resize (400, 225)) and A2D2-shaped (1920x1208 ->
 480x302), and prints one JSON line per dataset: ms per 16-scene ``gpu_batch`` (wall clock, synchronised) for
-``image="host"`` and for ``image="gpu"`` with 1 and 4 decode threads, and the GPU ms of the three image kernels (events).
+``image="host"`` and for ``image="gpu"`` with 1 and 4 host decode threads, and the GPU ms of the three image kernels (events).
+``gpu_decode_ms``: ``image="gpu"`` with the JPEGs decoded on the GPU (csrc/jpeg.hip), and ``decode_ms`` the GPU ms of the
+decoder (events).  The variants alternate within each repetition.
 
 ``vkitti``: the source domain of the vkitti -> skitti experiment (VirtualKITTISCN with camera_coords, so float64 points;
 downsample 10000, 1242x375 PNGs, bottom crop (480, 302), fliplr, colour jitter, the 3D augmentation, use_rgb=False) on
@@ -123,7 +125,7 @@ def _kernel_ms(ds, indices, device):
     lut = imageprep.lut(ds._to_float, ds._normalise)
     timing = {}
     dataprep.prepare_images([w.image for w in works], draws, flips, [lut] * len(works), device, 4, timing=timing)
-    return timing["kernels_ms"]
+    return timing
 
 
 def _voxelize_ms(ds, indices, device):
@@ -177,21 +179,35 @@ def main():
             res = {"kind": kind, "scenes": args.scenes, "full": KINDS[kind]["full"], "resize": KINDS[kind]["resize"]}
             if kind == "vkitti":
                 res["loader_ms"] = _loader_ms(ds, indices, args.reps)
-            for name, image, threads in (("host", "host", 1), ("gpu_1thread", "gpu", 1), ("gpu_4threads", "gpu", 4)):
-                times = []
-                for r in range(args.reps + 1):  # the first call warms up
-                    np.random.seed(r)
-                    torch.manual_seed(r)
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    ds.gpu_batch(indices, device=dev, want_seg2d=True, image=image, decode_threads=threads)
-                    torch.cuda.synchronize()
+            from mm2d3d_amd import dataprep
+
+            variants = [("host", "host", 1, False), ("gpu_1thread", "gpu", 1, False), ("gpu_4threads", "gpu", 4, False)]
+            if kind != "vkitti":
+                variants.append(("gpu_decode", "gpu", 4, True))
+            times = {name: [] for name, _, _, _ in variants}
+            for r in range(args.reps + 1):  # the first round warms up; the variants alternate
+                for name, image, threads, gpu_jpeg in variants:
+                    dataprep.GPU_JPEG = gpu_jpeg
+                    try:
+                        np.random.seed(r)
+                        torch.manual_seed(r)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        ds.gpu_batch(indices, device=dev, want_seg2d=True, image=image, decode_threads=threads)
+                        torch.cuda.synchronize()
+                    finally:
+                        dataprep.GPU_JPEG = True
                     if r:
-                        times.append((time.perf_counter() - t0) * 1e3)
-                res[f"{name}_ms"] = round(float(np.median(times)), 2)
-            gpu_ms = _voxelize_ms if kind == "vkitti" else _kernel_ms
-            key = "voxelize_ms" if kind == "vkitti" else "kernels_ms"
-            res[key] = round(float(np.median([gpu_ms(ds, indices, dev) for _ in range(args.reps + 1)][1:])), 3)
+                        times[name].append((time.perf_counter() - t0) * 1e3)
+            for name in times:
+                res[f"{name}_ms"] = round(float(np.median(times[name])), 2)
+            if kind == "vkitti":
+                res["voxelize_ms"] = round(float(np.median([_voxelize_ms(ds, indices, dev) for _ in range(args.reps + 1)][1:])), 3)
+            else:
+                tm = [_kernel_ms(ds, indices, dev) for _ in range(args.reps + 1)][1:]
+                res["kernels_ms"] = round(float(np.median([t["kernels_ms"] for t in tm])), 3)
+                res["decode_ms"] = round(float(np.median([t["decode_ms"] for t in tm])), 3)
+                res["gpu_decoded"] = tm[-1]["gpu_decoded"]
             print(json.dumps(res), flush=True)
 
 
