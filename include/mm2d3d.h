@@ -400,6 +400,23 @@ int mm_lift_scatter_key(const float* dout, int C, const int32_t* order, const in
 /* evaluation (EXP/train.py:297-339): confusion matrices [3][C][C] int64 of argmax(2D), argmax(3D), argmax(softmax mean) */
 int mm_eval_confusion(const float* logits2d, int ld2, const float* logits3d, int ld3, const int64_t* labels, int64_t N,
                       int C, int64_t ignore_index, int64_t* cm, mm_stream_t stream);
+/* ---------------------------------------------------------------- pseudo labels (csrc/pselab.hip)
+ * mm_pselab_predict: what a self-training round stores per point (the files lib/dataset/*_dataloader.py read back): for the 2D
+ * logits, the 3D logits and the softmax average 0.5 * (softmax2d + softmax3d) (EXP/train.py:315-318) the largest probability
+ * (fp32 [N]) and its class (uint8 [N], the first maximum wins).  Same arithmetic as mm_eval_confusion (one shared device function):
+ * the exported labels are the labels evaluation counts.  logits [N, C] fp32 with row pitches ld2 / ld3 >= C, C <= 32.
+ * logits3d may be NULL (2D-only export): then only probs_2d / label_2d are written and the other four may be NULL. */
+int mm_pselab_predict(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, float* probs_2d,
+                      uint8_t* label_2d, float* probs_3d, uint8_t* label_3d, float* probs_ensemble, uint8_t* label_ensemble,
+                      mm_stream_t stream);
+/* lib/utils/refine_pseudo_labels.py, exact: for every class c of [0, C) that occurs n_c > 0 times, med_c = the element of rank
+ * (n_c - 1) / 2 (ascending, 0-based: torch.median's lower median) among the probs of that class, thr_c = min(med_c, 0.9f);
+ * labels_out[i] = ignore_label where labels[i] == c and probs[i] < thr_c, else labels[i].  Labels outside [0, C) pass through.
+ * An exact radix select (four 8-bit passes, integer counts): deterministic, no host read-back.  probs must be FINITE (a NaN has
+ * no place in the order); N < 2^40, C <= 32.  ws: mm_pselab_refine_ws_bytes(C) bytes of device scratch (0 for a bad C). */
+size_t mm_pselab_refine_ws_bytes(int C);
+int mm_pselab_refine(const float* probs, const int64_t* labels, int64_t N, int C, int64_t ignore_label, int64_t* labels_out,
+                     void* ws, size_t ws_bytes, mm_stream_t stream);
 /* torch.optim.AdamW update over flat fp32 arenas (EXP/train.py:627-636); step counts from 1; g is multiplied by grad_scale.
  * skip_dev / nskip (0 .. 16, may be NULL / 0): device words - the update is a no-op when any of them is nonzero (the
  * data-parallel reducer's collective "this step's gradients are invalid" flags: decided on the device, no read-back) */

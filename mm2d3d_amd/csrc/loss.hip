@@ -5,11 +5,12 @@
 // and the fused flat AdamW update (K16; train.py:627-636 -> torch.optim.AdamW).
 // Block partial sums are fp64 and combined in a fixed order: bit-stable run to run.
 #include "common.h"
+#include "pointpred.h"
 
 namespace {
 constexpr int T = 256;
 constexpr int MAX_PART = 1024;
-constexpr int MAXC = 32;
+constexpr int MAXC = MM_PRED_MAXC;
 
 __device__ inline double block_sum(double v, double* red) {
   __syncthreads();
@@ -208,28 +209,10 @@ __global__ __launch_bounds__(T) void k_eval_confusion(const float* __restrict__ 
   for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
     int64_t y = labels[i];
     if (y == ignore || y < 0 || y >= C) continue;
-    const float* a = l2 + i * ld2;
-    const float* b = l3 + i * ld3;
-    float ma = a[0], mb = b[0];
-    int ia = 0, ib = 0;
-    for (int c = 1; c < C; c++) {
-      if (a[c] > ma) { ma = a[c]; ia = c; }
-      if (b[c] > mb) { mb = b[c]; ib = c; }
-    }
-    float sa = 0.f, sb = 0.f;
-    for (int c = 0; c < C; c++) {
-      sa += expf(a[c] - ma);
-      sb += expf(b[c] - mb);
-    }
-    float best = -1.f;
-    int ie = 0;
-    for (int c = 0; c < C; c++) {
-      float e = 0.5f * (expf(a[c] - ma) / sa + expf(b[c] - mb) / sb);
-      if (e > best) { best = e; ie = c; }
-    }
-    atomicAdd(&hist[(0 * C + (int)y) * C + ia], 1u);
-    atomicAdd(&hist[(1 * C + (int)y) * C + ib], 1u);
-    atomicAdd(&hist[(2 * C + (int)y) * C + ie], 1u);
+    const MMPointPred r = mm_point_predict<true>(l2 + i * ld2, l3 + i * ld3, C);  // pointpred.h: shared with the pseudo-label export
+    atomicAdd(&hist[(0 * C + (int)y) * C + r.ia], 1u);
+    atomicAdd(&hist[(1 * C + (int)y) * C + r.ib], 1u);
+    atomicAdd(&hist[(2 * C + (int)y) * C + r.ie], 1u);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 3 * C * C; i += T)

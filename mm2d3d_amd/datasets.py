@@ -136,9 +136,12 @@ class _Scenes:
             order = sorted(range(len(self.data)), key=lambda i: self.data[i]["camera_path"])
             self.data = [self.data[i] for j, i in enumerate(order) if j % reduce_factor == 0]
 
-    def _load_pseudo_labels(self, path, length_key):
-        """nuscenes_dataloader.py:96-162 / semantic_kitti.py:143-205: refine over the WHOLE dataset, then cut back per scene."""
+    def _load_pseudo_labels(self, path, length_key, refine_device=None):
+        """nuscenes_dataloader.py:96-162 / semantic_kitti.py:143-205: refine over the WHOLE dataset, then cut back per scene.
+        ``refine_device``: None = the host refinement; "cuda" (or a device) = the same refinement by csrc/pselab.hip
+        (mm2d3d_amd.pselab.refine_pseudo_labels), the same labels exactly."""
         self.pselab_data = None
+        self.pselab_length_key = length_key  # the per-scene array the file's rows line up with (pselab.export_pseudo_labels)
         if not path:
             return
         data = [dict(d) for d in np.load(path, allow_pickle=True)]
@@ -151,6 +154,10 @@ class _Scenes:
         def refined(prob_key, lab_key):
             probs = np.concatenate([d[prob_key] for d in data])
             labs = np.concatenate([d[lab_key] for d in data]).astype(int)
+            if refine_device is not None:
+                from . import pselab
+
+                return pselab.refine_pseudo_labels(probs, labs, num_classes=int(labs.max()) + 1, device=refine_device)
             return refine_pseudo_labels(probs, labs)
 
         lab2d = refined("probs_2d", "pseudo_label_2d")
@@ -333,9 +340,9 @@ class NuScenesLidarSegSCN(_Scenes):
     def __init__(self, split, preprocess_dir, nuscenes_dir="", pselab_paths=None, merge_classes=False, scale=20, full_scale=4096,
                  resize=(400, 225), image_normalizer=None, noisy_rot=0.0, flip_x=0.0, rot=0.0, transl=False, fliplr=0.0,
                  color_jitter=None, output_orig=False, short_run=False, reduce_factor=1, camera_coords=False, use_rgb=False,
-                 label_mapping=None):
+                 label_mapping=None, pselab_refine_device=None):
         self._load_splits(split, preprocess_dir, short_run, reduce_factor)
-        self._load_pseudo_labels(pselab_paths, "seg_labels")
+        self._load_pseudo_labels(pselab_paths, "seg_labels", pselab_refine_device)
         self.class_names = list(label_maps.NUSCENES_RAW)
         self.label_mapping = None
         if merge_classes:
@@ -377,9 +384,9 @@ class SemanticKITTISCN(_Scenes):
     def __init__(self, split, preprocess_dir, semantic_kitti_dir="", pselab_paths=None, merge_classes_style=None, merge_classes=None,
                  scale=20, full_scale=4096, image_normalizer=None, noisy_rot=0.0, flip_x=0.0, rot=0.0, transl=False, crop_size=tuple(),
                  bottom_crop=False, rand_crop=tuple(), fliplr=0.0, color_jitter=None, output_orig=False, resize=tuple(),
-                 downsample=(-1,), short_run=False, reduce_factor=1, camera_coords=False, use_rgb=False):
+                 downsample=(-1,), short_run=False, reduce_factor=1, camera_coords=False, use_rgb=False, pselab_refine_device=None):
         self._load_splits(split, preprocess_dir, short_run, reduce_factor)
-        self._load_pseudo_labels(pselab_paths, "points")
+        self._load_pseudo_labels(pselab_paths, "points", pselab_refine_device)
         if not merge_classes_style:
             raise NotImplementedError("The merge classes style needs to be provided, e.g. A2D2.")
         self.label_mapping, self.class_names = label_maps.merged(label_maps.SEMANTIC_KITTI_MERGE[merge_classes_style],
@@ -585,10 +592,12 @@ def worker_init_fn(worker_id):
     np.random.seed(worker_id)  # lib/dataset/__init__.py:142-153
 
 
-def load_datasets(name, cfg_source, cfg_target, ds_args=None, augmentations=None, short_run=False, reduce_factor=1, pselab_paths=None):
+def load_datasets(name, cfg_source, cfg_target, ds_args=None, augmentations=None, short_run=False, reduce_factor=1, pselab_paths=None,
+                  pselab_refine_device=None):
     """The dataset choice of ``load_datamodule`` (lib/dataset/__init__.py:156-296) without the Lightning wrapper: returns
     ``dict(train_source=, train_target=, val_target=, test=)``.  ``cfg_*`` are mappings with the keys of the DATASET_SOURCE /
-    DATASET_TARGET blocks of datasets/*.yaml."""
+    DATASET_TARGET blocks of datasets/*.yaml.  ``pselab_refine_device``: where the target training set refines its pseudo labels
+    (None = host, "cuda" = csrc/pselab.hip; the same labels)."""
     ds_args, aug = dict(ds_args or {}), dict(augmentations or {})
     short = dict(short_run=short_run, reduce_factor=reduce_factor)
     if name == "nuscenes":
@@ -598,7 +607,7 @@ def load_datasets(name, cfg_source, cfg_target, ds_args=None, augmentations=None
             train_source=mk(cfg_source["TRAIN"], output_orig=False, **short, **aug),
             train_target=NuScenesLidarSegSCN(split=cfg_target["TRAIN"], preprocess_dir=cfg_target["preprocess_dir"],
                                              nuscenes_dir=cfg_target["nuscenes_dir"], output_orig=False, pselab_paths=pselab_paths,
-                                             **short, **ds_args, **aug),
+                                             pselab_refine_device=pselab_refine_device, **short, **ds_args, **aug),
             val_target=mk(cfg_target["VAL"], output_orig=True), test=mk(cfg_target["TEST"], output_orig=True))
     if name in ("ad2d_semantic_kitti", "vkitti_semantic_kitti"):
         if name == "ad2d_semantic_kitti":
@@ -608,6 +617,7 @@ def load_datasets(name, cfg_source, cfg_target, ds_args=None, augmentations=None
                                   virtual_kitti_dir=cfg_source["virtual_kitti_dir"], **short, **ds_args, **aug)
         mk = lambda split, **kw: SemanticKITTISCN(split=split, preprocess_dir=cfg_target["preprocess_dir"],
                                                   semantic_kitti_dir=cfg_target["semantic_kitti_dir"], **ds_args, **kw)
-        return dict(train_source=src, train_target=mk(cfg_target["TRAIN"], output_orig=False, pselab_paths=pselab_paths, **short, **aug),
+        return dict(train_source=src, train_target=mk(cfg_target["TRAIN"], output_orig=False, pselab_paths=pselab_paths,
+                                                       pselab_refine_device=pselab_refine_device, **short, **aug),
                     val_target=mk(cfg_target["VAL"], output_orig=True), test=mk(cfg_target["TEST"], output_orig=True))
     raise ValueError(f"not found datamodule {name}")

@@ -1,0 +1,294 @@
+"""Pseudo labels: the producer side of the self-training round (csrc/pselab.hip).
+
+The reference's second training round reads ``pselab_paths=`` files (lib/dataset/nuscenes_dataloader.py:96-162,
+semantic_kitti.py:143-205): a pickled object array with one dict per scene, ``probs_2d / pseudo_label_2d / probs_3d /
+pseudo_label_3d / probs_ensemble / pseudo_label_ensemble``, each ``[n_points]`` - the largest softmax probability (fp32) and
+its class (uint8) of the 2D network, of the 3D network and of their average (train.py:297-339).  This module writes them:
+
+    predict(logits_2d, logits_3d)            the six per-point tensors of one batch, one kernel (mm_pselab_predict)
+    PseudoLabelWriter(path)                  collects scenes, ``close()`` writes the file
+    export_pseudo_labels(trainer, dataset, path)   walks a dataset through ``TrainModel.predict_step`` into a writer
+    refine_pseudo_labels(probs, labels)      lib/utils/refine_pseudo_labels.py on the GPU (mm_pselab_refine), exact: what the
+                                             loaders run three times over every point of a split at construction
+
+``radix_select_medians`` restates the kernel's selection in numpy; only tests use it.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream
+
+KEYS = ("probs_2d", "pseudo_label_2d", "probs_3d", "pseudo_label_3d", "probs_ensemble", "pseudo_label_ensemble")
+MAX_CLASSES = 32  # csrc/pointpred.h MM_PRED_MAXC
+
+
+# ---------------------------------------------------------------------------------------------------- prediction
+def _logits(t, name):
+    _lib.require_cuda(t, name)
+    t = t.detach()
+    if t.dim() != 2:
+        raise ValueError(f"pselab.predict: {name} must be [N, C]")
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()  # a row-pitched view (stride(1) == 1) is read in place; one row has no pitch to check
+    return t
+
+
+@torch.no_grad()
+def predict(logits_2d, logits_3d=None):
+    """Per point the confidence and the class of the 2D logits, the 3D logits and the softmax average, as device tensors under
+    the keys of the pseudo-label file (fp32 probabilities, uint8 labels).  ``logits_3d=None``: a 2D-only prediction, the
+    3D and ensemble entries are ``None``."""
+    a = _logits(logits_2d, "logits_2d")
+    b = None if logits_3d is None else _logits(logits_3d, "logits_3d")
+    if b is not None and (b.shape != a.shape or b.device != a.device):
+        raise ValueError("pselab.predict: logits_2d and logits_3d must have the same shape and device")
+    N, C = a.shape
+    n_out = 1 if b is None else 3
+    probs = torch.empty((n_out, N), dtype=torch.float32, device=a.device)
+    labels = torch.empty((n_out, N), dtype=torch.uint8, device=a.device)
+    pitch = lambda t: t.stride(0) if N > 1 else C
+    with torch.cuda.device(a.device):
+        check(_lib.lib().mm_pselab_predict(ptr(a), pitch(a), ptr(b), pitch(b) if b is not None else 0, N, C, ptr(probs[0]), ptr(labels[0]),
+                                           ptr(probs[1]) if b is not None else None, ptr(labels[1]) if b is not None else None,
+                                           ptr(probs[2]) if b is not None else None, ptr(labels[2]) if b is not None else None,
+                                           stream()), "pselab_predict")
+    out = dict.fromkeys(KEYS)
+    out["probs_2d"], out["pseudo_label_2d"] = probs[0], labels[0]
+    if b is not None:
+        out["probs_3d"], out["pseudo_label_3d"] = probs[1], labels[1]
+        out["probs_ensemble"], out["pseudo_label_ensemble"] = probs[2], labels[2]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- refinement
+def refine_pseudo_labels(probs, labels, ignore_label=-100, num_classes=None, device="cuda"):
+    """``datasets.refine_pseudo_labels`` on the GPU: the same labels, exactly.  ``probs`` / ``labels``: numpy arrays or tensors
+    ``[N]``; they are uploaded (if they are not on ``device`` already), refined by mm_pselab_refine and returned in the input's
+    kind, dtype and shape.  ``num_classes``: classes are ``[0, num_classes)`` (default: largest label + 1); labels outside
+    (``-100`` from an earlier refinement, say) pass through.  float32 probabilities only - the selection works on their bit
+    patterns; every other dtype raises ``TypeError``: use ``mm2d3d_amd.datasets.refine_pseudo_labels`` for those."""
+    as_numpy = not torch.is_tensor(labels)
+    p = probs if torch.is_tensor(probs) else torch.from_numpy(np.ascontiguousarray(probs))
+    y = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    if p.dtype != torch.float32:
+        raise TypeError(f"pselab.refine_pseudo_labels takes float32 probabilities, not {p.dtype}: the host function "
+                        "mm2d3d_amd.datasets.refine_pseudo_labels handles other dtypes")
+    if y.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8):
+        raise TypeError(f"pselab.refine_pseudo_labels takes signed integer labels (ignore_label must fit), not {y.dtype}")
+    if p.shape != y.shape:
+        raise ValueError("pselab.refine_pseudo_labels: probs and labels must have the same shape")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pselab.refine_pseudo_labels runs on a GPU; the host function is mm2d3d_amd.datasets.refine_pseudo_labels")
+    if num_classes is None:
+        num_classes = int(y.max()) + 1 if y.numel() else 0
+    out_dev = y.device
+    if y.numel() == 0 or num_classes <= 0:
+        res = y.clone()
+    else:
+        pd = p.reshape(-1).to(dev).contiguous()
+        yd = y.reshape(-1).to(dev, torch.int64).contiguous()
+        od = torch.empty_like(yd)
+        L = _lib.lib()
+        with torch.cuda.device(pd.device):
+            ws = _lib.workspace.get(int(L.mm_pselab_refine_ws_bytes(int(num_classes))), pd.device, "pselab")
+            check(L.mm_pselab_refine(ptr(pd), ptr(yd), yd.numel(), int(num_classes), int(ignore_label), ptr(od), ptr(ws), ws.numel(),
+                                     stream()), "pselab_refine")
+        res = od.to(out_dev).to(y.dtype).reshape(y.shape)
+    return res.numpy() if as_numpy else res
+
+
+def float_keys(p):
+    """The order-preserving uint32 image of float32 values (csrc/pselab.hip f2key)."""
+    u = np.ascontiguousarray(p, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def radix_select_medians(probs, labels, num_classes):
+    """Numpy restatement of the kernel chain's selection (tests only): per class of ``[0, num_classes)`` the element of rank
+    ``(n - 1) // 2`` among its probabilities, by four most-significant-digit passes of 256-bucket counts.  Returns
+    ``(medians float32 [num_classes], present bool [num_classes])``."""
+    probs = np.ascontiguousarray(probs, dtype=np.float32)
+    labels = np.asarray(labels)
+    keys = float_keys(probs)
+    med, present = np.zeros(num_classes, np.float32), np.zeros(num_classes, bool)
+    for c in range(num_classes):
+        k = keys[labels == c]
+        if not len(k):
+            continue
+        present[c] = True
+        rank, prefix = (len(k) - 1) // 2, 0
+        for p in range(4):
+            shift = 24 - 8 * p
+            if p:
+                k = k[(k >> np.uint32(shift + 8)) == prefix]
+            counts = np.bincount((k >> np.uint32(shift)) & np.uint32(255), minlength=256)
+            incl = np.cumsum(counts)
+            b = int(np.searchsorted(incl, rank, side="right"))  # first bucket with incl > rank
+            rank -= int(incl[b] - counts[b])
+            prefix = (prefix << 8) | b
+        key = np.uint32(prefix)
+        bits = key & np.uint32(0x7FFFFFFF) if key & np.uint32(0x80000000) else ~key
+        med[c] = np.array([bits], dtype=np.uint32).view(np.float32)[0]
+    return med, present
+
+
+def refine_with_medians(probs, labels, medians, present, ignore_label=-100):
+    """The threshold rule of the refinement on given medians: ``thr = min(median, float32(0.9))``, compared in float32."""
+    probs = np.ascontiguousarray(probs, dtype=np.float32)
+    out = np.array(labels, copy=True)
+    for c in np.nonzero(present)[0]:
+        thr = np.minimum(np.float32(medians[c]), np.float32(0.9))
+        out[(out == c) & (probs < thr)] = ignore_label
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- the file
+class PseudoLabelWriter:
+    """Collects per-scene pseudo labels and writes the file the loaders' ``pselab_paths=`` reads: ``close()`` saves
+    ``np.array(list_of_dicts, dtype=object)`` with the six ``KEYS`` per scene, float32 probabilities and uint8 labels.
+    ``with_3d=False``: the two 3D entries are ``None`` (a 2D-only round; the loaders accept it)."""
+
+    def __init__(self, path, with_3d=True):
+        self.path, self.with_3d, self.scenes, self.closed = path, with_3d, [], False
+
+    @staticmethod
+    def _host(x, dtype, n=None, what=""):
+        if torch.is_tensor(x):
+            x = x.detach().cpu().numpy()
+        x = np.array(x, dtype=dtype, copy=True).reshape(-1)  # a copy: callers reuse their staging buffers
+        if n is not None and len(x) != n:
+            raise ValueError(f"PseudoLabelWriter: {what} has {len(x)} entries, probs_2d has {n}")
+        return x
+
+    def add_scene(self, probs_2d, label_2d, probs_3d, label_3d, probs_ensemble, label_ensemble):
+        if self.closed:
+            raise RuntimeError("PseudoLabelWriter: already closed")
+        if probs_ensemble is None or label_ensemble is None:
+            raise ValueError("PseudoLabelWriter: the ensemble entries are required (the loaders refine them unconditionally)")
+        if self.with_3d and (probs_3d is None or label_3d is None):
+            raise ValueError("PseudoLabelWriter: with_3d=True needs probs_3d and label_3d")
+        d = {"probs_2d": self._host(probs_2d, np.float32)}
+        n = len(d["probs_2d"])
+        d["pseudo_label_2d"] = self._host(label_2d, np.uint8, n, "label_2d")
+        d["probs_3d"] = self._host(probs_3d, np.float32, n, "probs_3d") if self.with_3d else None
+        d["pseudo_label_3d"] = self._host(label_3d, np.uint8, n, "label_3d") if self.with_3d else None
+        d["probs_ensemble"] = self._host(probs_ensemble, np.float32, n, "probs_ensemble")
+        d["pseudo_label_ensemble"] = self._host(label_ensemble, np.uint8, n, "label_ensemble")
+        self.scenes.append(d)
+
+    def close(self):
+        if self.closed:
+            return self.path
+        arr = np.empty(len(self.scenes), dtype=object)  # = np.array(self.scenes, dtype=object), 1-D also for an empty list
+        for i, d in enumerate(self.scenes):
+            arr[i] = d
+        with open(self.path, "wb") as f:  # np.save appends ".npy" to a name; a file object keeps the caller's path
+            np.save(f, arr, allow_pickle=True)
+        self.closed = True
+        return self.path
+
+
+class _HostCopy:
+    """One batch's outputs on their way to the host: asynchronous copies into pinned buffers on the current stream, then an
+    event (the pattern of scn/metadata._Readback); ``wait()`` blocks only if the GPU has not got there yet.  The pinned
+    buffers belong to a slot of the exporter and are reused by the batch after next."""
+
+    def __init__(self, slot, tensors):
+        self.views, self._keep = {}, tensors
+        dev = next(t.device for t in tensors.values() if t is not None)
+        for k, t in tensors.items():
+            if t is None:
+                self.views[k] = None
+                continue
+            buf = slot.get(k)
+            if buf is None or buf.numel() < t.numel() or buf.dtype != t.dtype:
+                buf = slot[k] = torch.empty(max(int(t.numel() * 1.25), 1024), dtype=t.dtype).pin_memory()
+            buf[: t.numel()].copy_(t.reshape(-1), non_blocking=True)
+            self.views[k] = buf[: t.numel()].numpy()
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(dev))
+
+    def wait(self):
+        self.event.synchronize()
+        self._keep = None
+        return self.views
+
+
+def export_pseudo_labels(trainer, dataset, path, batch_size=8, device="cuda", **gpu_batch_kwargs):
+    """Pseudo labels of every scene of ``dataset`` under ``trainer``'s current weights, written to ``path`` in the format
+    ``pselab_paths=`` reads.  Scenes are walked in index order, ``batch_size`` at a time (the last batch may be short):
+    ``dataset.gpu_batch`` -> ``trainer.predict_step`` -> per-scene slices -> pinned host buffers (one batch's copies in flight while
+    the next batch is computed) -> :class:`PseudoLabelWriter`.
+
+    The file's rows must line up with the scenes' points as the loader will see them, so the dataset must be built with
+    ``output_orig=True`` and without augmentation that drops points; a scene of which a point fell outside the voxel range,
+    or whose exported length differs from the length the loader checks (a cropping or down-sampling configuration), raises
+    ``ValueError`` naming the scene, and no file is written.  ``predict_step`` leaves the trainer's model in eval mode and nothing
+    here undoes that: call ``trainer.model.train()`` before training goes on.  Returns ``dict(path, scenes, points, num_classes, hist_2d,
+    hist_3d, hist_ensemble)`` with the per-class label counts."""
+    name = type(dataset).__name__
+    if not getattr(dataset, "has_pselab", False):
+        raise ValueError(f"export_pseudo_labels: {name} is a source-only dataset (has_pselab = False): its loader reads no pseudo labels "
+                         "(refused before scene 0)")
+    if not getattr(dataset, "output_orig", False):
+        raise ValueError(f"export_pseudo_labels: this {name} was not built with output_orig=True, so the per-scene range masks cannot be "
+                         "checked (refused before scene 0)")
+    length_key = getattr(dataset, "pselab_length_key", None)
+    if length_key is None:
+        raise ValueError(f"export_pseudo_labels: {name} does not say which per-scene array its pseudo labels line up with "
+                         "(refused before scene 0)")
+    writer = PseudoLabelWriter(path, with_3d=True)
+    hist = np.zeros((3, 256), dtype=np.int64)
+    slots, pending, points = [{}, {}], None, 0
+
+    def drain(job):
+        nonlocal points
+        copy, counts = job
+        host = copy.wait()
+        left = 0
+        for n in counts:
+            cut = [host[k][left : left + n] for k in KEYS]
+            writer.add_scene(*cut)
+            for j, k in enumerate(("pseudo_label_2d", "pseudo_label_3d", "pseudo_label_ensemble")):
+                hist[j] += np.bincount(host[k][left : left + n], minlength=256)
+            left += n
+            points += n
+
+    n_scenes = len(dataset)
+    for k, start in enumerate(range(0, n_scenes, batch_size)):
+        indices = list(range(start, min(start + batch_size, n_scenes)))
+        batch = dataset.gpu_batch(indices, device=device, **gpu_batch_kwargs)
+        counts = [int(t.shape[0]) for t in batch["img_indices"]]
+        for b, i in enumerate(indices):
+            mask = np.asarray(batch["orig_points_idx"][b])
+            if not mask.all():
+                raise ValueError(f"export_pseudo_labels: scene {i}: {int((~mask).sum())} of {len(mask)} points fall outside the voxel range "
+                                 f"(full_scale={dataset.full_scale}): the file's rows would not line up with the scene's points")
+            want = len(dataset.data[i][length_key])
+            if counts[b] != want:
+                raise ValueError(f"export_pseudo_labels: scene {i}: {counts[b]} points reach the networks but the loader checks "
+                                 f"len(data[{i}][{length_key!r}]) = {want}: export without cropping or down-sampling")
+        out = trainer.predict_step(batch)
+        if out["probs_3d"] is None:
+            raise ValueError("export_pseudo_labels: predict_step returned no 3D prediction")
+        if sum(counts) != out["probs_2d"].shape[0]:
+            raise ValueError(f"export_pseudo_labels: scene {indices[0]}: the batch has {sum(counts)} points, the prediction {out['probs_2d'].shape[0]}")
+        job = (_HostCopy(slots[k % 2], {key: out[key] for key in KEYS}), counts)
+        if pending is not None:
+            drain(pending)  # the previous batch, while this one's kernels and copies run
+        pending = job
+    if pending is not None:
+        drain(pending)
+    writer.close()
+    used = np.nonzero(hist.sum(0))[0]
+    C = max(int(getattr(trainer, "num_classes", None) or 0), int(used[-1]) + 1 if len(used) else 0)
+    return dict(path=os.fspath(path), scenes=n_scenes, points=points, num_classes=C, hist_2d=hist[0, :C].copy(), hist_3d=hist[1, :C].copy(),
+                hist_ensemble=hist[2, :C].copy())

@@ -384,6 +384,20 @@ class TrainModel(nn.Module):
     def test_step(self, batch, batch_idx=0):
         return self._generic_step_val(batch, "test/target")
 
+    @torch.no_grad()
+    def predict_step(self, batch):
+        """The pseudo labels of a batch (mm2d3d_amd/pselab.py): the two forwards of the evaluation step, then per point the
+        confidence and the class of the 2D, the 3D and the softmax-average prediction - the labels ``test_step`` counts.
+        Computes no loss, so the batch needs no labels beyond what the loaders put there.  Like ``validation_step`` it leaves
+        the model in eval mode; no epoch-end hook follows it, so call ``trainer.model.train()`` before training goes on."""
+        from . import pselab
+
+        with self._use():
+            self.model.eval()
+            p2d, _, _, _ = self(batch, model_name=self.modules_name[0])
+            p3d, _, _ = self(batch, model_name=self.modules_name[1])
+            return pselab.predict(p2d["seg_logit"], p3d["seg_logit"])
+
     def evaluation_end(self, stage):
         """Epoch end: sync the confusion matrices over ranks, mean IoU of 2D / 3D / ensemble, best-metric tracking."""
         m = self._ious[stage]
