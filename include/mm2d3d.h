@@ -438,6 +438,42 @@ int mm_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, c
 int mm_amp_update(float* scale_dev, int* tracker_dev, const int* found_dev, int nfound, double growth, double backoff, int interval,
                   mm_stream_t stream);
 
+/* ---------------------------------------------------------------- SGD / Adam / RMSprop over flat arenas (csrc/optim.hip)
+ * The other three names of the reference's optimiser registry (lib/optimizers.py: adamw, adam, sgd, rmsprop), one fused launch
+ * per touched range like mm_adamw_step: fp32 arithmetic in the op order of torch.optim.{SGD, Adam, RMSprop}'s single-tensor
+ * paths, g is multiplied by grad_scale, skip_dev / nskip as for mm_adamw_step.  A state array that the hyper-parameters do not
+ * need is NULL and is neither read nor written; a non-NULL pointer selects the variant:
+ *   mm_sgd_step      buf = momentum buffer (NULL: no momentum); nesterov needs it.  ``step`` counts the optimiser's taken steps
+ *                    from 1: on step 1 buf = g (torch's rule, no dampening), afterwards buf = momentum*buf + (1-dampening)*g.
+ *   mm_adam_step     m, v; vmax = amsgrad's running maximum of v (NULL: amsgrad off).  decoupled = 0: weight decay is L2
+ *                    (torch.optim.Adam); 1: p *= 1 - lr*wd (torch.optim.AdamW).  ``step`` drives the bias corrections.
+ *   mm_rmsprop_step  sq; gavg = gradient average (NULL: not centered); buf = momentum buffer (NULL: no momentum).
+ * Loss-scaled form, as mm_amp_prepare / mm_adamw_step_dev: mm_*_prepare (one thread) writes one parameter group's coefficients
+ * (mm_optim_coef_bytes bytes: 1 / scale, "skip" = any of found_dev[0 .. nfound) set, Adam's bias corrections, SGD's first-step
+ * rule) from the device-resident scale, flag words and step counter, which advances only when the step is taken and ``advance``
+ * is set; mm_*_step_dev applies them and is a no-op when they say "skip".  No read-back anywhere. */
+int mm_optim_coef_bytes(void);
+int mm_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double dampening, double weight_decay,
+                int nesterov, int64_t step, double grad_scale, const int* skip_dev, int nskip, mm_stream_t stream);
+int mm_adam_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, double lr, double beta1, double beta2,
+                 double eps, double weight_decay, int decoupled, int64_t step, double grad_scale, const int* skip_dev, int nskip,
+                 mm_stream_t stream);
+int mm_rmsprop_step(float* p, const float* g, float* sq, float* gavg, float* buf, int64_t n, double lr, double alpha, double eps,
+                    double weight_decay, double momentum, double grad_scale, const int* skip_dev, int nskip, mm_stream_t stream);
+int mm_sgd_prepare(const float* scale_dev, const int* found_dev, int nfound, int64_t* step_dev, int advance, double lr,
+                   double momentum, double dampening, double weight_decay, double grad_scale, void* coef_dev, mm_stream_t stream);
+int mm_adam_prepare(const float* scale_dev, const int* found_dev, int nfound, int64_t* step_dev, int advance, double lr,
+                    double beta1, double beta2, double eps, double weight_decay, int decoupled, double grad_scale, void* coef_dev,
+                    mm_stream_t stream);
+int mm_rmsprop_prepare(const float* scale_dev, const int* found_dev, int nfound, int64_t* step_dev, int advance, double lr,
+                       double alpha, double eps, double weight_decay, double momentum, double grad_scale, void* coef_dev,
+                       mm_stream_t stream);
+int mm_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, int nesterov, const void* coef_dev, mm_stream_t stream);
+int mm_adam_step_dev(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, int decoupled, const void* coef_dev,
+                     mm_stream_t stream);
+int mm_rmsprop_step_dev(float* p, const float* g, float* sq, float* gavg, float* buf, int64_t n, const void* coef_dev,
+                        mm_stream_t stream);
+
 /* ---------------------------------------------------------------- dense 2D convolutions (csrc/conv2d.hip)
  * torch.nn.Conv2d / ConvTranspose2d of EXP/2d_net/backbones.py:43-65 and EXP/2d_net/model.py:64-82,104-123.
  * NHWC bf16 activations, fp32 accumulate.  mm_conv2d_gemm: out[m][n] = sum_{tap,k} A[src(m,tap)][k] * Wp[n][tap][k]

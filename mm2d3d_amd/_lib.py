@@ -117,6 +117,16 @@ _PROTOS = {
     "mm_amp_prepare": (i32, [vp, vp, i32, vp, i32, f64, f64, f64, f64, f64, f64, vp, vp]),
     "mm_adamw_step_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
     "mm_amp_update": (i32, [vp, vp, vp, i32, f64, f64, i32, vp]),
+    "mm_optim_coef_bytes": (i32, []),
+    "mm_sgd_step": (i32, [vp, vp, vp, i64, f64, f64, f64, f64, i32, i64, f64, vp, i32, vp]),
+    "mm_adam_step": (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, i64, f64, vp, i32, vp]),
+    "mm_rmsprop_step": (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, f64, vp, i32, vp]),
+    "mm_sgd_prepare": (i32, [vp, vp, i32, vp, i32, f64, f64, f64, f64, f64, vp, vp]),
+    "mm_adam_prepare": (i32, [vp, vp, i32, vp, i32, f64, f64, f64, f64, f64, i32, f64, vp, vp]),
+    "mm_rmsprop_prepare": (i32, [vp, vp, i32, vp, i32, f64, f64, f64, f64, f64, f64, vp, vp]),
+    "mm_sgd_step_dev": (i32, [vp, vp, vp, i64, i32, vp, vp]),
+    "mm_adam_step_dev": (i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+    "mm_rmsprop_step_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "mm_conv2d_gemm": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
                              vp, i32, i64, i32, vp, vp, i64, vp, i32, vp]),
     "mm_conv2d_3x3s1": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, i32, vp]),

@@ -4,9 +4,10 @@ The reference trains with ``precision: 16`` (/root/reference/.../config/train.ya
 autocast + ``torch.cuda.amp.GradScaler`` (init_scale 65536, growth_factor 2, backoff_factor 0.5, growth_interval 2000; an
 optimiser whose gradients hold an inf / nan skips its step, ``update()`` then halves the scale, 2000 clean steps double it).
 IEEE fp16 gradient rows need that scale (bf16 rows do not: the default 16-bit kind here), so ``GradScaler`` below restates
-those semantics for :class:`mm2d3d_amd.optimizers.FlatAdamW` - with the scale, the non-finite flags, the clean-step tracker and
-the optimisers' step counters RESIDENT ON THE DEVICE (csrc/loss.hip k_grad_nonfinite / k_amp_prepare / k_adamw<., true> /
-k_amp_update): a skipped step costs no read-back, the host never waits for the GPU.
+those semantics for the flat optimisers of :mod:`mm2d3d_amd.optimizers` (adamw, adam, sgd, rmsprop; a mixed list takes ONE joint
+decision) - with the scale, the non-finite flags, the clean-step tracker and the optimisers' step counters RESIDENT ON THE DEVICE
+(csrc/loss.hip k_grad_nonfinite / k_amp_prepare / k_adamw<., true> / k_amp_update, csrc/optim.hip k_optim_prepare /
+k_optim<., ., ., true>): a skipped step costs no read-back, the host never waits for the GPU.
 
     scaler = GradScaler(device)
     (loss * scaler.scale_tensor).backward()          # or scaler.scale(loss).backward()
@@ -41,7 +42,7 @@ class GradScaler:
     def _state(self, opt):
         k = id(opt)
         if k not in self._found:
-            nb = int(_lib.lib().mm_amp_coef_bytes())
+            nb = opt._coef_bytes()  # the optimiser's own coefficient struct (csrc/loss.hip AmpCoef / csrc/optim.hip OptCoef)
             if len(self._found) >= self._flags.numel() - self.N_SKIP:
                 raise RuntimeError("GradScaler: more than 12 optimisers")
             self._found[k] = self._flags[len(self._found) : len(self._found) + 1]
@@ -49,13 +50,18 @@ class GradScaler:
             self._coef[k] = torch.zeros((max(1, len(opt.param_groups)), nb), dtype=torch.uint8, device=self.device)
         return self._found[k], self._steps[k], self._coef[k]
 
+    @staticmethod
+    def _require_flat(opt):
+        if not hasattr(opt, "step_scaled"):
+            raise TypeError(f"GradScaler.step: {type(opt).__name__} is not a flat optimiser (mm2d3d_amd.optimizers: adamw, adam, sgd, "
+                            "rmsprop); other optimisers have no device-side skip")
+
     def step(self, opt, grad_scale: float = 1.0):
         """``opt.step()`` on the unscaled gradients unless one of ITS gradients is inf / nan (decided and applied on the device):
         the per-optimiser form of torch's GradScaler.step.  A trainer whose optimisers are one HybridOptim uses ``step_all``."""
         if not self.enabled:
             return opt.step(grad_scale=grad_scale)
-        if not hasattr(opt, "step_scaled"):
-            raise TypeError("GradScaler.step: the optimiser must be a FlatAdamW (adamw); other optimisers have no device-side skip")
+        self._require_flat(opt)
         found, steps, coef = self._state(opt)
         found.zero_()
         L = _lib.lib()
@@ -75,8 +81,7 @@ class GradScaler:
                 o.step(grad_scale=grad_scale, skip_words=skip_words) if hasattr(o, "step_scaled") else o.step()
             return
         for o in opts:
-            if not hasattr(o, "step_scaled"):
-                raise TypeError("GradScaler.step: the optimiser must be a FlatAdamW (adamw); other optimisers have no device-side skip")
+            self._require_flat(o)
         L = _lib.lib()
         states = [self._state(o) for o in opts]
         n = len(self._found)

@@ -2,7 +2,7 @@
 
 The reference wraps both nets in torch DDP (``DDPStrategy(find_unused_parameters=True)``, run.py:262-268):
 fp32 gradient buckets (25 MB) all-reduced over NCCL during backward.  MI355X-first restatement:
-  * gradients already live in the optimiser's flat arenas (mm2d3d_amd.optimizers.FlatAdamW), so a bucket is a
+  * gradients already live in the optimiser's flat arenas (mm2d3d_amd.optimizers: FlatAdamW / FlatAdam / FlatSGD / FlatRMSprop), so a bucket is a
     SLICE of an arena - no packing / unpacking copies;
   * buckets are cut in reverse parameter order (the order backward produces them) and launched from
     post-accumulate-grad hooks as soon as a bucket is complete, on RCCL's own stream, overlapping the rest of
@@ -17,7 +17,7 @@ fp32 gradient buckets (25 MB) all-reduced over NCCL during backward.  MI355X-fir
     receive a gradient later, ``finish()`` raises and the next step re-learns;
   * xGMI is point-to-point (7 links/GPU): fewer, larger messages are better than NVSwitch-style 25 MB buckets;
     default bucket = 64 MB (~196 MB of fp32 gradients -> 4 all-reduces per step);
-  * the sum is averaged inside the fused AdamW kernel (grad_scale = 1/world), not by an extra pass.
+  * the sum is averaged inside the fused optimiser kernel (grad_scale = 1/world), not by an extra pass.
 Schedules (``overlap``): "tail" (default, round 5) - the buckets go out from the hooks, beside backward, but only once the LAST
 grid-barrier kernel of the backward pass (the single-launch batch norms, csrc/fused_bn.h) has been queued: every batch norm keeps
 its single-launch kernel AND the collectives overlap the barrier-free tail of backward (layer1.0 / max-pool / stem backward of the
@@ -130,6 +130,12 @@ class GradAllReducer:
             self.bn_path = ("forward single-launch, backward three-kernel" if keep and (was2d | was3d) & 1
                             else "three-kernel in both directions" + (" (MM_DDP_BN_FUSED=0)" if not keep else ""))
         for opt in optimizers:
+            if not getattr(opt, "_arenas", None):
+                import warnings
+
+                warnings.warn(f"GradAllReducer: {type(opt).__name__} keeps no flat gradient arenas (not one of mm2d3d_amd.optimizers' "
+                              "adamw / adam / sgd / rmsprop): its gradients are NOT all-reduced, the ranks' weights will diverge",
+                              RuntimeWarning, stacklevel=2)
             for a in getattr(opt, "_arenas", []):
                 if a is None:
                     continue

@@ -1,11 +1,15 @@
 """Optimiser / scheduler factory with the reference's API (lib/optimizers.py:11-42).
 
 ``Optimizer(name, **kw).set_scheduler(name, **kw).build(params) -> (optimizer, scheduler | None)``.
-``adamw`` / ``adam`` build :class:`FlatAdamW`: parameters, gradients and both moments live in flat fp32 arenas
-(one allocation each), so the update is ONE fused HIP kernel per step (csrc/loss.hip k_adamw) instead of
-torch 1.11's per-tensor loop, and the data-parallel all-reduce runs on slices of the same
-gradient arena without packing copies (mm2d3d_amd/ddp.py).  Schedulers are torch's own host-side classes, as in
-the reference (``one_cycle`` cycles lr AND beta1, which FlatAdamW reads from ``param_groups`` every step).
+The four names of the reference's registry build flat optimisers: ``adamw`` -> :class:`FlatAdamW`, ``adam`` -> :class:`FlatAdam`
+(weight decay as L2, torch.optim.Adam), ``sgd`` -> :class:`FlatSGD`, ``rmsprop`` -> :class:`FlatRMSprop`.  Parameters, gradients
+and the optimiser's state live in flat fp32 arenas (one allocation each), so the update is ONE fused HIP kernel per step
+(csrc/loss.hip k_adamw for AdamW, csrc/optim.hip k_optim for the others and for ``amsgrad``) instead of torch's per-tensor loop
+(SURVEY.md K16), the data-parallel all-reduce runs on slices of the same gradient arena without packing copies
+(mm2d3d_amd/ddp.py), backward kernels may accumulate straight into it (mm2d3d_amd/gradsink.py) and the loss scale of the fp16
+mode can skip a step on the device (mm2d3d_amd/amp.py).  ``param_groups`` / ``defaults`` carry the keys of torch's classes, and
+every hyper-parameter is read from ``param_groups`` on each step: schedulers are torch's own host-side classes, as in the
+reference (``one_cycle`` cycles lr AND momentum, or beta1 where the optimiser has ``betas``).
 """
 from __future__ import annotations
 
@@ -16,18 +20,29 @@ from torch.optim import lr_scheduler
 from . import _lib
 from ._lib import check, ptr, stream
 
-__all__ = ["Optimizer", "FlatAdamW"]
+__all__ = ["Optimizer", "FlatAdamW", "FlatAdam", "FlatSGD", "FlatRMSprop"]
 
 
-class FlatAdamW(optim.Optimizer):
-    """AdamW (decoupled weight decay, torch semantics) over flat arenas.  ``adam_l2=True`` gives plain Adam (L2 in grad)."""
+def _only_supported(name, maximize=False, **flags):
+    """Arguments torch accepts that do not apply to a fused flat update: fine when None / False."""
+    if maximize:
+        raise NotImplementedError(f"{name}: maximize=True is not implemented")
+    for k, v in flags.items():
+        if v:
+            raise NotImplementedError(f"{name}: {k}=True does not apply (the update is one fused HIP kernel over flat arenas)")
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
-        if amsgrad:
-            raise NotImplementedError("amsgrad is not on the hot path")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+class _FlatOptimizer(optim.Optimizer):
+    """What the flat optimisers share: the arenas (``params, p, g, spans, touched`` + the state arrays named by
+    ``_state_names(group)``, allocated only when the hyper-parameters need them), the gradient sinks, the step counter that
+    lives on the host or on the device, and the checkpoint format.  A subclass supplies ``_state_names``, ``_coef_bytes`` and
+    the three launches ``_plain`` / ``_prepare`` / ``_scaled``."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self._arenas = []
         self._step = 0
+        self._own = None  # device state of step(skip_words=): unit scale, step counter, coefficient rows
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.requires_grad]
             if not ps:
@@ -45,8 +60,8 @@ class FlatAdamW(optim.Optimizer):
                 p.grad = flat_g[off : off + k].view(p.shape)
                 spans.append((off, off + k))
                 off += k
-            arena = dict(params=ps, p=flat_p, g=flat_g, m=torch.zeros_like(flat_p), v=torch.zeros_like(flat_p), spans=spans,
-                         touched=[False] * len(ps))
+            arena = dict(params=ps, p=flat_p, g=flat_g, spans=spans, touched=[False] * len(ps), state=())
+            self._ensure_state(group, arena)
             for i, p in enumerate(ps):
                 hook = self._make_hook(arena, i)
                 p.register_post_accumulate_grad_hook(hook)
@@ -57,6 +72,34 @@ class FlatAdamW(optim.Optimizer):
                 p._mm_pending = 0
                 p._mm_hooks = [hook]
             self._arenas.append(arena)
+
+    # ------------------------------------------------------------------ what a subclass supplies
+    def _state_names(self, group):
+        raise NotImplementedError
+
+    def _coef_bytes(self):
+        """Size of one parameter group's device coefficients (mm2d3d_amd/amp.py sizes its buffer by it)."""
+        return int(_lib.lib().mm_optim_coef_bytes())
+
+    def _plain(self, L, group, a, lo, hi, grad_scale, skip_words):
+        raise NotImplementedError
+
+    def _prepare(self, L, group, scale_dev, found_dev, step_dev, advance, grad_scale, coef):
+        raise NotImplementedError
+
+    def _scaled(self, L, group, a, lo, hi, coef):
+        raise NotImplementedError
+
+    # a skipped step(skip_words=) does not use up a step of the counter (FlatAdamW without amsgrad keeps its host counter)
+    _skips_on_device = True
+
+    # ------------------------------------------------------------------ arenas
+    def _ensure_state(self, group, a):
+        """State arrays the group's CURRENT hyper-parameters need (a scheduler may have switched momentum on): zero-filled."""
+        for name in self._state_names(group):
+            if name not in a:
+                a[name] = torch.zeros_like(a["p"])
+                a["state"] = a["state"] + (name,)
 
     @staticmethod
     def _make_hook(arena, i):
@@ -95,71 +138,9 @@ class FlatAdamW(optim.Optimizer):
             if a is not None:
                 a["touched"] = [True] * len(a["params"])
 
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0, skip_words=None):
-        """``skip_words``: device int32 words (<= 16) - the update is a no-op on the device when any of them is nonzero (the
-        data-parallel reducer's collective flags, ddp.GradAllReducer.skip_words: no read-back, the host never waits).  The HOST step
-        counter (Adam's bias correction) advances even when the device skipped the update: the host learns of a flagged step one step
-        late and the trainer raises then (train.py), so training does not continue on that counter; ``step_scaled`` (the fp16 path)
-        keeps its counter on the device and does not advance it for a skipped step."""
-        loss = closure() if closure is not None else None
-        if any(a is not None and a["p"].device.type != "cuda" for a in self._arenas):
-            raise RuntimeError("FlatAdamW.step: parameters must be on the GPU (the update is a HIP kernel, no CPU fallback)")
-        L = _lib.lib()
-        if getattr(self, "_dev_step", None) is not None:
-            # plain step after loss-scaled ones: the device counter is the truth (skipped steps never advanced it); one read-back,
-            # then the host counter leads again
-            self._step = int(self._dev_step.item())
-            self._dev_step = None
-        self._step += 1
-        from . import conv2d as _c2d
-
-        _c2d.PARAM_EPOCH[0] += 1  # packed bf16 weight copies are stale after this update
-        for group, a in zip(self.param_groups, self._arenas):
-            if a is None:
-                continue
-            b1, b2 = group["betas"]
-            for lo, hi in self._touched_ranges(a):
-                check(L.mm_adamw_step(ptr(a["p"][lo:hi]), ptr(a["g"][lo:hi]), ptr(a["m"][lo:hi]), ptr(a["v"][lo:hi]), hi - lo,
-                                      float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                      float(group["weight_decay"]), self._step, float(grad_scale), ptr(skip_words),
-                                      0 if skip_words is None else int(skip_words.numel()), stream()), "adamw_step")
-        return loss
-
-    @torch.no_grad()
-    def step_scaled(self, scale_dev, found_dev, step_dev, coef_dev, grad_scale: float = 1.0):
-        """The update of ``step`` under a device-resident loss scale (mm2d3d_amd/amp.py): gradients are multiplied by
-        ``grad_scale / scale``, and nothing is updated when ANY word of ``found_dev`` is set (the non-finite flags of every optimiser
-        of the step + the caller's skip words: one decision for all, as the reference's HybridOptim gets from Lightning's
-        GradScaler, train.py:627-636) - decided on the device, the step counter of the bias corrections (``step_dev``) advances
-        only when the step is taken."""
-        if any(a is not None and a["p"].device.type != "cuda" for a in self._arenas):
-            raise RuntimeError("FlatAdamW.step_scaled: parameters must be on the GPU (the update is a HIP kernel, no CPU fallback)")
-        L = _lib.lib()
-        if getattr(self, "_dev_step", None) is not step_dev:
-            # first scaled step, or the first after plain steps / a restored checkpoint: the host counter is the truth until now
-            step_dev.fill_(int(self._step))
-        self._dev_step = step_dev
-        self._opt_called = True  # what torch's lr schedulers look at to tell "step() before scheduler.step()"
-        from . import conv2d as _c2d
-
-        _c2d.PARAM_EPOCH[0] += 1
-        first = True
-        for gi, (group, a) in enumerate(zip(self.param_groups, self._arenas)):
-            if a is None:
-                continue
-            b1, b2 = group["betas"]
-            check(L.mm_amp_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), 1 if first else 0, float(group["lr"]), float(b1),
-                                   float(b2), float(group["eps"]), float(group["weight_decay"]), float(grad_scale),
-                                   ptr(coef_dev[gi]), stream()), "amp_prepare")
-            first = False
-            for lo, hi in self._touched_ranges(a):
-                check(L.mm_adamw_step_dev(ptr(a["p"][lo:hi]), ptr(a["g"][lo:hi]), ptr(a["m"][lo:hi]), ptr(a["v"][lo:hi]), hi - lo,
-                                          ptr(coef_dev[gi]), stream()), "adamw_step_dev")
-
     @staticmethod
     def _touched_ranges(a):
-        """Parameters that took part in no backward keep weights and moments (torch skips grad=None params)."""
+        """Parameters that took part in no backward keep weights and state (torch skips grad=None params)."""
         ranges, cur = [], None
         for t, (lo, hi) in zip(a["touched"], a["spans"]):
             if t:
@@ -171,10 +152,78 @@ class FlatAdamW(optim.Optimizer):
             ranges.append(cur)
         return ranges
 
+    def _require_gpu(self, what):
+        if any(a is not None and a["p"].device.type != "cuda" for a in self._arenas):
+            raise RuntimeError(f"{type(self).__name__}.{what}: parameters must be on the GPU (the update is a HIP kernel, no CPU fallback)")
+
+    # ------------------------------------------------------------------ steps
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0, skip_words=None):
+        """``skip_words``: device int32 words (<= 16) - the update is a no-op on the device when any of them is nonzero (the
+        data-parallel reducer's collective flags, ddp.GradAllReducer.skip_words: no read-back, the host never waits).  The step
+        then runs in the form of ``step_scaled`` with a unit scale and the counter on the device, so a skipped step does not use
+        up a step of the counter (Adam's bias corrections, SGD's first-step rule)."""
+        loss = closure() if closure is not None else None
+        self._require_gpu("step")
+        if skip_words is not None and self._skips_on_device:
+            if self._own is None:
+                dev = next(a["p"].device for a in self._arenas if a is not None)
+                self._own = (torch.ones(1, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                             torch.zeros((max(1, len(self.param_groups)), self._coef_bytes()), dtype=torch.uint8, device=dev))
+            self.step_scaled(self._own[0], skip_words, self._own[1], self._own[2], grad_scale)
+            return loss
+        L = _lib.lib()
+        if getattr(self, "_dev_step", None) is not None:
+            # plain step after device-counted ones: the device counter is the truth (skipped steps never advanced it); one
+            # read-back, then the host counter leads again
+            self._step = int(self._dev_step.item())
+            self._dev_step = None
+        self._step += 1
+        from . import conv2d as _c2d
+
+        _c2d.PARAM_EPOCH[0] += 1  # packed bf16 weight copies are stale after this update
+        for group, a in zip(self.param_groups, self._arenas):
+            if a is None:
+                continue
+            self._ensure_state(group, a)
+            for lo, hi in self._touched_ranges(a):
+                self._plain(L, group, a, lo, hi, float(grad_scale), skip_words)
+        return loss
+
+    @torch.no_grad()
+    def step_scaled(self, scale_dev, found_dev, step_dev, coef_dev, grad_scale: float = 1.0):
+        """The update of ``step`` under a device-resident loss scale (mm2d3d_amd/amp.py): gradients are multiplied by
+        ``grad_scale / scale``, and nothing is updated when ANY word of ``found_dev`` is set (the non-finite flags of every optimiser
+        of the step + the caller's skip words: one decision for all, as the reference's HybridOptim gets from Lightning's
+        GradScaler, train.py:627-636) - decided on the device; the step counter (``step_dev``) advances only when the step is
+        taken."""
+        self._require_gpu("step_scaled")
+        L = _lib.lib()
+        if getattr(self, "_dev_step", None) is not step_dev:
+            if getattr(self, "_dev_step", None) is not None:  # another device counter led until now (one read-back)
+                self._step = int(self._dev_step.item())
+            # first device-counted step, or the first after plain steps / a restored checkpoint: the host counter is the truth until now
+            step_dev.fill_(int(self._step))
+        self._dev_step = step_dev
+        self._opt_called = True  # what torch's lr schedulers look at to tell "step() before scheduler.step()"
+        from . import conv2d as _c2d
+
+        _c2d.PARAM_EPOCH[0] += 1
+        first = True
+        for gi, (group, a) in enumerate(zip(self.param_groups, self._arenas)):
+            if a is None:
+                continue
+            self._ensure_state(group, a)
+            self._prepare(L, group, scale_dev, found_dev, step_dev, 1 if first else 0, float(grad_scale), coef_dev[gi])
+            first = False
+            for lo, hi in self._touched_ranges(a):
+                self._scaled(L, group, a, lo, hi, coef_dev[gi])
+
+    # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         sd = super().state_dict()
-        sd["flat"] = [None if a is None else dict(m=a["m"].clone(), v=a["v"].clone()) for a in self._arenas]
-        if getattr(self, "_dev_step", None) is not None:  # loss-scaled training: the device counter is the truth (skipped steps)
+        sd["flat"] = [None if a is None else {name: a[name].clone() for name in a["state"]} for a in self._arenas]
+        if getattr(self, "_dev_step", None) is not None:  # device-counted steps: the device counter is the truth (skipped steps)
             self._step = int(self._dev_step.item())
         sd["step"] = self._step
         return sd
@@ -187,8 +236,163 @@ class FlatAdamW(optim.Optimizer):
         if flat:
             for a, f in zip(self._arenas, flat):
                 if a is not None and f is not None:
-                    a["m"].copy_(f["m"])
-                    a["v"].copy_(f["v"])
+                    for name, t in f.items():
+                        if name not in a:
+                            a[name] = torch.zeros_like(a["p"])
+                            a["state"] = a["state"] + (name,)
+                        a[name].copy_(t)
+
+
+def _range(a, names, lo, hi):
+    """Pointers of the slices [lo, hi) of the named arrays; None for a name the arena does not hold."""
+    return [ptr(a[n][lo:hi]) if n is not None else None for n in names]
+
+
+class FlatAdamW(_FlatOptimizer):
+    """AdamW (decoupled weight decay, torch.optim.AdamW semantics) over flat arenas: state ``m``, ``v`` and, with ``amsgrad``,
+    ``vmax``.  The bias corrections are keyed to the optimiser's step counter, not to a parameter's own: a parameter that first
+    receives a gradient on a later step differs from torch there.  Without ``amsgrad`` the update is k_adamw of csrc/loss.hip
+    (and ``step(skip_words=)`` keeps the counter on the host, which advances also when the device skipped the update: the
+    trainer raises one step later, train.py); with it, the Adam kernel of csrc/optim.hip with decoupled decay."""
+
+    _decoupled = 1
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None):
+        _only_supported(type(self).__name__, maximize, foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                                      foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused,
+                                      decoupled_weight_decay=bool(self._decoupled)))
+
+    def _adamw_kernel(self, group):
+        """The group runs on csrc/loss.hip's AdamW kernels (unchanged), not on csrc/optim.hip's Adam family."""
+        return bool(self._decoupled) and not group.get("amsgrad")
+
+    def _state_names(self, group):
+        return ("m", "v", "vmax") if group.get("amsgrad") else ("m", "v")
+
+    @property
+    def _skips_on_device(self):
+        return not all(self._adamw_kernel(g) for g in self.param_groups)
+
+    def _coef_bytes(self):
+        L = _lib.lib()
+        return max(int(L.mm_amp_coef_bytes()), int(L.mm_optim_coef_bytes()))
+
+    @staticmethod
+    def _hp(group):
+        b1, b2 = group["betas"]
+        return float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])
+
+    @staticmethod
+    def _arrays(group):
+        return ("p", "g", "m", "v", "vmax" if group.get("amsgrad") else None)
+
+    def _plain(self, L, group, a, lo, hi, grad_scale, skip_words):
+        nskip = 0 if skip_words is None else int(skip_words.numel())
+        if self._adamw_kernel(group):
+            check(L.mm_adamw_step(*_range(a, ("p", "g", "m", "v"), lo, hi), hi - lo, *self._hp(group), self._step, grad_scale,
+                                  ptr(skip_words), nskip, stream()), "adamw_step")
+        else:
+            check(L.mm_adam_step(*_range(a, self._arrays(group), lo, hi), hi - lo, *self._hp(group), self._decoupled, self._step,
+                                 grad_scale, ptr(skip_words), nskip, stream()), "adam_step")
+
+    def _prepare(self, L, group, scale_dev, found_dev, step_dev, advance, grad_scale, coef):
+        if self._adamw_kernel(group):
+            check(L.mm_amp_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
+                                   grad_scale, ptr(coef), stream()), "amp_prepare")
+        else:
+            check(L.mm_adam_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
+                                    self._decoupled, grad_scale, ptr(coef), stream()), "adam_prepare")
+
+    def _scaled(self, L, group, a, lo, hi, coef):
+        if self._adamw_kernel(group):
+            check(L.mm_adamw_step_dev(*_range(a, ("p", "g", "m", "v"), lo, hi), hi - lo, ptr(coef), stream()), "adamw_step_dev")
+        else:
+            check(L.mm_adam_step_dev(*_range(a, self._arrays(group), lo, hi), hi - lo, self._decoupled, ptr(coef), stream()),
+                  "adam_step_dev")
+
+
+class FlatAdam(FlatAdamW):
+    """torch.optim.Adam over flat arenas: weight decay is L2 (added to the gradient); ``amsgrad`` adds the state ``vmax``.  Bias
+    corrections are keyed to the optimiser's step counter, as :class:`FlatAdamW`'s are."""
+
+    _decoupled = 0
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        if decoupled_weight_decay:
+            raise NotImplementedError("FlatAdam: decoupled_weight_decay=True is FlatAdamW (adamw)")
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize, foreach=foreach, capturable=capturable,
+                         differentiable=differentiable, fused=fused)
+
+
+class FlatSGD(_FlatOptimizer):
+    """torch.optim.SGD over flat arenas: state ``buf`` (the momentum buffer) when ``momentum != 0``.  torch's first-step rule
+    (``buf = g``, no dampening) is keyed to the optimiser's counter of TAKEN steps - on the device in the loss-scaled form and
+    under ``step(skip_words=)``, so a skipped step does not use it up - not to a parameter's own: with ``dampening != 0`` a
+    parameter that first receives a gradient on a later step (or a momentum that a scheduler switches on later) differs from
+    torch there.  :class:`FlatAdamW`'s bias corrections are keyed the same way."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, foreach=None,
+                 differentiable=False, fused=None):
+        _only_supported("FlatSGD", maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                      maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused))
+
+    def _state_names(self, group):
+        return ("buf",) if group["momentum"] != 0 else ()
+
+    @staticmethod
+    def _hp(group):
+        return float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"])
+
+    def _plain(self, L, group, a, lo, hi, grad_scale, skip_words):
+        check(L.mm_sgd_step(*_range(a, ("p", "g", "buf" if group["momentum"] != 0 else None), lo, hi), hi - lo, *self._hp(group),
+                            int(bool(group["nesterov"])), self._step, grad_scale, ptr(skip_words),
+                            0 if skip_words is None else int(skip_words.numel()), stream()), "sgd_step")
+
+    def _prepare(self, L, group, scale_dev, found_dev, step_dev, advance, grad_scale, coef):
+        check(L.mm_sgd_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
+                               grad_scale, ptr(coef), stream()), "sgd_prepare")
+
+    def _scaled(self, L, group, a, lo, hi, coef):
+        check(L.mm_sgd_step_dev(*_range(a, ("p", "g", "buf" if group["momentum"] != 0 else None), lo, hi), hi - lo,
+                                int(bool(group["nesterov"])), ptr(coef), stream()), "sgd_step_dev")
+
+
+class FlatRMSprop(_FlatOptimizer):
+    """torch.optim.RMSprop over flat arenas: state ``sq``, plus ``gavg`` when ``centered`` and ``buf`` when ``momentum > 0``."""
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, capturable=False,
+                 foreach=None, maximize=False, differentiable=False):
+        _only_supported("FlatRMSprop", maximize, foreach=foreach, capturable=capturable, differentiable=differentiable)
+        super().__init__(params, dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered, weight_decay=weight_decay,
+                                      capturable=capturable, foreach=foreach, maximize=maximize, differentiable=differentiable))
+
+    def _state_names(self, group):
+        return ("sq",) + (("gavg",) if group["centered"] else ()) + (("buf",) if group["momentum"] > 0 else ())
+
+    @staticmethod
+    def _hp(group):
+        return float(group["lr"]), float(group["alpha"]), float(group["eps"]), float(group["weight_decay"]), float(group["momentum"])
+
+    @staticmethod
+    def _arrays(group):
+        return ("p", "g", "sq", "gavg" if group["centered"] else None, "buf" if group["momentum"] > 0 else None)
+
+    def _plain(self, L, group, a, lo, hi, grad_scale, skip_words):
+        check(L.mm_rmsprop_step(*_range(a, self._arrays(group), lo, hi), hi - lo, *self._hp(group), grad_scale, ptr(skip_words),
+                                0 if skip_words is None else int(skip_words.numel()), stream()), "rmsprop_step")
+
+    def _prepare(self, L, group, scale_dev, found_dev, step_dev, advance, grad_scale, coef):
+        check(L.mm_rmsprop_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
+                                   grad_scale, ptr(coef), stream()), "rmsprop_prepare")
+
+    def _scaled(self, L, group, a, lo, hi, coef):
+        check(L.mm_rmsprop_step_dev(*_range(a, self._arrays(group), lo, hi), hi - lo, ptr(coef), stream()), "rmsprop_step_dev")
 
 
 class Optimizer:
@@ -204,7 +408,7 @@ class Optimizer:
         return self
 
     def build(self, params):
-        table = {"adamw": FlatAdamW, "adam": optim.Adam, "sgd": optim.SGD, "rmsprop": optim.RMSprop}
+        table = {"adamw": FlatAdamW, "adam": FlatAdam, "sgd": FlatSGD, "rmsprop": FlatRMSprop}
         optimizer = table[self._optim_name](params, **self._optim_args)
         scheduler = None
         if self._use_scheduler:
