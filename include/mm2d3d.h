@@ -474,6 +474,27 @@ int mm_adam_step_dev(float* p, const float* g, float* m, float* v, float* vmax, 
 int mm_rmsprop_step_dev(float* p, const float* g, float* sq, float* gavg, float* buf, int64_t n, const void* coef_dev,
                         mm_stream_t stream);
 
+/* ---------------------------------------------------------------- gradient clipping for the flat optimisers (csrc/clip.hip)
+ * torch.nn.utils.clip_grad_norm_ (norm_type 2) / clip_grad_value_ on the TRUE gradient g * grad_scale / scale of arenas that hold
+ * loss-scaled, un-averaged gradients (Lightning's gradient_clip_val / gradient_clip_algorithm, EXP/run.py:262-288).  No read-back.
+ *   mm_grad_sqnorm     sum of squares of one fp32 arena in double (a finite arena never gives a non-finite sum): one double
+ *                      partial per workgroup into partial_ws[slot .. slot + mm_grad_sqnorm_ws_bytes(n) / 8).  Which workgroup
+ *                      sums which elements depends on n and on g's offset from a 16-byte boundary only, never on the device.
+ *                      found_dev (may be NULL): found_dev[0] = 1 if an element is inf / nan, as mm_grad_nonfinite sets it.
+ *   mm_clip_finalize   one workgroup: adds counts[0] + .. + counts[narenas - 1] consecutive partials (the arenas of EVERY
+ *                      optimiser of the step: one joint norm) in a fixed order, so the result is the same bits on every run;
+ *                      norm_out_dev[0] = sqrt(sum) * grad_scale / scale_dev[0] (fp32), c = min(1, max_norm / (norm + 1e-6)) as
+ *                      torch forms it (NaN for a NaN norm), eff_scale_out_dev[0] = scale_dev[0] / c.  Passed as scale_dev to
+ *                      mm_amp_prepare / mm_*_prepare, the effective scale makes the update kernels apply grad_scale * c / scale.
+ *                      mm_amp_update keeps the real scale.
+ *   mm_grad_clip_value clamps g in place to +-clip_value * scale_dev[0] / grad_scale, i.e. the true gradient to +-clip_value;
+ *                      a NaN passes through, as in torch.clamp. */
+size_t mm_grad_sqnorm_ws_bytes(int64_t n);
+int mm_grad_sqnorm(const float* g, int64_t n, void* partial_ws, int64_t slot, int* found_dev, mm_stream_t stream);
+int mm_clip_finalize(const void* partial_ws, const int64_t* counts, int narenas, const float* scale_dev, double grad_scale,
+                     double max_norm, float* norm_out_dev, float* eff_scale_out_dev, mm_stream_t stream);
+int mm_grad_clip_value(float* g, int64_t n, double clip_value, const float* scale_dev, double grad_scale, mm_stream_t stream);
+
 /* ---------------------------------------------------------------- dense 2D convolutions (csrc/conv2d.hip)
  * torch.nn.Conv2d / ConvTranspose2d of EXP/2d_net/backbones.py:43-65 and EXP/2d_net/model.py:64-82,104-123.
  * NHWC bf16 activations, fp32 accumulate.  mm_conv2d_gemm: out[m][n] = sum_{tap,k} A[src(m,tap)][k] * Wp[n][tap][k]

@@ -127,6 +127,10 @@ _PROTOS = {
     "mm_sgd_step_dev": (i32, [vp, vp, vp, i64, i32, vp, vp]),
     "mm_adam_step_dev": (i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     "mm_rmsprop_step_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp]),
+    "mm_grad_sqnorm_ws_bytes": (sz, [i64]),
+    "mm_grad_sqnorm": (i32, [vp, i64, vp, i64, vp, vp]),
+    "mm_clip_finalize": (i32, [vp, vp, i32, vp, f64, f64, vp, vp, vp]),
+    "mm_grad_clip_value": (i32, [vp, i64, f64, vp, f64, vp]),
     "mm_conv2d_gemm": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
                              vp, i32, i64, i32, vp, vp, i64, vp, i32, vp]),
     "mm_conv2d_3x3s1": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, i32, vp]),

@@ -13,6 +13,11 @@ k_optim<., ., ., true>): a skipped step costs no read-back, the host never waits
     (loss * scaler.scale_tensor).backward()          # or scaler.scale(loss).backward()
     scaler.step_all(optimizers, grad_scale)          # checks every gradient arena; ONE decision: all update, or none does
     scaler.update()
+
+``clip=`` of ``step`` / ``step_all`` clips the unscaled gradients between the check and the update (mm2d3d_amd/clip.py: a max
+norm, or ``("norm" | "value", x)``; the norm is joint over the optimisers of the call and is left in ``last_grad_norm``, a device
+tensor).  The norm kernel raises the non-finite flags itself, so a norm-clipped step reads the gradients once before the update,
+as an unclipped one does; the update kernels get ``scale / c`` for the scale, ``update()`` keeps the real one.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ class GradScaler:
         self._found = {}   # id(optimizer) -> int32[1] flag of the current step
         self._steps = {}   # id(optimizer) -> int64[1] device step counter (advances only on steps that are taken)
         self._coef = {}    # id(optimizer) -> uint8 coefficient rows, one per parameter group
+        self.last_grad_norm = None  # clip=("norm", x): the gradient norm of the last step before clipping (0-dim device tensor)
 
     def scale(self, loss):
         return loss * self.scale_tensor.to(loss.dtype) if self.enabled else loss
@@ -56,34 +62,61 @@ class GradScaler:
             raise TypeError(f"GradScaler.step: {type(opt).__name__} is not a flat optimiser (mm2d3d_amd.optimizers: adamw, adam, sgd, "
                             "rmsprop); other optimisers have no device-side skip")
 
-    def step(self, opt, grad_scale: float = 1.0):
+    def _check_and_clip(self, opts, founds, grad_scale, clip):
+        """The non-finite check of every arena into its optimiser's flag word and, between it and the update, the clip.  A step
+        that the flags veto stays skipped whatever the clip makes of its gradients."""
+        from .clip import clip_grad_norm_, clip_grad_value_, parse_clip
+
+        clip = parse_clip(clip)
+        if clip is not None and clip[0] == "norm":  # mm_grad_sqnorm raises the flags: no separate pass over the gradients
+            self.last_grad_norm = clip_grad_norm_(opts, clip[1], scaler=self, grad_scale=grad_scale, found=founds)
+            return
+        L = _lib.lib()
+        for o, found in zip(opts, founds):
+            for g in o.grad_arenas():
+                check(L.mm_grad_nonfinite(ptr(g), g.numel(), ptr(found), stream()), "grad_nonfinite")
+        if clip is not None:
+            clip_grad_value_(opts, clip[1], scaler=self, grad_scale=grad_scale)
+
+    def step(self, opt, grad_scale: float = 1.0, clip=None):
         """``opt.step()`` on the unscaled gradients unless one of ITS gradients is inf / nan (decided and applied on the device):
-        the per-optimiser form of torch's GradScaler.step.  A trainer whose optimisers are one HybridOptim uses ``step_all``."""
+        the per-optimiser form of torch's GradScaler.step.  A trainer whose optimisers are one HybridOptim uses ``step_all``.
+        ``clip``: see the module's docstring."""
         if not self.enabled:
+            self._clip_unscaled([opt], grad_scale, clip)
             return opt.step(grad_scale=grad_scale)
         self._require_flat(opt)
         found, steps, coef = self._state(opt)
         found.zero_()
-        L = _lib.lib()
-        for g in opt.grad_arenas():
-            check(L.mm_grad_nonfinite(ptr(g), g.numel(), ptr(found), stream()), "grad_nonfinite")
+        self._check_and_clip([opt], [found], grad_scale, clip)
         opt.step_scaled(self.scale_tensor, found, steps, coef, grad_scale)
+
+    def _clip_unscaled(self, opts, grad_scale, clip):
+        """A disabled scaler: the clip of steps without a loss scale (a non-flat optimiser raises TypeError)."""
+        from .clip import clip_grad_norm_, clip_grad_value_, parse_clip
+
+        clip = parse_clip(clip)
+        if clip is not None and clip[0] == "norm":
+            self.last_grad_norm = clip_grad_norm_(opts, clip[1], grad_scale=grad_scale)
+        elif clip is not None:
+            clip_grad_value_(opts, clip[1], grad_scale=grad_scale)
 
     N_SKIP = 4  # words [12, 16) of the flag buffer: the caller's extra skip words (ddp.GradAllReducer.skip_words)
 
-    def step_all(self, opts, grad_scale: float = 1.0, skip_words=None):
+    def step_all(self, opts, grad_scale: float = 1.0, skip_words=None, clip=None):
         """The steps of ALL optimisers of a training step under one decision: the reference's HybridOptim is ONE
         optimiser to Lightning's GradScaler (``param_groups`` is the concatenation, train.py:627-636), so a non-finite gradient
         in either network skips both updates.  ``skip_words``: up to 4 more device int32 words that veto the step (the
-        data-parallel reducer's collective "gradients invalid" flags) - they do not touch the loss scale."""
+        data-parallel reducer's collective "gradients invalid" flags) - they do not touch the loss scale.  ``clip``: see the
+        module's docstring; one norm over all of ``opts``."""
         if not self.enabled:
+            self._clip_unscaled(opts, grad_scale, clip)
             for o in opts:
                 o.step(grad_scale=grad_scale, skip_words=skip_words) if hasattr(o, "step_scaled") else o.step()
             return
         for o in opts:
             self._require_flat(o)
-        L = _lib.lib()
-        states = [self._state(o) for o in opts]
+        states =[self._state(o) for o in opts]
         n = len(self._found)
         if n > self._flags.numel() - self.N_SKIP:
             raise RuntimeError("GradScaler: more than 12 optimisers")
@@ -93,9 +126,7 @@ class GradScaler:
             if k > self.N_SKIP:
                 raise ValueError("GradScaler.step_all: at most 4 skip words")
             self._flags[self._flags.numel() - self.N_SKIP : self._flags.numel() - self.N_SKIP + k].copy_(skip_words)
-        for o, (found, _, _) in zip(opts, states):
-            for g in o.grad_arenas():
-                check(L.mm_grad_nonfinite(ptr(g), g.numel(), ptr(found), stream()), "grad_nonfinite")
+        self._check_and_clip(opts, [found for found, _, _ in states], grad_scale, clip)
         for o, (_, steps, coef) in zip(opts, states):
             o.step_scaled(self.scale_tensor, self._flags, steps, coef, grad_scale)
 

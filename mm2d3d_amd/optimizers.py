@@ -19,8 +19,9 @@ from torch.optim import lr_scheduler
 
 from . import _lib
 from ._lib import check, ptr, stream
+from .clip import clip_grad_norm_, clip_grad_value_
 
-__all__ = ["Optimizer", "FlatAdamW", "FlatAdam", "FlatSGD", "FlatRMSprop"]
+__all__ = ["Optimizer", "FlatAdamW", "FlatAdam", "FlatSGD", "FlatRMSprop", "clip_grad_norm_", "clip_grad_value_"]
 
 
 def _only_supported(name, maximize=False, **flags):
@@ -42,7 +43,8 @@ class _FlatOptimizer(optim.Optimizer):
         super().__init__(params, defaults)
         self._arenas = []
         self._step = 0
-        self._own = None  # device state of step(skip_words=): unit scale, step counter, coefficient rows
+        self._own = None  # device state of step(skip_words=): unit scale, step counter, coefficient rows, a zero flag word
+        self._clip_scale = None  # clip.clip_grad_norm_: the effective scale (device) the NEXT step takes in place of the loss scale
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.requires_grad]
             if not ps:
@@ -123,6 +125,7 @@ class _FlatOptimizer(optim.Optimizer):
         from . import gradsink
 
         gradsink.reset_deferred()
+        self._clip_scale = None  # a clip coefficient belongs to the gradients it was formed from
         for a in self._arenas:
             if a is None:
                 continue
@@ -162,15 +165,17 @@ class _FlatOptimizer(optim.Optimizer):
         """``skip_words``: device int32 words (<= 16) - the update is a no-op on the device when any of them is nonzero (the
         data-parallel reducer's collective flags, ddp.GradAllReducer.skip_words: no read-back, the host never waits).  The step
         then runs in the form of ``step_scaled`` with a unit scale and the counter on the device, so a skipped step does not use
-        up a step of the counter (Adam's bias corrections, SGD's first-step rule)."""
+        up a step of the counter (Adam's bias corrections, SGD's first-step rule).  A step after ``clip.clip_grad_norm_`` takes that
+        form too, for every optimiser: the clip coefficient exists on the device only."""
         loss = closure() if closure is not None else None
         self._require_gpu("step")
-        if skip_words is not None and self._skips_on_device:
+        if self._clip_scale is not None or (skip_words is not None and self._skips_on_device):
             if self._own is None:
                 dev = next(a["p"].device for a in self._arenas if a is not None)
                 self._own = (torch.ones(1, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
-                             torch.zeros((max(1, len(self.param_groups)), self._coef_bytes()), dtype=torch.uint8, device=dev))
-            self.step_scaled(self._own[0], skip_words, self._own[1], self._own[2], grad_scale)
+                             torch.zeros((max(1, len(self.param_groups)), self._coef_bytes()), dtype=torch.uint8, device=dev),
+                             torch.zeros(1, dtype=torch.int32, device=dev))
+            self.step_scaled(self._own[0], self._own[3] if skip_words is None else skip_words, self._own[1], self._own[2], grad_scale)
             return loss
         L = _lib.lib()
         if getattr(self, "_dev_step", None) is not None:
@@ -196,9 +201,11 @@ class _FlatOptimizer(optim.Optimizer):
         ``grad_scale / scale``, and nothing is updated when ANY word of ``found_dev`` is set (the non-finite flags of every optimiser
         of the step + the caller's skip words: one decision for all, as the reference's HybridOptim gets from Lightning's
         GradScaler, train.py:627-636) - decided on the device; the step counter (``step_dev``) advances only when the step is
-        taken."""
+        taken.  After ``clip.clip_grad_norm_`` the clip's effective scale ``scale / c`` stands in for ``scale_dev``, once."""
         self._require_gpu("step_scaled")
         L = _lib.lib()
+        if self._clip_scale is not None:
+            scale_dev, self._clip_scale = self._clip_scale, None
         if getattr(self, "_dev_step", None) is not step_dev:
             if getattr(self, "_dev_step", None) is not None:  # another device counter led until now (one read-back)
                 self._step = int(self._dev_step.item())

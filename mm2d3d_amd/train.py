@@ -60,6 +60,14 @@ class TrainModel(nn.Module):
         # arguments (init_scale, growth_interval, ...).
         self._scaler_cfg = train_kwargs.get("loss_scale", nn2d.half_kind() == "fp16" or scn.ACTIVATION_DTYPE[0] == torch.float16)
         self.scaler = None
+        # Lightning's Trainer(gradient_clip_val=, gradient_clip_algorithm=) (the reference's run.py:262-288 passes the trainer's
+        # arguments through): None = off; "norm" clips ONE 2-norm over both networks' gradients (HybridOptim's param_groups is
+        # the concatenation, train.py:587-592), "value" clamps every element.  On the reduced, unscaled gradients, on the device
+        # (mm2d3d_amd/clip.py); ``last_grad_norm``: the norm before clipping of the last "norm" step, a device tensor.
+        from .clip import parse_clip
+
+        self._clip = parse_clip((train_kwargs.get("gradient_clip_algorithm") or "norm", train_kwargs.get("gradient_clip_val")))
+        self.last_grad_norm = None
         # The trainer's own C-ABI handle (include/mm2d3d.h mm_create: grid-barrier words, fault word and switches of the
         # single-launch batch norms) - two trainers in one process do not share switches.  ``bn2d_fused`` / ``bn3d_fused``: bit 0 =
         # forward, bit 1 = backward single-launch kernels (default: the environment's MM_BN2D_FUSED / MM_BN_FUSED, else 3).
@@ -540,9 +548,18 @@ class TrainModel(nn.Module):
             self._raise_bn_fault("this step")
         skip = self.reducer.skip_words()
         if self.scaler is not None:
-            self.scaler.step_all(self.optimizers, self.reducer.grad_scale, skip_words=skip)
+            self.scaler.step_all(self.optimizers, self.reducer.grad_scale, skip_words=skip, clip=self._clip)
             self.scaler.update()
+            if self._clip is not None:
+                self.last_grad_norm = self.scaler.last_grad_norm
         else:
+            if self._clip is not None:
+                from .clip import clip_grad_norm_, clip_grad_value_
+
+                if self._clip[0] == "norm":
+                    self.last_grad_norm = clip_grad_norm_(self.optimizers, self._clip[1], grad_scale=self.reducer.grad_scale)
+                else:
+                    clip_grad_value_(self.optimizers, self._clip[1], grad_scale=self.reducer.grad_scale)
             for o in self.optimizers:
                 if hasattr(o, "grad_arenas"):
                     o.step(grad_scale=self.reducer.grad_scale, skip_words=skip)
