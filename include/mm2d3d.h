@@ -360,7 +360,7 @@ int mm_linear_bwd(const float* x, int ld_x, const float* dy, int ld_dy, int64_t 
                   float* dx, int ld_dx, int accumulate_dx, float* dw, float* db, int accumulate_w, void* ws,
                   size_t ws_bytes, mm_stream_t stream);
 
-/* ---------------------------------------------------------------- losses, lifting, optimiser (csrc/loss.hip) */
+/* ---------------------------------------------------------------- losses, lifting, evaluation (csrc/loss.hip) */
 size_t mm_loss_ws_bytes(void);
 /* weighted cross entropy, ignore_index, weighted-mean reduction (lib/losses.py:55-68 -> F.cross_entropy).
  * stats[0] = loss, stats[1] = sum of the class weights of the counted rows */
@@ -417,41 +417,32 @@ int mm_pselab_predict(const float* logits2d, int ld2, const float* logits3d, int
 size_t mm_pselab_refine_ws_bytes(int C);
 int mm_pselab_refine(const float* probs, const int64_t* labels, int64_t N, int C, int64_t ignore_label, int64_t* labels_out,
                      void* ws, size_t ws_bytes, mm_stream_t stream);
-/* torch.optim.AdamW update over flat fp32 arenas (EXP/train.py:627-636); step counts from 1; g is multiplied by grad_scale.
- * skip_dev / nskip (0 .. 16, may be NULL / 0): device words - the update is a no-op when any of them is nonzero (the
- * data-parallel reducer's collective "this step's gradients are invalid" flags: decided on the device, no read-back) */
-int mm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                  double eps, double weight_decay, int64_t step, double grad_scale, const int* skip_dev, int nskip,
-                  mm_stream_t stream);
-/* Loss-scaled steps (the fp16 kind of the 16-bit activation mode; torch.cuda.amp.GradScaler semantics as driven by the
- * reference's ``precision: 16`` trainer, train.yaml:11) WITHOUT a read-back: scale, non-finite flag, clean-step tracker and
- * step counter live on the device.  mm_grad_nonfinite: found_dev[0] = 1 if any gradient is inf / nan (the caller zeroes it);
- * mm_amp_prepare: the coefficients of one parameter group's update (mm_amp_coef_bytes bytes) incl. 1 / scale and "skip" =
- * any of found_dev[0 .. nfound) set - the flags of EVERY optimiser of the step (the reference's HybridOptim is one optimiser to
- * the GradScaler, EXP/train.py:627-636: an overflow in either network skips both updates) plus the caller's extra skip words;
- * mm_adamw_step_dev: mm_adamw_step with those coefficients, a no-op when skip is set; mm_amp_update: GradScaler.update(). */
-int mm_grad_nonfinite(const float* g, int64_t n, int* found_dev, mm_stream_t stream);
-int mm_amp_coef_bytes(void);
-int mm_amp_prepare(const float* scale_dev, const int* found_dev, int nfound, int64_t* step_dev, int advance, double lr, double beta1,
-                   double beta2, double eps, double weight_decay, double grad_scale, void* coef_dev, mm_stream_t stream);
-int mm_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const void* coef_dev, mm_stream_t stream);
-int mm_amp_update(float* scale_dev, int* tracker_dev, const int* found_dev, int nfound, double growth, double backoff, int interval,
-                  mm_stream_t stream);
 
-/* ---------------------------------------------------------------- SGD / Adam / RMSprop over flat arenas (csrc/optim.hip)
- * The other three names of the reference's optimiser registry (lib/optimizers.py: adamw, adam, sgd, rmsprop), one fused launch
- * per touched range like mm_adamw_step: fp32 arithmetic in the op order of torch.optim.{SGD, Adam, RMSprop}'s single-tensor
- * paths, g is multiplied by grad_scale, skip_dev / nskip as for mm_adamw_step.  A state array that the hyper-parameters do not
- * need is NULL and is neither read nor written; a non-NULL pointer selects the variant:
+/* ---------------------------------------------------------------- AdamW / Adam / SGD / RMSprop over flat arenas (csrc/optim.hip)
+ * The four names of the reference's optimiser registry (lib/optimizers.py: adamw, adam, sgd, rmsprop; its trainer runs AdamW,
+ * EXP/train.py:627-636), one fused launch per touched range: fp32 arithmetic in the op order of torch.optim.{SGD, Adam, AdamW,
+ * RMSprop}'s single-tensor paths, g is multiplied by grad_scale.  skip_dev / nskip (0 .. 16, may be NULL / 0): device words - the
+ * update is a no-op when any of them is nonzero (the data-parallel reducer's collective "this step's gradients are invalid" flags:
+ * decided on the device, no read-back).  A state array that the hyper-parameters do not need is NULL and is neither read nor
+ * written; a non-NULL pointer selects the variant:
  *   mm_sgd_step      buf = momentum buffer (NULL: no momentum); nesterov needs it.  ``step`` counts the optimiser's taken steps
  *                    from 1: on step 1 buf = g (torch's rule, no dampening), afterwards buf = momentum*buf + (1-dampening)*g.
  *   mm_adam_step     m, v; vmax = amsgrad's running maximum of v (NULL: amsgrad off).  decoupled = 0: weight decay is L2
- *                    (torch.optim.Adam); 1: p *= 1 - lr*wd (torch.optim.AdamW).  ``step`` drives the bias corrections.
+ *                    (torch.optim.Adam); 1: p *= 1 - lr*wd (torch.optim.AdamW).  ``step`` (from 1) drives the bias corrections.
  *   mm_rmsprop_step  sq; gavg = gradient average (NULL: not centered); buf = momentum buffer (NULL: no momentum).
- * Loss-scaled form, as mm_amp_prepare / mm_adamw_step_dev: mm_*_prepare (one thread) writes one parameter group's coefficients
- * (mm_optim_coef_bytes bytes: 1 / scale, "skip" = any of found_dev[0 .. nfound) set, Adam's bias corrections, SGD's first-step
- * rule) from the device-resident scale, flag words and step counter, which advances only when the step is taken and ``advance``
- * is set; mm_*_step_dev applies them and is a no-op when they say "skip".  No read-back anywhere. */
+ * Loss-scaled form (the fp16 kind of the 16-bit activation mode; torch.cuda.amp.GradScaler semantics as driven by the reference's
+ * ``precision: 16`` trainer, train.yaml:11) WITHOUT a read-back: scale, non-finite flags, clean-step tracker and step counter
+ * live on the device.  mm_grad_nonfinite: found_dev[0] = 1 if any gradient is inf / nan (the caller zeroes it).  mm_*_prepare
+ * (one thread) writes one parameter group's coefficients (mm_optim_coef_bytes bytes: 1 / scale, Adam's bias corrections, SGD's
+ * first-step rule, and "skip") from the device-resident scale, flag words and step counter.  "skip" = any of
+ * found_dev[0 .. nfound) set: ONE decision from the flags of EVERY optimiser of the step (the reference's HybridOptim is one
+ * optimiser to the GradScaler, EXP/train.py:627-636: an overflow in either network skips both updates) plus the caller's extra
+ * skip words.  The counter advances only when the step is taken and ``advance`` is set; ``advance`` is 1 for the first parameter
+ * group of an optimiser and 0 for the others, which read the step the first one committed.  mm_*_step_dev applies the
+ * coefficients and is a no-op when they say "skip"; mm_amp_update: GradScaler.update() on the real scale. */
+int mm_grad_nonfinite(const float* g, int64_t n, int* found_dev, mm_stream_t stream);
+int mm_amp_update(float* scale_dev, int* tracker_dev, const int* found_dev, int nfound, double growth, double backoff, int interval,
+                  mm_stream_t stream);
 int mm_optim_coef_bytes(void);
 int mm_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double dampening, double weight_decay,
                 int nesterov, int64_t step, double grad_scale, const int* skip_dev, int nskip, mm_stream_t stream);
@@ -485,7 +476,7 @@ int mm_rmsprop_step_dev(float* p, const float* g, float* sq, float* gavg, float*
  *                      optimiser of the step: one joint norm) in a fixed order, so the result is the same bits on every run;
  *                      norm_out_dev[0] = sqrt(sum) * grad_scale / scale_dev[0] (fp32), c = min(1, max_norm / (norm + 1e-6)) as
  *                      torch forms it (NaN for a NaN norm), eff_scale_out_dev[0] = scale_dev[0] / c.  Passed as scale_dev to
- *                      mm_amp_prepare / mm_*_prepare, the effective scale makes the update kernels apply grad_scale * c / scale.
+ *                      mm_*_prepare, the effective scale makes the update kernels apply grad_scale * c / scale.
  *                      mm_amp_update keeps the real scale.
  *   mm_grad_clip_value clamps g in place to +-clip_value * scale_dev[0] / grad_scale, i.e. the true gradient to +-clip_value;
  *                      a NaN passes through, as in torch.clamp. */

@@ -111,11 +111,7 @@ _PROTOS = {
     "mm_pselab_predict": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
     "mm_pselab_refine_ws_bytes": (sz, [i32]),
     "mm_pselab_refine": (i32, [vp, vp, i64, i32, i64, vp, vp, sz, vp]),
-    "mm_adamw_step": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i64, f64, vp, i32, vp]),
     "mm_grad_nonfinite": (i32, [vp, i64, vp, vp]),
-    "mm_amp_coef_bytes": (i32, []),
-    "mm_amp_prepare": (i32, [vp, vp, i32, vp, i32, f64, f64, f64, f64, f64, f64, vp, vp]),
-    "mm_adamw_step_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
     "mm_amp_update": (i32, [vp, vp, vp, i32, f64, f64, i32, vp]),
     "mm_optim_coef_bytes": (i32, []),
     "mm_sgd_step": (i32, [vp, vp, vp, i64, f64, f64, f64, f64, i32, i64, f64, vp, i32, vp]),

@@ -6,8 +6,8 @@ optimiser whose gradients hold an inf / nan skips its step, ``update()`` then ha
 IEEE fp16 gradient rows need that scale (bf16 rows do not: the default 16-bit kind here), so ``GradScaler`` below restates
 those semantics for the flat optimisers of :mod:`mm2d3d_amd.optimizers` (adamw, adam, sgd, rmsprop; a mixed list takes ONE joint
 decision) - with the scale, the non-finite flags, the clean-step tracker and the optimisers' step counters RESIDENT ON THE DEVICE
-(csrc/loss.hip k_grad_nonfinite / k_amp_prepare / k_adamw<., true> / k_amp_update, csrc/optim.hip k_optim_prepare /
-k_optim<., ., ., true>): a skipped step costs no read-back, the host never waits for the GPU.
+(csrc/optim.hip k_grad_nonfinite / k_optim_prepare / k_optim<., ., ., true> / k_amp_update): a skipped step costs no read-back,
+the host never waits for the GPU.
 
     scaler = GradScaler(device)
     (loss * scaler.scale_tensor).backward()          # or scaler.scale(loss).backward()
@@ -48,7 +48,7 @@ class GradScaler:
     def _state(self, opt):
         k = id(opt)
         if k not in self._found:
-            nb = opt._coef_bytes()  # the optimiser's own coefficient struct (csrc/loss.hip AmpCoef / csrc/optim.hip OptCoef)
+            nb = opt._coef_bytes()  # one coefficient struct per parameter group (csrc/optim.hip OptCoef)
             if len(self._found) >= self._flags.numel() - self.N_SKIP:
                 raise RuntimeError("GradScaler: more than 12 optimisers")
             self._found[k] = self._flags[len(self._found) : len(self._found) + 1]

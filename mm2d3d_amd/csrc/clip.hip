@@ -3,7 +3,7 @@
 //   k_grad_sqnorm     sum of squares of one fp32 arena, one double partial per workgroup (no atomics: the caller's workspace)
 //   k_clip_finalize   one workgroup: the partials of every arena of the step in a fixed order -> total norm, torch's clip
 //                     coefficient c = min(1, max_norm / (norm + 1e-6)) and the EFFECTIVE SCALE scale / c.  The update kernels
-//                     (loss.hip k_adamw, optim.hip k_optim) then apply grad_scale * c / scale through their prepare kernels,
+//                     (optim.hip k_optim) then apply grad_scale * c / scale through their prepare kernels,
 //                     unchanged: the clip costs one read of the gradients and no write.
 //   k_grad_clip_value clamp of an arena to +-clip_value * scale / grad_scale in place (NaN passes, as torch.clamp)
 // Sums are carried in double: an arena holds gradients times a loss scale of 2^16 .. 2^24 and more, whose squares leave fp32's

@@ -2,7 +2,7 @@
 //   weighted cross entropy, ignore_index, weighted-mean reduction   (/root/reference/lib/losses.py:55-68)
 //   cross-modal KL( softmax(target) || softmax(pred) ).sum(1).mean() (/root/reference/.../train.py:157-184)
 // plus the 2D->3D lifting gather and its deterministic backward (2d_net/model.py:131-137,166-173)
-// and the fused flat AdamW update (K16; train.py:627-636 -> torch.optim.AdamW).
+// and the evaluation's confusion matrices.  (The optimiser updates and the loss-scale kernels are in optim.hip.)
 // Block partial sums are fp64 and combined in a fixed order: bit-stable run to run.
 #include "common.h"
 #include "pointpred.h"
@@ -218,113 +218,6 @@ __global__ __launch_bounds__(T) void k_eval_confusion(const float* __restrict__ 
   for (int i = threadIdx.x; i < 3 * C * C; i += T)
     if (hist[i]) atomicAdd(&cm[i], (unsigned long long)hist[i]);
 }
-
-// ---- AdamW over flat fp32 arenas (torch.optim.AdamW semantics, amsgrad off; same op order as torch's
-// single-tensor path: p*=1-lr*wd; m.lerp_(g,1-b1); v=b2*v+(1-b2)*g*g; p-=step_size*m/(sqrt(v)/sqrt(bc2)+eps))
-// Loss-scaled training (mm2d3d_amd/amp.py, the fp16 kind of the 16-bit activation mode): the coefficients of an update live
-// on the DEVICE, written by k_amp_prepare from the device-resident loss scale, non-finite flag and step counter, so that a
-// skipped step (torch.cuda.amp.GradScaler semantics) needs no read-back: DEV = true reads them, and returns when skip is set.
-struct AmpCoef {
-  float decay, omb1, beta2, omb2, eps, step_size, bc2_sqrt, grad_scale;
-  int skip, pad;
-};
-
-template <bool VEC, bool DEV = false>
-__global__ __launch_bounds__(T) void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, int64_t n, float decay, float omb1, float beta2,
-                                              float omb2, float eps, float step_size, float bc2_sqrt, float grad_scale,
-                                              const AmpCoef* __restrict__ dc = nullptr, const int* __restrict__ skip = nullptr,
-                                              int nskip = 0) {
-  // skip words (the data-parallel reducer's collective "this step's gradients are invalid" flags, mm2d3d_amd/ddp.py): decided on
-  // the device, uniform - the host never reads them before queueing the update
-  for (int i = 0; i < nskip; i++)
-    if (skip[i]) return;
-  if (DEV) {
-    if (dc->skip) return;  // uniform
-    decay = dc->decay, omb1 = dc->omb1, beta2 = dc->beta2, omb2 = dc->omb2, eps = dc->eps, step_size = dc->step_size;
-    bc2_sqrt = dc->bc2_sqrt, grad_scale = dc->grad_scale;
-  }
-  int64_t i = ((int64_t)blockIdx.x * T + threadIdx.x) * 4;
-  if (i >= n) return;
-  auto upd = [&](float gj, float& pj, float& mj, float& vj) {
-    const float gi = gj * grad_scale;
-    const float pi = pj * decay;
-    const float mi = mj + omb1 * (gi - mj);
-    const float vi = beta2 * vj + omb2 * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pj = pi - step_size * (mi / denom);
-    mj = mi;
-    vj = vi;
-  };
-  if (VEC && i + 4 <= n) {  // 16-byte accesses (host: all four pointers 16-B aligned); same arithmetic per element
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 G = *(const f4*)(g + i);
-    f4 P = *(f4*)(p + i), M = *(f4*)(m + i), V = *(f4*)(v + i);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      float pj = P[j], mj = M[j], vj = V[j];
-      upd(G[j], pj, mj, vj);
-      P[j] = pj, M[j] = mj, V[j] = vj;
-    }
-    *(f4*)(p + i) = P;
-    *(f4*)(m + i) = M;
-    *(f4*)(v + i) = V;
-    return;
-  }
-  for (int j = 0; j < 4 && i + j < n; j++) upd(g[i + j], p[i + j], m[i + j], v[i + j]);  // a thread owns elements [i, i+4)
-}
-
-// found[0] |= any element of g is inf / nan (benign race: every writer stores 1)
-__global__ __launch_bounds__(T) void k_grad_nonfinite(const float* __restrict__ g, int64_t n, int* __restrict__ found) {
-  const int64_t stride = (int64_t)gridDim.x * T * 4;
-  bool bad = false;
-  for (int64_t i = ((int64_t)blockIdx.x * T + threadIdx.x) * 4; i < n; i += stride) {
-    if (i + 4 <= n && (((uintptr_t)(g + i)) & 15) == 0) {
-      typedef float f4 __attribute__((ext_vector_type(4)));
-      const f4 G = *(const f4*)(g + i);
-#pragma unroll
-      for (int j = 0; j < 4; j++) bad |= !(fabsf(G[j]) <= 3.402823466e38f);
-    } else {
-      for (int j = 0; j < 4 && i + j < n; j++) bad |= !(fabsf(g[i + j]) <= 3.402823466e38f);
-    }
-  }
-  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) found[0] = 1;
-}
-
-// one thread: the update coefficients of one parameter group from the device state.  t = *step + 1 is the step this update
-// would be; it is committed to *step only when the step is taken and ``advance`` is set (first group of an optimiser).
-__global__ void k_amp_prepare(const float* __restrict__ scale, const int* __restrict__ found, int nfound, long long* __restrict__ step,
-                              int advance, double lr, double beta1, double beta2, double eps, double weight_decay, double grad_scale,
-                              AmpCoef* __restrict__ out) {
-  // ONE decision for every optimiser of the step (the reference's HybridOptim is one optimiser to Lightning's GradScaler:
-  // train.py:627-636 - a non-finite gradient in either network skips both updates) and for the caller's extra skip words
-  int skip = 0;
-  for (int i = 0; i < nfound; i++) skip |= found[i] != 0;
-  const long long t = step[0] + (advance ? 1 : 0);
-  if (!skip && advance) step[0] = t;
-  const double tt = (double)(t > 0 ? t : 1);
-  const double bc1 = 1.0 - pow(beta1, tt), bc2 = 1.0 - pow(beta2, tt);
-  AmpCoef c;
-  c.decay = (float)(1.0 - lr * weight_decay), c.omb1 = (float)(1.0 - beta1), c.beta2 = (float)beta2, c.omb2 = (float)(1.0 - beta2);
-  c.eps = (float)eps, c.step_size = (float)(lr / bc1), c.bc2_sqrt = (float)sqrt(bc2);
-  c.grad_scale = (float)(grad_scale / (double)scale[0]);
-  c.skip = skip, c.pad = 0;
-  *out = c;
-}
-
-// GradScaler.update(): found -> scale *= backoff, tracker = 0; else tracker += 1 and scale *= growth every ``interval`` clean steps
-__global__ void k_amp_update(float* __restrict__ scale, int* __restrict__ tracker, const int* __restrict__ found, int nfound,
-                             float growth, float backoff, int interval) {
-  int any = 0;
-  for (int i = 0; i < nfound; i++) any |= found[i];
-  if (any) {
-    scale[0] *= backoff;
-    tracker[0] = 0;
-  } else if (++tracker[0] >= interval) {
-    scale[0] *= growth;
-    tracker[0] = 0;
-  }
-}
 }  // namespace
 
 extern "C" {
@@ -420,70 +313,6 @@ int mm_eval_confusion(const float* logits2d, int ld2, const float* logits3d, int
   if (nb > 1024) nb = 1024;
   hipLaunchKernelGGL(k_eval_confusion, dim3(nb), dim3(T), (size_t)3 * C * C * sizeof(unsigned int), s, logits2d, ld2, logits3d, ld3,
                      labels, N, C, ignore_index, (unsigned long long*)cm);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-int mm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
-                  double weight_decay, int64_t step, double grad_scale, const int* skip_dev, int nskip, hipStream_t s) {
-  MM_CHECK_ARG(step >= 1, "adamw: step counts from 1");
-  MM_CHECK_ARG(nskip >= 0 && nskip <= 16 && (nskip == 0 || skip_dev), "adamw: bad skip words");
-  if (n == 0) return MM_OK;
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;  // parameter spans may start anywhere
-  if (vec)
-    hipLaunchKernelGGL(k_adamw<true>, dim3((unsigned)mm_cdiv(n, (int64_t)T * 4)), dim3(T), 0, s, p, g, m, v, n,
-                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                       (float)(lr / bc1), (float)sqrt(bc2), (float)grad_scale, (const AmpCoef*)nullptr, skip_dev, nskip);
-  else
-    hipLaunchKernelGGL(k_adamw<false>, dim3((unsigned)mm_cdiv(n, (int64_t)T * 4)), dim3(T), 0, s, p, g, m, v, n,
-                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                       (float)(lr / bc1), (float)sqrt(bc2), (float)grad_scale, (const AmpCoef*)nullptr, skip_dev, nskip);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-// ---- loss-scaled steps (torch.cuda.amp.GradScaler semantics without a read-back; mm2d3d_amd/amp.py)
-int mm_grad_nonfinite(const float* g, int64_t n, int* found_dev, hipStream_t s) {
-  if (n == 0) return MM_OK;
-  int64_t nb = mm_cdiv(n, (int64_t)T * 4);
-  if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(k_grad_nonfinite, dim3((unsigned)nb), dim3(T), 0, s, g, n, found_dev);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-int mm_amp_coef_bytes(void) { return (int)sizeof(AmpCoef); }
-
-int mm_amp_prepare(const float* scale_dev, const int* found_dev, int nfound, int64_t* step_dev, int advance, double lr, double beta1,
-                   double beta2, double eps, double weight_decay, double grad_scale, void* coef_dev, hipStream_t s) {
-  MM_CHECK_ARG(scale_dev && found_dev && step_dev && coef_dev && nfound >= 1 && nfound <= 32, "amp_prepare: bad argument");
-  hipLaunchKernelGGL(k_amp_prepare, dim3(1), dim3(1), 0, s, scale_dev, found_dev, nfound, (long long*)step_dev, advance, lr, beta1, beta2, eps,
-                     weight_decay, grad_scale, (AmpCoef*)coef_dev);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-// mm_adamw_step with the coefficients of mm_amp_prepare (a step whose coefficients say "skip" leaves p, m, v untouched)
-int mm_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const void* coef_dev, hipStream_t s) {
-  MM_CHECK_ARG(coef_dev != nullptr, "adamw_step_dev: no coefficients");
-  if (n == 0) return MM_OK;
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL((k_adamw<true, true>), dim3((unsigned)mm_cdiv(n, (int64_t)T * 4)), dim3(T), 0, s, p, g, m, v, n, 0.f, 0.f, 0.f, 0.f,
-                       0.f, 0.f, 0.f, 0.f, (const AmpCoef*)coef_dev);
-  else
-    hipLaunchKernelGGL((k_adamw<false, true>), dim3((unsigned)mm_cdiv(n, (int64_t)T * 4)), dim3(T), 0, s, p, g, m, v, n, 0.f, 0.f, 0.f, 0.f,
-                       0.f, 0.f, 0.f, 0.f, (const AmpCoef*)coef_dev);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-int mm_amp_update(float* scale_dev, int* tracker_dev, const int* found_dev, int nfound, double growth, double backoff, int interval,
-                  hipStream_t s) {
-  MM_CHECK_ARG(scale_dev && tracker_dev && found_dev && nfound >= 0 && interval >= 1, "amp_update: bad arguments");
-  hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, s, scale_dev, tracker_dev, found_dev, nfound, (float)growth, (float)backoff, interval);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -1,8 +1,8 @@
-// Fused SGD / Adam / RMSprop updates over flat fp32 arenas (mm2d3d_amd/optimizers.py FlatSGD / FlatAdam / FlatRMSprop and
-// FlatAdamW(amsgrad=True)): the reference's optimiser registry (lib/optimizers.py: adamw, adam, sgd, rmsprop) beside the AdamW
-// kernel of loss.hip.  ONE kernel family, templated on the optimiser and its compile-time flags: a variant neither reads nor
-// writes a state array it does not use.  Arithmetic is fp32 in the op order of torch's single-tensor paths
-// (torch/optim/{sgd,adam,rmsprop}.py); g is the gradient times grad_scale.  Layout as k_adamw (loss.hip): a thread owns four
+// Fused AdamW / Adam / SGD / RMSprop updates over flat fp32 arenas (mm2d3d_amd/optimizers.py FlatAdamW / FlatAdam / FlatSGD /
+// FlatRMSprop): the reference's optimiser registry (lib/optimizers.py: adamw, adam, sgd, rmsprop; its trainer runs AdamW,
+// train.py:627-636), and the device side of the loss scale (mm2d3d_amd/amp.py).  ONE kernel family, templated on the optimiser and
+// its compile-time flags: a variant neither reads nor writes a state array it does not use.  Arithmetic is fp32 in the op order of
+// torch's single-tensor paths (torch/optim/{sgd,adam,adamw,rmsprop}.py); g is the gradient times grad_scale.  A thread owns four
 // consecutive elements, 16-byte accesses when every array of the range is 16-byte aligned (all arenas of a range share one
 // offset), else the scalar instantiation; every element is updated exactly once.
 #include "common.h"
@@ -17,8 +17,8 @@ constexpr int SGD_MOMENTUM = 1, SGD_NESTEROV = 2;
 constexpr int ADAM_AMSGRAD = 1, ADAM_DECOUPLED = 2;  // decoupled weight decay = AdamW
 constexpr int RMS_MOMENTUM = 1, RMS_CENTERED = 2;
 
-// The coefficients of one parameter group's update: passed by value (plain step) or read from the device (loss-scaled step,
-// written by k_optim_prepare).  Meaning per optimiser:
+// The coefficients of one parameter group's update: formed on the host and passed as kernel arguments (plain step) or read from
+// the device (loss-scaled step, written by k_optim_prepare).  Meaning per optimiser:
 //   SGD      lr; wd; k0 = momentum (Nesterov look-ahead); k1 = momentum of the buffer update, k2 = 1 - dampening
 //            (k1 = 0, k2 = 1 on the optimiser's first taken step: torch sets buf = g there)
 //   Adam     lr = lr / bias_correction1; wd = weight decay (L2) or 1 - lr * wd (decoupled); k0 = 1 - beta1; k1 = beta2;
@@ -101,9 +101,16 @@ __device__ __forceinline__ void opt_update(const OptCoef& c, float gj, float& p,
 
 template <int KIND, int FLAGS, bool VEC, bool DEV>
 __global__ __launch_bounds__(T) void k_optim(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
-                                              float* __restrict__ s1, float* __restrict__ s2, int64_t n, OptCoef c,
+                                              float* __restrict__ s1, float* __restrict__ s2, int64_t n, float gs, float wd,
+                                              float lr, float k0, float k1, float k2, float k3, float eps,
                                               const OptCoef* __restrict__ dc, const int* __restrict__ skip, int nskip) {
   typedef Uses<KIND, FLAGS> U;
+  // The plain step's coefficients arrive as eight scalars, not as an OptCoef by value: with a struct the compiler pairs the
+  // multiplies and adds of the scalar path differently (which product joins which fused multiply-add), and AdamW's weights would
+  // leave the bits of tests/golden/adamw_bits.npz by an ulp or two on ranges that start unaligned and in ragged tails.  This
+  // rests on the compiler's contraction heuristics, not on the language: a new compiler may pair them differently again, and the
+  // golden test will say so.  (The DEV instantiations take the eight arguments too and ignore them: one signature for all.)
+  OptCoef c = {gs, wd, lr, k0, k1, k2, k3, eps, 0, 0};
   // skip words (the data-parallel reducer's collective flags): decided on the device, uniform
   for (int i = 0; i < nskip; i++)
     if (skip[i]) return;
@@ -144,8 +151,11 @@ __global__ __launch_bounds__(T) void k_optim(float* __restrict__ p, const float*
   }
 }
 
-// one thread: the coefficients of one parameter group from the device state, as k_amp_prepare (loss.hip) does for AdamW.
-// t = *step + 1 is the step this update would be; it is committed only when the step is taken and ``advance`` is set.
+// one thread: the coefficients of one parameter group from the device state, so that a skipped step (torch.cuda.amp.GradScaler
+// semantics) needs no read-back.  ONE decision for every optimiser of the step (the reference's HybridOptim is one optimiser to
+// Lightning's GradScaler, train.py:627-636: a non-finite gradient in either network skips both updates) and for the caller's
+// extra skip words.  t = *step + 1 is the step this update would be; it is committed to *step only when the step is taken and
+// ``advance`` is set (first group of an optimiser).
 __global__ void k_optim_prepare(int kind, int decoupled, const float* __restrict__ scale, const int* __restrict__ found, int nfound,
                                 long long* __restrict__ step, int advance, OptHyper h, double grad_scale, OptCoef* __restrict__ out) {
   int skip = 0;
@@ -155,6 +165,37 @@ __global__ void k_optim_prepare(int kind, int decoupled, const float* __restrict
   OptCoef c = make_coef(kind, decoupled, h, t, grad_scale / (double)scale[0]);
   c.skip = skip;
   *out = c;
+}
+
+// found[0] |= any element of g is inf / nan (benign race: every writer stores 1)
+__global__ __launch_bounds__(T) void k_grad_nonfinite(const float* __restrict__ g, int64_t n, int* __restrict__ found) {
+  const int64_t stride = (int64_t)gridDim.x * T * 4;
+  bool bad = false;
+  for (int64_t i = ((int64_t)blockIdx.x * T + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n && (((uintptr_t)(g + i)) & 15) == 0) {
+      typedef float f4 __attribute__((ext_vector_type(4)));
+      const f4 G = *(const f4*)(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; j++) bad |= !(fabsf(G[j]) <= 3.402823466e38f);
+    } else {
+      for (int j = 0; j < 4 && i + j < n; j++) bad |= !(fabsf(g[i + j]) <= 3.402823466e38f);
+    }
+  }
+  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) found[0] = 1;
+}
+
+// GradScaler.update(): found -> scale *= backoff, tracker = 0; else tracker += 1 and scale *= growth every ``interval`` clean steps
+__global__ void k_amp_update(float* __restrict__ scale, int* __restrict__ tracker, const int* __restrict__ found, int nfound,
+                             float growth, float backoff, int interval) {
+  int any = 0;
+  for (int i = 0; i < nfound; i++) any |= found[i];
+  if (any) {
+    scale[0] *= backoff;
+    tracker[0] = 0;
+  } else if (++tracker[0] >= interval) {
+    scale[0] *= growth;
+    tracker[0] = 0;
+  }
 }
 
 template <int KIND, int FLAGS>
@@ -170,17 +211,9 @@ int launch(float* p, const float* g, float* s0, float* s1, float* s2, int64_t n,
   if (U::s1) a |= (uintptr_t)s1;
   if (U::s2) a |= (uintptr_t)s2;
   const dim3 grid((unsigned)mm_cdiv(n, (int64_t)T * 4));
-  if ((a & 15) == 0) {
-    if (dc)
-      hipLaunchKernelGGL((k_optim<KIND, FLAGS, true, true>), grid, dim3(T), 0, s, p, g, s0, s1, s2, n, c, dc, skip, nskip);
-    else
-      hipLaunchKernelGGL((k_optim<KIND, FLAGS, true, false>), grid, dim3(T), 0, s, p, g, s0, s1, s2, n, c, dc, skip, nskip);
-  } else {
-    if (dc)
-      hipLaunchKernelGGL((k_optim<KIND, FLAGS, false, true>), grid, dim3(T), 0, s, p, g, s0, s1, s2, n, c, dc, skip, nskip);
-    else
-      hipLaunchKernelGGL((k_optim<KIND, FLAGS, false, false>), grid, dim3(T), 0, s, p, g, s0, s1, s2, n, c, dc, skip, nskip);
-  }
+  const auto kernel = (a & 15) == 0 ? (dc ? k_optim<KIND, FLAGS, true, true> : k_optim<KIND, FLAGS, true, false>)
+                                    : (dc ? k_optim<KIND, FLAGS, false, true> : k_optim<KIND, FLAGS, false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(T), 0, s, p, g, s0, s1, s2, n, c.gs, c.wd, c.lr, c.k0, c.k1, c.k2, c.k3, c.eps, dc, skip, nskip);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -282,6 +315,24 @@ int mm_rmsprop_step_dev(float* p, const float* g, float* sq, float* gavg, float*
                         hipStream_t s) {
   MM_CHECK_ARG(coef_dev != nullptr, "rmsprop_step_dev: no coefficients");
   return dispatch<RMSPROP>(rms_flags(gavg, buf), p, g, sq, gavg, buf, n, OptCoef{}, coef_dev, nullptr, 0, s);
+}
+
+// ---- the loss scale (torch.cuda.amp.GradScaler semantics without a read-back; mm2d3d_amd/amp.py)
+int mm_grad_nonfinite(const float* g, int64_t n, int* found_dev, hipStream_t s) {
+  if (n == 0) return MM_OK;
+  int64_t nb = mm_cdiv(n, (int64_t)T * 4);
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(k_grad_nonfinite, dim3((unsigned)nb), dim3(T), 0, s, g, n, found_dev);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_amp_update(float* scale_dev, int* tracker_dev, const int* found_dev, int nfound, double growth, double backoff, int interval,
+                  hipStream_t s) {
+  MM_CHECK_ARG(scale_dev && tracker_dev && found_dev && nfound >= 0 && interval >= 1, "amp_update: bad arguments");
+  hipLaunchKernelGGL(k_amp_update, dim3(1), dim3(1), 0, s, scale_dev, tracker_dev, found_dev, nfound, (float)growth, (float)backoff, interval);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 The four names of the reference's registry build flat optimisers: ``adamw`` -> :class:`FlatAdamW`, ``adam`` -> :class:`FlatAdam`
 (weight decay as L2, torch.optim.Adam), ``sgd`` -> :class:`FlatSGD`, ``rmsprop`` -> :class:`FlatRMSprop`.  Parameters, gradients
 and the optimiser's state live in flat fp32 arenas (one allocation each), so the update is ONE fused HIP kernel per step
-(csrc/loss.hip k_adamw for AdamW, csrc/optim.hip k_optim for the others and for ``amsgrad``) instead of torch's per-tensor loop
+(csrc/optim.hip k_optim, one kernel family for all four) instead of torch's per-tensor loop
 (SURVEY.md K16), the data-parallel all-reduce runs on slices of the same gradient arena without packing copies
 (mm2d3d_amd/ddp.py), backward kernels may accumulate straight into it (mm2d3d_amd/gradsink.py) and the loss scale of the fp16
 mode can skip a step on the device (mm2d3d_amd/amp.py).  ``param_groups`` / ``defaults`` carry the keys of torch's classes, and
@@ -258,9 +258,11 @@ def _range(a, names, lo, hi):
 class FlatAdamW(_FlatOptimizer):
     """AdamW (decoupled weight decay, torch.optim.AdamW semantics) over flat arenas: state ``m``, ``v`` and, with ``amsgrad``,
     ``vmax``.  The bias corrections are keyed to the optimiser's step counter, not to a parameter's own: a parameter that first
-    receives a gradient on a later step differs from torch there.  Without ``amsgrad`` the update is k_adamw of csrc/loss.hip
-    (and ``step(skip_words=)`` keeps the counter on the host, which advances also when the device skipped the update: the
-    trainer raises one step later, train.py); with it, the Adam kernel of csrc/optim.hip with decoupled decay."""
+    receives a gradient on a later step differs from torch there.  The update is the Adam kernel of csrc/optim.hip with decoupled
+    decay.  Without ``amsgrad``, ``step(skip_words=)`` is a plain launch that keeps the counter on the host, which advances also
+    when the device skipped the update (the trainer raises one step later, train.py); with it - and for :class:`FlatAdam` always -
+    the counter is on the device.  No kernel asks for that split any more: it is kept because the device-counted form would add
+    a ``k_optim_prepare`` launch per group to the data-parallel bf16 step and move its counter."""
 
     _decoupled = 1
 
@@ -271,20 +273,13 @@ class FlatAdamW(_FlatOptimizer):
                                       foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused,
                                       decoupled_weight_decay=bool(self._decoupled)))
 
-    def _adamw_kernel(self, group):
-        """The group runs on csrc/loss.hip's AdamW kernels (unchanged), not on csrc/optim.hip's Adam family."""
-        return bool(self._decoupled) and not group.get("amsgrad")
-
     def _state_names(self, group):
         return ("m", "v", "vmax") if group.get("amsgrad") else ("m", "v")
 
     @property
     def _skips_on_device(self):
-        return not all(self._adamw_kernel(g) for g in self.param_groups)
-
-    def _coef_bytes(self):
-        L = _lib.lib()
-        return max(int(L.mm_amp_coef_bytes()), int(L.mm_optim_coef_bytes()))
+        # FlatAdam (not decoupled) has always counted on the device; FlatAdamW does only for amsgrad (class docstring)
+        return not self._decoupled or any(g.get("amsgrad") for g in self.param_groups)
 
     @staticmethod
     def _hp(group):
@@ -297,27 +292,16 @@ class FlatAdamW(_FlatOptimizer):
 
     def _plain(self, L, group, a, lo, hi, grad_scale, skip_words):
         nskip = 0 if skip_words is None else int(skip_words.numel())
-        if self._adamw_kernel(group):
-            check(L.mm_adamw_step(*_range(a, ("p", "g", "m", "v"), lo, hi), hi - lo, *self._hp(group), self._step, grad_scale,
-                                  ptr(skip_words), nskip, stream()), "adamw_step")
-        else:
-            check(L.mm_adam_step(*_range(a, self._arrays(group), lo, hi), hi - lo, *self._hp(group), self._decoupled, self._step,
-                                 grad_scale, ptr(skip_words), nskip, stream()), "adam_step")
+        check(L.mm_adam_step(*_range(a, self._arrays(group), lo, hi), hi - lo, *self._hp(group), self._decoupled, self._step,
+                             grad_scale, ptr(skip_words), nskip, stream()), "adam_step")
 
     def _prepare(self, L, group, scale_dev, found_dev, step_dev, advance, grad_scale, coef):
-        if self._adamw_kernel(group):
-            check(L.mm_amp_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
-                                   grad_scale, ptr(coef), stream()), "amp_prepare")
-        else:
-            check(L.mm_adam_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
-                                    self._decoupled, grad_scale, ptr(coef), stream()), "adam_prepare")
+        check(L.mm_adam_prepare(ptr(scale_dev), ptr(found_dev), int(found_dev.numel()), ptr(step_dev), advance, *self._hp(group),
+                                self._decoupled, grad_scale, ptr(coef), stream()), "adam_prepare")
 
     def _scaled(self, L, group, a, lo, hi, coef):
-        if self._adamw_kernel(group):
-            check(L.mm_adamw_step_dev(*_range(a, ("p", "g", "m", "v"), lo, hi), hi - lo, ptr(coef), stream()), "adamw_step_dev")
-        else:
-            check(L.mm_adam_step_dev(*_range(a, self._arrays(group), lo, hi), hi - lo, self._decoupled, ptr(coef), stream()),
-                  "adam_step_dev")
+        check(L.mm_adam_step_dev(*_range(a, self._arrays(group), lo, hi), hi - lo, self._decoupled, ptr(coef), stream()),
+              "adam_step_dev")
 
 
 class FlatAdam(FlatAdamW):

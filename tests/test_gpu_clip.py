@@ -270,8 +270,8 @@ def test_four_clipped_steps_match_torch(case, scaled, algo):
 
 
 def test_clipped_adamw_takes_the_device_coefficient_form_and_matches_torch():
-    """FlatAdamW without amsgrad (k_adamw of csrc/loss.hip) keeps its counter on the host in plain steps; a clipped step runs as
-    mm_amp_prepare + mm_adamw_step_dev with the optimiser's own device counter."""
+    """FlatAdamW without amsgrad keeps its counter on the host in plain steps; a clipped step runs as mm_adam_prepare +
+    mm_adam_step_dev (decoupled decay) with the optimiser's own device counter."""
     from mm2d3d_amd.clip import clip_grad_norm_
 
     dev = _dev()

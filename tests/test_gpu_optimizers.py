@@ -1,7 +1,9 @@
-"""GPU parity of the flat SGD / Adam / RMSprop / AdamW(amsgrad) updates (csrc/optim.hip) with the reference's own registry entries:
+"""GPU parity of the flat SGD / Adam / RMSprop / AdamW updates (csrc/optim.hip) with the reference's own registry entries:
 ``torch.optim.<Class>`` in fp32 on the CPU.  Envelope: the project's own for AdamW, atol 2e-6 + rtol 1e-6 (torch's fp32
 optimisers drift from its fp64 ones by < 8e-7 on these inputs over 12 steps, so the reference alone sits well inside it)."""
 import copy
+import importlib.util
+import os
 
 import numpy as np
 import pytest
@@ -26,6 +28,9 @@ CASES = [
     ("rmsprop_centered", "FlatRMSprop", "RMSprop", dict(momentum=0.9, weight_decay=0.05, centered=True)),
 ]
 IDS = [c[0] for c in CASES]
+# AdamW without amsgrad keeps the host counter under step(skip_words=): it joins every test but the one on that counter
+ADAMW = ("adamw", "FlatAdamW", "AdamW", dict(lr=0.01, weight_decay=0.05))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _dev():
@@ -73,7 +78,7 @@ def _assert_frozen(o, snap, what):
 
 
 @pytest.mark.parametrize("scaled", [False, True], ids=["plain", "loss_scaled"])
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + [ADAMW], ids=IDS + [ADAMW[0]])
 def test_four_steps_match_torch_on_a_touched_range_that_starts_unaligned(case, scaled):
     """An untouched 6-element parameter ahead of the touched ones: the touched range starts at arena offset 6 (not 16-byte
     aligned), so the scalar instantiations of k_optim run; every element is updated exactly once per step."""
@@ -103,7 +108,7 @@ def test_aligned_ranges_and_ragged_tails_take_the_vector_path_and_match_torch():
     """All parameters touched: the range starts at the 16-byte aligned arena base (vector instantiation), 6149 elements = 6 full
     blocks of 1024 + a block whose second thread owns a single element (scalar tail)."""
     dev = _dev()
-    for _, flat, ref, kw in (CASES[3], CASES[5], CASES[9]):
+    for _, flat, ref, kw in (CASES[3], CASES[5], CASES[9], ADAMW):
         from mm2d3d_amd import optimizers
 
         g = torch.Generator().manual_seed(11)
@@ -150,7 +155,8 @@ def test_a_set_skip_word_freezes_everything_and_does_not_use_up_the_first_step(c
 
 
 def test_skip_words_of_the_plain_entry_points():
-    """skip_dev / nskip of mm_sgd_step / mm_adam_step / mm_rmsprop_step themselves: any nonzero word makes the launch a no-op."""
+    """skip_dev / nskip of mm_sgd_step / mm_adam_step (also as AdamW: decoupled = 1, vmax = NULL) / mm_rmsprop_step themselves: any
+    nonzero word makes the launch a no-op."""
     from mm2d3d_amd import _lib
     from mm2d3d_amd._lib import check, ptr, stream
 
@@ -166,8 +172,64 @@ def test_skip_words_of_the_plain_entry_points():
         check(L.mm_sgd_step(ptr(p), ptr(g), ptr(s0), n, 0.1, 0.9, 0.0, 0.0, 0, 2, 1.0, ptr(w), 3, stream()), "sgd")
         check(L.mm_adam_step(ptr(p), ptr(g), ptr(s0), ptr(s1), ptr(s2), n, 0.1, 0.9, 0.999, 1e-8, 0.0, 0, 1, 1.0, ptr(w), 3, stream()), "adam")
         check(L.mm_rmsprop_step(ptr(p), ptr(g), ptr(s0), ptr(s1), ptr(s2), n, 0.1, 0.99, 1e-8, 0.0, 0.9, 1.0, ptr(w), 3, stream()), "rms")
+        check(L.mm_adam_step(ptr(p), ptr(g), ptr(s0), ptr(s1), None, n, 0.1, 0.9, 0.999, 1e-8, 0.01, 1, 1, 1.0, ptr(w), 3, stream()), "adamw")
         same = [torch.equal(a, b) for a, b in zip(before, (p, s0, s1, s2))]
         assert same == [any(words)] * 4, (words, same)
+
+
+def test_adamw_without_amsgrad_keeps_the_host_counter_under_skip_words():
+    """FlatAdamW without amsgrad takes step(skip_words=) as a plain launch: the device skips the update, the HOST counter
+    advances all the same, and no device state of the device-counted form is created."""
+    _, flat, ref, kw = ADAMW
+    dev = _dev()
+    g, init, hp, rp, o, r = _pair(flat, ref, kw, dev)
+    assert not o._skips_on_device
+    word = torch.tensor([0, 1], dtype=torch.int32, device=dev)
+    _backward(g, hp, rp, o, r, dev)
+    snap = _snapshot(o)
+    o.step(skip_words=word)
+    _assert_frozen(o, snap, "first step skipped")
+    word.zero_()
+    o.step(skip_words=word)
+    assert not torch.equal(o._arenas[0]["p"], snap["p"])  # the second step is taken
+    assert o.state_dict()["step"] == 2
+    assert o._own is None
+
+
+def _adamw_bits_module():
+    spec = importlib.util.spec_from_file_location("make_golden_adamw_bits", os.path.join(GOLDEN, "make_golden_adamw_bits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_adamw_without_amsgrad_is_bit_identical_with_the_retired_kernel():
+    """tests/golden/adamw_bits.npz pins the bits of the AdamW update (no amsgrad): p, m, v after steps 1 and 4, recorded on an
+    MI355X by tests/golden/make_golden_adamw_bits.py at commit 93edc00, where a kernel of its own in csrc/loss.hip did this update.
+    Four runs: plain and loss-scaled, on the whole arena (aligned base, a block of 1024 + a block whose sixth thread owns 3
+    elements) and on the range from offset 6 (unaligned: scalar instantiation, 1041 elements, a one-element tail).
+    k_optim<ADAM, ADAM_DECOUPLED> must give the same bits.  Measured with the coefficients passed as an OptCoef by value: steps 1
+    and every loss-scaled run identical; plain runs after step 4 differ on the scalar path only (range from offset 6: 20 / 461 /
+    249 of 1047 elements of p / m / v, p by 1 - 4 ulp; whole arena: 1 / 2 elements of m / v among its last three).  k_optim
+    therefore takes the plain step's coefficients as scalar kernel arguments, which gives the old kernel's instruction sequence
+    in gfx950 assembly; that build has not yet been run against this fixture on a GPU."""
+    mod = _adamw_bits_module()
+    gold = np.load(os.path.join(GOLDEN, "adamw_bits.npz"))
+    dev = _dev()
+    seen_keys = set()
+    for key, scaled, first, ranges in mod.RUNS:
+        out, seen = mod.run(dev, scaled, first)
+        assert len(seen) == 4
+        for touched, misalign in seen:  # the case under test
+            assert touched == ranges, (key, touched)
+            assert (misalign == 0) == (first == 0), (key, misalign)
+        assert sorted(out) == sorted(f"step{k}_{n}" for k in (1, 4) for n in ("p", "m", "v")), key
+        for name, t in out.items():
+            want = torch.from_numpy(gold[f"{key}_{name}"])
+            assert want.dtype == torch.float32 and want.shape == (1047,)
+            assert torch.equal(t, want), (key, name, int((t != want).sum()))
+            seen_keys.add(f"{key}_{name}")
+    assert seen_keys == set(gold.files) and len(seen_keys) == 24
 
 
 def test_an_overflow_skips_sgd_and_adam_together_and_the_next_step_is_step_one():

@@ -104,7 +104,7 @@ def test_unused_parameters_keep_their_weights():
 @pytest.mark.parametrize("scaled", [False, True])
 def test_adamw_touched_range_that_starts_unaligned_matches_torch_adamw(scaled):
     """an untouched 6-element parameter ahead of touched ones makes the touched range start at arena offset
-    6 (not 16-byte aligned): the scalar instantiations k_adamw<false> / <false, true> run.  Every element must be updated
+    6 (not 16-byte aligned): the scalar instantiations of k_optim (csrc/optim.hip) run.  Every element must be updated
     exactly once per step, as torch.optim.AdamW does."""
     from mm2d3d_amd.amp import GradScaler
     from mm2d3d_amd.optimizers import FlatAdamW

@@ -1,4 +1,4 @@
-"""GPU time of the gradient-clipping kernels (csrc/clip.hip) against the yardstick ``mm_grad_nonfinite`` (csrc/loss.hip), which
+"""GPU time of the gradient-clipping kernels (csrc/clip.hip) against the yardstick ``mm_grad_nonfinite`` (csrc/optim.hip), which
 reads the same bytes, and of a whole clipped update against the unclipped one of the same optimiser.
 
 Sizes: the two parameter arenas of the benchmark's trainer (46,229,010 and 2,689,830 elements; tools/bench_optim.py prints them).
@@ -70,7 +70,7 @@ def main():
         k = int(L.mm_grad_sqnorm_ws_bytes(n)) // 8
         part = torch.zeros(k, dtype=torch.float64, device=dev)
         counts = np.array([k], dtype=np.int64)
-        coef = torch.zeros(max(int(L.mm_optim_coef_bytes()), int(L.mm_amp_coef_bytes())), dtype=torch.uint8, device=dev)
+        coef = torch.zeros(int(L.mm_optim_coef_bytes()), dtype=torch.uint8, device=dev)
         P, G, M, V = (t.data_ptr() for t in (p, g, m, v))
 
         yard = lambda: check(L.mm_grad_nonfinite(G, n, flags.data_ptr(), s), "nonfinite")
@@ -80,9 +80,9 @@ def main():
         val = lambda: check(L.mm_grad_clip_value(G, n, 1.0, scale.data_ptr(), 1.0, s), "clip_value")
 
         def adamw(scale_t):
-            check(L.mm_amp_prepare(scale_t.data_ptr(), flags.data_ptr(), 16, step.data_ptr(), 1, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 1.0,
-                                   coef.data_ptr(), s), "amp_prepare")
-            check(L.mm_adamw_step_dev(P, G, M, V, n, coef.data_ptr(), s), "adamw_dev")
+            check(L.mm_adam_prepare(scale_t.data_ptr(), flags.data_ptr(), 16, step.data_ptr(), 1, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 1, 1.0,
+                                    coef.data_ptr(), s), "adam_prepare")
+            check(L.mm_adam_step_dev(P, G, M, V, None, n, 1, coef.data_ptr(), s), "adamw_dev")
 
         def sgd(scale_t):
             check(L.mm_sgd_prepare(scale_t.data_ptr(), flags.data_ptr(), 16, step.data_ptr(), 1, 1e-3, 0.0, 0.0, 0.0, 1.0,

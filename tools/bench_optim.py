@@ -1,10 +1,11 @@
-"""GPU time of the flat optimiser update kernels (csrc/optim.hip) against the yardstick ``mm_adamw_step`` (csrc/loss.hip).
+"""GPU time of the flat optimiser update kernels (csrc/optim.hip) against their own ``adamw`` variant, the update of the headline step.
 
 Sizes: the two parameter arenas of the benchmark's trainer (bench.build_trainer: Net2DSeg / Net3DSeg; printed).  Per variant:
 the plain entry point on a 16-byte aligned range (vector instantiation), the loss-scaled form (``*_step_dev``: coefficients read
 from the device) and the plain form on a range that starts one element in (scalar instantiation).  HIP events around ``--launches``
 back-to-back launches, median of ``--reps`` after a warm-up; GB/s = 4 bytes x (p, g and state arrays read + p and state arrays
-written) per element over that time.  ``ratio`` = GB/s of the aligned plain form over ``mm_adamw_step``'s of the same run.  torch's own
+written) per element over that time.  ``ratio`` = GB/s of the aligned plain form over the yardstick's (``adamw``, timed beside every
+variant in the same run, alternating).  torch's own
 optimiser on one GPU tensor of the same size is timed for context.  One JSON line per measurement, then a markdown table.
 
     python tools/bench_optim.py [--reps 5] [--launches 10] [--sizes N ...] [--out table.md]
@@ -26,7 +27,7 @@ VARIANTS = [
     ("sgd nesterov", "sgd", (1, 0, 0), dict(nesterov=1), ("SGD", dict(lr=1e-3, momentum=0.9, nesterov=True))),
     ("adam", "adam", (1, 1, 0), dict(decoupled=0), ("Adam", dict(lr=1e-3))),
     ("adam amsgrad", "adam", (1, 1, 1), dict(decoupled=0), ("Adam", dict(lr=1e-3, amsgrad=True))),
-    ("adamw (k_optim)", "adam", (1, 1, 0), dict(decoupled=1), ("AdamW", dict(lr=1e-3))),
+    ("adamw", "adam", (1, 1, 0), dict(decoupled=1), ("AdamW", dict(lr=1e-3))),
     ("adamw amsgrad", "adam", (1, 1, 1), dict(decoupled=1), ("AdamW", dict(lr=1e-3, amsgrad=True))),
     ("rmsprop", "rmsprop", (1, 0, 0), {}, ("RMSprop", dict(lr=1e-3))),
     ("rmsprop momentum", "rmsprop", (1, 0, 1), {}, ("RMSprop", dict(lr=1e-3, momentum=0.9))),
@@ -95,7 +96,6 @@ def main():
     import torch
 
     from mm2d3d_amd import _lib
-    from mm2d3d_amd._lib import check
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -120,10 +120,7 @@ def main():
         bufs.update(one=torch.ones(1, device=dev), zero=torch.zeros(1, dtype=torch.int32, device=dev),
                     step=torch.full((1,), 9, dtype=torch.int64, device=dev))
         coef = torch.zeros(int(L.mm_optim_coef_bytes()), dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream().cuda_stream
-        ptr = lambda k: bufs[k].data_ptr()
-        yard = lambda: check(L.mm_adamw_step(ptr("p"), ptr("g"), ptr("s0"), ptr("s1"), n, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 10, 1.0, None, 0, s),
-                             "adamw")
+        yard, _ = _launchers(L, "adam", (1, 1, 0), dict(decoupled=1), bufs, n, 0, coef)
         yard_ms = []
         for name, fam, use, kw, (tcls, tkw) in VARIANTS:
             yard_ms.append(_events_ms(yard, args.reps, args.launches))  # the yardstick beside every variant: same run, alternating
@@ -144,14 +141,14 @@ def main():
             print(json.dumps(rows[-1]), flush=True)
         y = float(np.median(yard_ms))
         ygb = 28 * n / y / 1e6
-        print(json.dumps(dict(what="yardstick", n=n, variant="mm_adamw_step", bytes_per_elem=28, ms=round(y, 4), gb_per_s=round(ygb, 1),
+        print(json.dumps(dict(what="yardstick", n=n, variant="adamw", bytes_per_elem=28, ms=round(y, 4), gb_per_s=round(ygb, 1),
                               ms_min=round(min(yard_ms), 4), ms_max=round(max(yard_ms), 4))), flush=True)
         for r in rows:
             if r["n"] == n:
                 r["ratio"] = round(r["gb_per_s"] / ygb, 3)
-        rows.append(dict(n=n, variant="mm_adamw_step (yardstick)", bytes_per_elem=28, ms=round(y, 4), gb_per_s=round(ygb, 1), ratio=1.0))
+        rows.append(dict(n=n, variant="adamw (yardstick)", bytes_per_elem=28, ms=round(y, 4), gb_per_s=round(ygb, 1), ratio=1.0))
         del bufs
-    lines = ["| elements | variant | B/elem | ms | GB/s | ratio to mm_adamw_step | *_step_dev ms | unaligned ms | torch.optim ms |",
+    lines = ["| elements | variant | B/elem | ms | GB/s | ratio to adamw | *_step_dev ms | unaligned ms | torch.optim ms |",
              "|---:|---|---:|---:|---:|---:|---:|---:|---:|"]
     for r in rows:
         lines.append(f"| {r['n']} | {r['variant']} | {r['bytes_per_elem']} | {r['ms']:.4f} | {r['gb_per_s']:.0f} | {r['ratio']:.2f} | "

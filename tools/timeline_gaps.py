@@ -10,10 +10,11 @@ with open(path) as f:
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", "")))
 rows.sort()
 short = lambda n: re.sub(r"\(anonymous namespace\)::", "", n).split("(")[0][:60]
-# step boundaries: the optimiser kernel k_adamw runs twice per step (two optimisers), the last launches of a step
-ends = [e for s, e, n, q in rows if "k_adamw" in n]
+# step boundaries: the optimiser kernel (k_optim; k_adamw in traces of older trees) runs twice per step (two optimisers), the last
+# launches of a step
+ends = [e for s, e, n, q in rows if re.search(r"k_adamw|k_optim<", n)]
 if len(ends) < 2 * steps + 2:
-    print("not enough k_adamw launches", len(ends)); sys.exit(1)
+    print("not enough optimiser launches", len(ends)); sys.exit(1)
 t1 = ends[-1]
 t0 = ends[-1 - 2 * steps]
 sel = [(s, e, n, q) for s, e, n, q in rows if s >= t0 and e <= t1]
