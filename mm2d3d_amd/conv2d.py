@@ -7,7 +7,7 @@ by one batched launch (``_PackRegistry``).  A map may be a channel slice of a wi
 from __future__ import annotations
 
 import ctypes as C
-
+import os
 import weakref
 
 import torch
@@ -16,6 +16,34 @@ from . import _lib, domains, gradsink
 from ._lib import check, ptr, stream
 
 CL = torch.channels_last
+
+# The A/B switches of this module, each read from the environment once, here.
+# mm_conv2d_3x3s1's flip argument, bit 1: whole work items only (A/B of the half-item last round; MM_CONV_WHOLE_ITEMS=1)
+WHOLE_ITEMS = [2 if os.environ.get("MM_CONV_WHOLE_ITEMS", "0") != "0" else 0]
+# ... bits 2-3: which 3x3 stride-1 kernel (A/B and tests; MM_CONV3X3_LEGACY = 1 / 2): 0 = k_conv3x3s (round 6, 16x16x32 MFMAs: the default),
+# 4 = the round-2 kernel k_conv3x3w, 8 = k_conv3x3v (round 6 on 32x32x16 MFMAs: bit-identical with k_conv3x3w)
+LEGACY3X3 = [{"1": 4, "2": 8, "3": 12}.get(os.environ.get("MM_CONV3X3_LEGACY", "0"), 0)]
+# BatchNorm statistics in the convolution epilogue (csrc/conv2d.hip stats_accum): a training-mode BatchNorm2d behind the layer then
+# takes its batch statistics from the slab instead of reading the map (nn2d._BN2dFn, mm_bn2d_fwd_train_pre).
+# MM_BN2D_PRE = auto (default): only for maps too large for the single-launch batch norm, which reads a map once anyway (same-box
+# A/B on the headline step, round 4: every layer 40.1-40.4 ms, none 39.3-39.9 - two extra launches per layer cost more than
+# the barriers they replace); 1: every layer; 0: never.
+BN_PRE = [{"0": False, "1": True}.get(os.environ.get("MM_BN2D_PRE", "auto"), "auto")]
+# The weight gradient of a layer = a "partial slabs" kernel + a small slab-sum kernel (csrc/conv2d.hip).  With a gradient sink
+# (FlatAdamW's arena) the slab sums of ALL layers of a backward pass are deferred into ONE launch (mm_conv2d_wgrad_reduce_batch,
+# issued from an end-of-backward callback of the autograd engine): ~50 launches of ~14 us per step, each behind a dependent-launch
+# gap, become one; every layer keeps its slabs (<= 40 MB) in a buffer of its own until then - ~1.4 GB per step of 288 GB.  Same
+# slabs, same summation order: bit-identical.  MM_CONV_WGRAD_BATCH=0: the per-layer form (also what the data-parallel reducer
+# selects when its buckets go out DURING backward, ddp.GradAllReducer(overlap=True): a deferred sum would hold every bucket back).
+WGRAD_BATCH = [os.environ.get("MM_CONV_WGRAD_BATCH", "1") != "0"]
+# ... also inside a captured backward pass (MM_CONV_WGRAD_BATCH_GRAPH=0: per-layer sums there, as in round 5)
+WGRAD_BATCH_GRAPH = [os.environ.get("MM_CONV_WGRAD_BATCH_GRAPH", "1") != "0"]
+STEM7 = [os.environ.get("MM_CONV_STEM7", "1") != "0"]  # the 7x7 stems on their own kernel (A/B switch: 0 = generic implicit GEMM)
+DGRAD_S2 = [os.environ.get("MM_CONV_DGRAD_S2", "1") != "0"]  # stride-2 data gradients by output parity (A/B switch)
+# Two 3x3 convolutions of one shape in ONE launch (mm_conv2d_3x3s1_pair): the same layer of the RGB and of the depth backbone.
+# MM_CONV_PAIR=0: two launches (A/B).
+PAIR = [os.environ.get("MM_CONV_PAIR", "1") != "0"]
+PAIR_WGRAD = [os.environ.get("MM_CONV_PAIR_WGRAD", "1") != "0"]  # the pairs' weight gradients in one launch too
 
 # Storage format of the 2D maps and of the packed weights: IEEE float16 (default: the reference's ``precision: 16`` is fp16
 # autocast + GradScaler, config/run/train.yaml:11) or bfloat16.  The kernels exist in both builds (csrc/h16.h: entry points
@@ -73,13 +101,6 @@ def as_nhwc_bf16(x):
     return x
 
 
-import os as _os
-
-# mm_conv2d_3x3s1's flip argument, bit 1: whole work items only (A/B of the half-item last round; MM_CONV_WHOLE_ITEMS=1)
-WHOLE_ITEMS = [2 if _os.environ.get("MM_CONV_WHOLE_ITEMS", "0") != "0" else 0]
-# ... bits 2-3: which 3x3 stride-1 kernel (A/B and tests; MM_CONV3X3_LEGACY = 1 / 2): 0 = k_conv3x3s (round 6, 16x16x32 MFMAs: the default),
-# 4 = the round-2 kernel k_conv3x3w, 8 = k_conv3x3v (round 6 on 32x32x16 MFMAs: bit-identical with k_conv3x3w)
-LEGACY3X3 = [{"1": 4, "2": 8, "3": 12}.get(_os.environ.get("MM_CONV3X3_LEGACY", "0"), 0)]
 PARAM_EPOCH = [0]  # bumped by FlatAdamW.step(): packed bf16 copies of the fp32 master weights are valid for one epoch
 
 
@@ -201,14 +222,6 @@ def _bias_grad(dy, into=None):
     return out
 
 
-# BatchNorm statistics in the convolution epilogue (csrc/conv2d.hip stats_accum): a training-mode BatchNorm2d behind the layer then
-# takes its batch statistics from the slab instead of reading the map (nn2d._BN2dFn, mm_bn2d_fwd_train_pre).
-# MM_BN2D_PRE = auto (default): only for maps too large for the single-launch batch norm, which reads a map once anyway (same-box
-# A/B on the headline step, round 4: every layer 40.1-40.4 ms, none 39.3-39.9 - two extra launches per layer cost more than
-# the barriers they replace); 1: every layer; 0: never.
-BN_PRE = [{"0": False, "1": True}.get(_os.environ.get("MM_BN2D_PRE", "auto"), "auto")]
-
-
 def bn_pre_wanted(x_device, Bn, Ho, Wo, Cn):
     """Should a convolution producing a [Bn, Cn, Ho, Wo] map for a training-mode BatchNorm2d file the statistics?"""
     mode = BN_PRE[0]
@@ -220,45 +233,34 @@ def bn_pre_wanted(x_device, Bn, Ho, Wo, Cn):
     return not lib2d().mm_bn2d_single_launch(_lib.handle(x_device).h, N, Ns, Cn, 0)
 
 
-def _stat_group_split(Bn):
-    """Number of leading batch entries in statistics group 0 (domains.split), Bn = a single group."""
+def _stat_slab(holder, device, dims, rows):
+    """(slab, n_first) for a convolution that produces a [Bn, Cn, Ho, Wo] map, ``dims`` = (Bn, Ho, Wo, Cn): the slab its epilogue
+    files the BatchNorm statistics in, or None when nobody asked (``holder`` None) or they are not wanted (bn_pre_wanted), and the
+    number of leading batch entries in statistics group 0 (domains.split; Bn = a single group).  ``holder``: a one-element list that
+    receives (slab, rows, n_first, Bn); ``rows``: the slab's row count, or a callable giving it (called only when a slab is made)."""
+    Bn, Ho, Wo, Cn = dims
+    if holder is None or not bn_pre_wanted(device, Bn, Ho, Wo, Cn):
+        return None, Bn
     nf = domains.current()
-    return nf if (nf is not None and 0 < nf < Bn) else Bn
-
-
-def _stat_slab(holder, rows, Cn, nf, Bn, device):
+    nf = nf if (nf is not None and 0 < nf < Bn) else Bn
+    rows = int(rows() if callable(rows) else rows)
     slab = torch.empty((rows, 2, Cn), dtype=torch.float32, device=device)
     holder[0] = (slab, rows, nf, Bn)
-    return slab
+    return slab, nf
 
 
 def _gemm(A, Bn, Hi, Wi, Ca, out, Ho, Wo, Cn, Hg, Wg, so, sa, fr, ty, tx, Wp, nz=1, wz=0, zpar=0, bias=None, lda=None, stats=None,
           addend=None, ld_add=0):
     """``stats``: a one-element list that receives (slab, rows, n_first, B) - the output's BatchNorm statistics slab.
     ``addend``: a 16-bit map of the output's shape (pixel pitch ``ld_add``) added to the result in the epilogue."""
-    slab, split_m = None, 0
-    if stats is not None and bn_pre_wanted(out.device, Bn, Ho, Wo, Cn):
-        nf = _stat_group_split(Bn)
-        slab = _stat_slab(stats, int(lib2d().mm_conv2d_gemm_stat_rows(Bn * Hg * Wg, nz)), Cn, nf, Bn, out.device)
-        split_m = nf * Hg * Wg
+    slab, nf = _stat_slab(stats, out.device, (Bn, Ho, Wo, Cn), lambda: lib2d().mm_conv2d_gemm_stat_rows(Bn * Hg * Wg, nz))
+    split_m = nf * Hg * Wg if slab is not None else 0
     check(
         lib2d().mm_conv2d_gemm(ptr(A), Bn, Hi, Wi, Ca, lda or Ca, ptr(out), Ho, Wo, Cn, Cn, 1 if out.dtype == torch.float32 else 0,
                                   Hg, Wg, so, 0, 0, sa, fr, len(ty), _arr(ty), _arr(tx), ptr(Wp), nz, wz, zpar, ptr(bias), ptr(slab), split_m,
                                   ptr(addend), ld_add, stream()),
         "conv2d_gemm",
     )
-
-
-# The weight gradient of a layer = a "partial slabs" kernel + a small slab-sum kernel (csrc/conv2d.hip).  With a gradient sink
-# (FlatAdamW's arena) the slab sums of ALL layers of a backward pass are deferred into ONE launch (mm_conv2d_wgrad_reduce_batch,
-# issued from an end-of-backward callback of the autograd engine): ~50 launches of ~14 us per step, each behind a dependent-launch
-# gap, become one; every layer keeps its slabs (<= 40 MB) in a buffer of its own until then - ~1.4 GB per step of 288 GB.  Same
-# slabs, same summation order: bit-identical.  MM_CONV_WGRAD_BATCH=0: the per-layer form (also what the data-parallel reducer
-# selects when its buckets go out DURING backward, ddp.GradAllReducer(overlap=True): a deferred sum would hold every bucket back).
-WGRAD_BATCH = [True]  # (set from the environment below, next to the other A/B switches)
-
-
-WGRAD_BATCH_GRAPH = [True]  # ... also inside a captured backward pass (MM_CONV_WGRAD_BATCH_GRAPH=0: per-layer sums there, as in round 5)
 
 
 def _defer_wgrad():
@@ -268,49 +270,23 @@ def _defer_wgrad():
     return WGRAD_BATCH[0] and (WGRAD_BATCH_GRAPH[0] or not torch.cuda.is_current_stream_capturing())
 
 
-class _WgBatch:
+class _WgBatch(gradsink.DeferredSums):
+    """Items: (slabs, dW, dW1, sn, st, sk, nsplit, Cn, ntaps, Ck, params); dW1: the second destination of a paired launch, else None."""
+
     def __init__(self):
-        self.items = []  # (slabs, dW, dW1, sn, st, sk, nsplit, Cn, ntaps, Ck, params)
-        self.cb_queued = False
+        super().__init__()
         self.captured = []  # (device table, host table) of launches recorded into a HIP graph, not yet filled in
         self.cap_buf, self.cap_used = None, 0  # device memory for those tables, allocated OUTSIDE the graph's pool (begin_capture)
 
-    def add(self, item):
-        self.items.append(item)
-        if not self.cb_queued:
-            self.cb_queued = True
-            torch.autograd.Variable._execution_engine.queue_callback(self.flush)
+    def _dests(self, it):
+        return (it[1].data_ptr(),) if it[2] is None else (it[1].data_ptr(), it[2].data_ptr())
+
+    def _params(self, it):
+        return it[10]
 
     def reset(self):
-        """Forget slabs whose backward pass never reached its end (an exception in between): called by FlatAdamW.zero_grad.  The
-        autograd engine skips the final callbacks of a graph task that raised, so ``flush`` never ran and never cleared ``cb_queued``:
-        left set, no later backward pass would queue it again (the deferred sums would never launch, the conv weight
-        gradients stay zero and their hooks never fire)."""
-        self.items = []
-        self.cb_queued = False
+        super().reset()
         self.captured, self.cap_buf, self.cap_used = [], None, 0
-
-    def flush(self):
-        self.cb_queued = False
-        items, self.items = self.items, []
-        if not items:
-            return
-        # A weight that took part in the forward pass twice (the literal two-call sequence of the two domains, train.py:186-292)
-        # has two slab sets that ADD into one gradient: they must not share a launch (two blocks would read-modify-write the same
-        # words) - a new launch starts whenever a destination repeats.  The joint-domain step uses every weight once: one launch.
-        groups, seen = [[]], set()
-        for it in items:
-            dst = {it[1].data_ptr()} | ({it[2].data_ptr()} if it[2] is not None else set())
-            if dst & seen:
-                groups.append([])
-                seen = set()
-            seen |= dst
-            groups[-1].append(it)
-        for g in groups:
-            self._launch(g)
-        for it in items:
-            for prm in it[10]:
-                gradsink.done(prm)
 
     def begin_capture(self, device, nbytes=1 << 16):
         """Before a backward pass is captured: memory for the descriptor tables of its batch launches.  NOT from the graph's pool
@@ -354,7 +330,6 @@ class _WgBatch:
 
 
 _WGB = _WgBatch()
-gradsink.RESETTERS.append(_WGB.reset)
 
 
 def _wgrad_deferred(X, Bn, Hi, Wi, Ck, dY, Hg, Wg, Cn, sa, ty, tx, param, sn, st, sk, ldx=None, ldy=None):
@@ -377,6 +352,30 @@ def _wgrad(X, Bn, Hi, Wi, Ck, dY, Hg, Wg, Cn, sa, ty, tx, dW, sn, st, sk, accumu
                           ptr(ws), ws.numel(), stream()),
         "conv2d_wgrad",
     )
+
+
+def _deliver_wgrad(param, X, Bn, Hi, Wi, Ck, dY, Hg, Wg, Cn, sa, ty, tx, sn, st, sk, like, ldx=None, ldy=None):
+    """The weight gradient of one layer on its way: with a sink (``param`` not None) deferred slabs (_WgBatch) or accumulated
+    straight into the optimiser's gradient arena - None is returned; without one a fresh tensor shaped like ``like``."""
+    if param is not None and _defer_wgrad():  # slabs now, summed into the arena with every other layer's
+        _wgrad_deferred(X, Bn, Hi, Wi, Ck, dY, Hg, Wg, Cn, sa, ty, tx, param, sn, st, sk, ldx=ldx, ldy=ldy)
+        return None
+    if param is not None:
+        _wgrad(X, Bn, Hi, Wi, Ck, dY, Hg, Wg, Cn, sa, ty, tx, param._mm_sink, sn, st, sk, accumulate=1, ldx=ldx, ldy=ldy)
+        gradsink.done(param)
+        return None
+    dw = torch.empty_like(like)
+    _wgrad(X, Bn, Hi, Wi, Ck, dY, Hg, Wg, Cn, sa, ty, tx, dw, sn, st, sk, ldx=ldx, ldy=ldy)
+    return dw
+
+
+def _deliver_bgrad(param, dy):
+    """The bias gradient: into ``param``'s sink (None is returned), or a fresh tensor."""
+    if param is None:
+        return _bias_grad(dy)
+    _bias_grad(dy, into=param._mm_sink)
+    gradsink.done(param)
+    return None
 
 
 def hip_eligible(cin, cout, kh, kw, stride, padding, dilation=1, groups=1):
@@ -406,10 +405,7 @@ class Conv2dFn(torch.autograd.Function):
         tx = [kw - padding for _ in range(KH) for kw in range(KW)]
         b = bias.detach().float().contiguous() if bias is not None else None
         if (KH, KW, stride, padding) == (3, 3, 1, 1):  # halo-tile kernel: input patch staged once for all 9 taps
-            slab, nf = None, Bn
-            if stats is not None and bn_pre_wanted(x.device, Bn, H, W, Cout):
-                nf = _stat_group_split(Bn)
-                slab = _stat_slab(stats, int(lib2d().mm_conv2d_3x3s1_stat_rows(Bn, H, W)), Cout, nf, Bn, x.device)
+            slab, nf = _stat_slab(stats, x.device, (Bn, H, W, Cout), lambda: lib2d().mm_conv2d_3x3s1_stat_rows(Bn, H, W))
             check(lib2d().mm_conv2d_3x3s1(ptr(x), Bn, H, W, Cin, ldx, ptr(y), Cout, Cout, ptr(Wp), ptr(b), 0 | WHOLE_ITEMS[0] | LEGACY3X3[0], ptr(slab), nf,
                                           stream()), "conv2d_3x3s1")
         else:
@@ -462,35 +458,13 @@ class Conv2dFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             ty = [kh - padding for kh in range(KH) for _ in range(KW)]
             tx = [kw - padding for _ in range(KH) for kw in range(KW)]
-            if ctx.wparam is not None and _defer_wgrad():  # slabs now, summed into the arena with every other layer's (_WgBatch)
-                _wgrad_deferred(x, Bn, H, W, Cin, dy, Ho, Wo, Cout, stride, ty, tx, ctx.wparam, Cin * T, 1, T, ldx=ldx, ldy=ldy)
-            elif ctx.wparam is not None:  # accumulate straight into the optimiser's gradient arena
-                _wgrad(x, Bn, H, W, Cin, dy, Ho, Wo, Cout, stride, ty, tx, ctx.wparam._mm_sink, Cin * T, 1, T, accumulate=1, ldx=ldx,
-                       ldy=ldy)
-                gradsink.done(ctx.wparam)
-            else:
-                dw = torch.empty_like(w)
-                _wgrad(x, Bn, H, W, Cin, dy, Ho, Wo, Cout, stride, ty, tx, dw, Cin * T, 1, T, ldx=ldx, ldy=ldy)
+            dw = _deliver_wgrad(ctx.wparam, x, Bn, H, W, Cin, dy, Ho, Wo, Cout, stride, ty, tx, Cin * T, 1, T, w, ldx=ldx, ldy=ldy)
         if has_bias and ctx.needs_input_grad[2]:
-            if ctx.bparam is not None:
-                _bias_grad(as_nhwc_bf16(dy), into=ctx.bparam._mm_sink)
-                gradsink.done(ctx.bparam)
-            else:
-                db = _bias_grad(as_nhwc_bf16(dy))
+            db = _deliver_bgrad(ctx.bparam, as_nhwc_bf16(dy))
         if ctx.handoff is not None and dx is not None:  # the producer's backward kernels add it (fp32) to the other consumer's
             ctx.handoff.extra.append(dx)
             dx = None
         return dx, dw, db, None, None, None, None
-
-
-# Two 3x3 convolutions of one shape in ONE launch (mm_conv2d_3x3s1_pair): the same layer of the RGB and of the depth backbone.
-# MM_CONV_PAIR=0: two launches (A/B).
-STEM7 = [_os.environ.get("MM_CONV_STEM7", "1") != "0"]  # the 7x7 stems on their own kernel (A/B switch: 0 = generic implicit GEMM)
-DGRAD_S2 = [_os.environ.get("MM_CONV_DGRAD_S2", "1") != "0"]  # stride-2 data gradients by output parity (A/B switch)
-PAIR = [_os.environ.get("MM_CONV_PAIR", "1") != "0"]
-PAIR_WGRAD = [_os.environ.get("MM_CONV_PAIR_WGRAD", "1") != "0"]  # the pairs' weight gradients in one launch too
-WGRAD_BATCH[0] = _os.environ.get("MM_CONV_WGRAD_BATCH", "1") != "0"
-WGRAD_BATCH_GRAPH[0] = _os.environ.get("MM_CONV_WGRAD_BATCH_GRAPH", "1") != "0"
 
 
 def pairable(x1, x2, w1, w2):
@@ -518,11 +492,9 @@ class Conv2dPairFn(torch.autograd.Function):
         wf = [w.detach().float().contiguous() for w in (w1, w2)]
         Wp = [_pack(w, 1, Cout, 9, Cin, 0, Cin * 9, 1, 9, owner, "fwd") for w, owner in zip(wf, (w1, w2))]
         y = [torch.empty((Bn, Cout, H, W), dtype=HALF[0], device=x1.device, memory_format=CL) for _ in range(2)]
-        slabs, nf = [None, None], Bn
-        if stats1 is not None and stats2 is not None and bn_pre_wanted(x1.device, Bn, H, W, Cout):
-            nf = _stat_group_split(Bn)
-            rows = int(lib2d().mm_conv2d_3x3s1_stat_rows(Bn, H, W))
-            slabs = [_stat_slab(h, rows, Cout, nf, Bn, x1.device) for h in (stats1, stats2)]
+        dims = (Bn, H, W, Cout)  # statistics for both maps or for neither: the second slab is the first one's twin
+        slab1, nf = _stat_slab(stats1 if stats2 is not None else None, x1.device, dims, lambda: lib2d().mm_conv2d_3x3s1_stat_rows(Bn, H, W))
+        slabs = [slab1, _stat_slab(stats2, x1.device, dims, slab1.shape[0])[0] if slab1 is not None else None]
         # (64 -> 64: the weights-resident kernel pairs when the item list splits at an XCD boundary, else the entry point runs the
         # two problems one after the other)
         check(lib2d().mm_conv2d_3x3s1_pair(ptr(x1), ptr(x2), Bn, H, W, Cin, Cin, ptr(y[0]), ptr(y[1]), Cout, Cout, ptr(Wp[0]), ptr(Wp[1]),
@@ -581,14 +553,7 @@ class Conv2dPairFn(torch.autograd.Function):
         for i in range(2):
             if not ctx.needs_input_grad[2 + i]:
                 continue
-            if ctx.wparams[i] is not None and _defer_wgrad():
-                _wgrad_deferred(xs[i], Bn, H, W, Cin, dys[i], H, W, Cout, 1, ty, tx, ctx.wparams[i], Cin * 9, 1, 9)
-            elif ctx.wparams[i] is not None:  # straight into the optimiser's gradient arena
-                _wgrad(xs[i], Bn, H, W, Cin, dys[i], H, W, Cout, 1, ty, tx, ctx.wparams[i]._mm_sink, Cin * 9, 1, 9, accumulate=1)
-                gradsink.done(ctx.wparams[i])
-            else:
-                dw[i] = torch.empty_like(wfs[i])
-                _wgrad(xs[i], Bn, H, W, Cin, dys[i], H, W, Cout, 1, ty, tx, dw[i], Cin * 9, 1, 9)
+            dw[i] = _deliver_wgrad(ctx.wparams[i], xs[i], Bn, H, W, Cin, dys[i], H, W, Cout, 1, ty, tx, Cin * 9, 1, 9, wfs[i])
         return dx[0], dx[1], dw[0], dw[1], None, None
 
 
@@ -628,20 +593,9 @@ class ConvTranspose2dFn(torch.autograd.Function):
             _gemm(dy, Bn, 2 * H, 2 * W, Cout, dx, H, W, Cin, H, W, 1, 2, 1, ty, tx, Wd)
         if ctx.needs_input_grad[1]:
             # roles: "dY" := x (base grid H x W, n = ci), "X" := dy (source pixel (2y+a, 2x+b), k = co)
-            if ctx.wparam is not None and _defer_wgrad():
-                _wgrad_deferred(dy, Bn, 2 * H, 2 * W, Cout, x, H, W, Cin, 2, ty, tx, ctx.wparam, Cout * 4, 1, 4)
-            elif ctx.wparam is not None:  # straight into the optimiser's gradient arena
-                _wgrad(dy, Bn, 2 * H, 2 * W, Cout, x, H, W, Cin, 2, ty, tx, ctx.wparam._mm_sink, Cout * 4, 1, 4, accumulate=1)
-                gradsink.done(ctx.wparam)
-            else:
-                dw = torch.empty_like(w)
-                _wgrad(dy, Bn, 2 * H, 2 * W, Cout, x, H, W, Cin, 2, ty, tx, dw, Cout * 4, 1, 4)
+            dw = _deliver_wgrad(ctx.wparam, dy, Bn, 2 * H, 2 * W, Cout, x, H, W, Cin, 2, ty, tx, Cout * 4, 1, 4, w)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            if ctx.bparam is not None:
-                _bias_grad(dy, into=ctx.bparam._mm_sink)
-                gradsink.done(ctx.bparam)
-            else:
-                db = _bias_grad(dy)
+            db = _deliver_bgrad(ctx.bparam, dy)
         return dx, dw, db, None
 
 
@@ -707,19 +661,13 @@ class StemConvFn(torch.autograd.Function):
         y = torch.empty((Bn, Cout, H, W), dtype=HALF[0], device=img.device, memory_format=CL)
         ty = [t * R for t in range(T)]
         # virtual activation: pixel pitch (lda) 8, 64 channels, Wi = Wb - 7 valid window starts; output (y,x) reads row y + t*R at x
-        slab, split_m = None, 0
         if STEM7[0] and Cout == 64:
             # the stems' own kernel (csrc/conv2d.hip k_stem7): weights resident, the raw strip of a tile staged once
-            nf = Bn
-            if stats is not None and bn_pre_wanted(img.device, Bn, H, W, Cout):
-                nf = _stat_group_split(Bn)
-                slab = _stat_slab(stats, int(L.mm_conv2d_stem7_stat_rows(Bn, H, W)), Cout, nf, Bn, img.device)
+            slab, nf = _stat_slab(stats, img.device, (Bn, H, W, Cout), lambda: L.mm_conv2d_stem7_stat_rows(Bn, H, W))
             check(L.mm_conv2d_stem7(ptr(xb), Bn, Hb, Wb, H, W, R, T, ptr(y), Cout, ptr(Wp), ptr(slab), nf, stream()), "conv2d_stem7")
         else:
-            if stats is not None and bn_pre_wanted(img.device, Bn, H, W, Cout):
-                nf = _stat_group_split(Bn)
-                slab = _stat_slab(stats, int(L.mm_conv2d_gemm_stat_rows(Bn * H * W, 1)), Cout, nf, Bn, img.device)
-                split_m = nf * H * W
+            slab, nf = _stat_slab(stats, img.device, (Bn, H, W, Cout), lambda: L.mm_conv2d_gemm_stat_rows(Bn * H * W, 1))
+            split_m = nf * H * W if slab is not None else 0
             check(L.mm_conv2d_gemm(ptr(xb), Bn, Hb, Wb, 64, 8, ptr(y), H, W, Cout, Cout, 0, H, W, 1, 0, 0, 1, 1, T, _arr(ty),
                                    _arr([0] * T), ptr(Wp), 1, 0, 0, None, ptr(slab), split_m, None, 0, stream()), "conv2d_gemm(stem)")
         ctx.save_for_backward(xb)

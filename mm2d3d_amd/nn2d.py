@@ -202,10 +202,7 @@ class _BN2dFn(torch.autograd.Function):
                                           ptr(running_var), ptr(nbt), eps, momentum, 1 if relu else 0, ptr(y), ldy, ptr(stats[0]), ptr(stats[1]),
                                           ptr(ws), ws.numel(), stream()), "bn2d_fwd_train")
             ctx.save_for_backward(x, y, weight, stats, bias)
-            ctx.sinks = None
-            if weight is not None and bias is not None and gradsink.claim(ctx, weight, ctx.needs_input_grad[2]):
-                gradsink.claim(ctx, bias, True)
-                ctx.sinks = (weight, bias)
+            ctx.sinks = gradsink.claim_affine(ctx, weight, bias, ctx.needs_input_grad[2])
         else:
             check(L.mm_bn2d_fwd_eval(ptr(x), ldx, ptr(res), ldr, N, C, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var), eps,
                                      1 if relu else 0, ptr(y), ldy, stream()), "bn2d_fwd_eval")
@@ -234,14 +231,7 @@ class _BN2dFn(torch.autograd.Function):
         dx = torch.empty((B, C, H, W), dtype=_c2d.HALF[0], device=x.device, memory_format=CL)
         dres = torch.empty_like(dx) if ctx.has_res else None
         ws = _lib.workspace.get(int(L.mm_bn2d_ws_bytes(C)), x.device)
-        if ctx.sinks is not None:  # dgamma / dbeta accumulate straight into the optimiser's gradient arena
-            wp, bp = ctx.sinks
-            dw = db = None
-            dwt, dbt, acc = wp._mm_sink, bp._mm_sink, 1
-        else:
-            dw = dwt = torch.empty(C, dtype=F32, device=x.device)
-            db = dbt = torch.empty(C, dtype=F32, device=x.device)
-            acc = 0
+        dwt, dbt, acc, dw, db = gradsink.affine_targets(ctx.sinks, C, x.device)  # dgamma / dbeta: into the gradient arena, or fresh
         if _lib.BARRIER_LISTENERS and L.mm_bn2d_single_launch(ctx.hd.h, N, ctx.Ns, C, 1):
             _lib.before_barrier_kernel(True)
         check(L.mm_bn2d_bwd(ctx.hd.h, ptr(x), ldx, ptr(dy), lddy, ptr(dy2), lddy2, ptr(ymask), ldy, 1 if ctx.relu else 0, N, ctx.Ns, C, ptr(weight),
@@ -249,9 +239,7 @@ class _BN2dFn(torch.autograd.Function):
                             ptr(stats[0]), ptr(stats[1]),
                             ptr(dx), C, ptr(dres), C, ptr(dwt), ptr(dbt), acc, ptr(ws), ws.numel(),
                             stream()), "bn2d_bwd")
-        if ctx.sinks is not None:
-            gradsink.done(wp)
-            gradsink.done(bp)
+        gradsink.done_all(ctx.sinks)
         if dres is not None and ctx.res_handoff is not None:  # the residual's producer sums it in its own backward kernels
             ctx.res_handoff.extra.append(dres)
             dres = None
@@ -303,11 +291,7 @@ class _BN2dPairFn(torch.autograd.Function):
         check(L.mm_bn2d_fwd_train_pair(hd.h, C_.byref(args[0]), C_.byref(args[1]), N, Ns, C, cfg1["eps"], cfg1["momentum"], 1 if cfg1["relu"] else 0,
                                        ptr(ws), ws.numel(), stream()), "bn2d_fwd_train_pair")
         ctx.save_for_backward(xs[0], xs[1], ys[0], ys[1], w1, w2, stats[0], stats[1], b1, b2)
-        ctx.sinks = [None, None]
-        for i in range(2):
-            if gradsink.claim(ctx, ws_[i], ctx.needs_input_grad[4 + i]):
-                gradsink.claim(ctx, bs[i], True)
-                ctx.sinks[i] = (ws_[i], bs[i])
+        ctx.sinks = [gradsink.claim_affine(ctx, ws_[i], bs[i], ctx.needs_input_grad[4 + i]) for i in range(2)]
         ctx.relu, ctx.has_res = cfg1["relu"], res1 is not None
         ctx.lds = (ldx, ldy)
         ctx.handoffs = (cfg1["handoff"], cfg2["handoff"])
@@ -338,12 +322,7 @@ class _BN2dPairFn(torch.autograd.Function):
         wsb = _lib.workspace.get(int(L.mm_bn2d_ws_bytes(C)), x1.device)
         # the pair entry shares ``accumulate``: both problems into their sinks, or both into fresh tensors
         both_sinks = ctx.sinks[0] is not None and ctx.sinks[1] is not None
-        tgt = []
-        for i in range(2):
-            if both_sinks:
-                tgt.append((ctx.sinks[i][0]._mm_sink, ctx.sinks[i][1]._mm_sink))
-            else:
-                tgt.append((torch.empty(C, dtype=F32, device=x1.device), torch.empty(C, dtype=F32, device=x1.device)))
+        tgt = [gradsink.affine_targets(ctx.sinks[i] if both_sinks else None, C, x1.device)[:2] for i in range(2)]
         if _lib.BARRIER_LISTENERS and L.mm_bn2d_single_launch(ctx.hd.h, N, ctx.Ns, C, 1):
             _lib.before_barrier_kernel(True)
         args = [_lib.Bn2dBwdArgs(ptr(xs[i]), ldx[i], ptr(dys[i]), lddy[i], ptr(dy2s[i]), lddy2[i], ptr(ymask[i]), ldy[i], ptr(ws_[i]), ptr(bs[i]),
@@ -352,16 +331,12 @@ class _BN2dPairFn(torch.autograd.Function):
                                  ptr(wsb), wsb.numel(), stream()), "bn2d_bwd_pair")
         dw, db = [None, None], [None, None]
         for i in range(2):
-            if both_sinks:
-                gradsink.done(ctx.sinks[i][0])
-                gradsink.done(ctx.sinks[i][1])
-            elif ctx.sinks[i] is not None:  # only one of the two has a sink: add its fresh gradient there by hand
+            if ctx.sinks[i] is None:
+                dw[i], db[i] = tgt[i]
+            elif not both_sinks:  # only one of the two has a sink: add its fresh gradient there by hand
                 ctx.sinks[i][0]._mm_sink.add_(tgt[i][0])
                 ctx.sinks[i][1]._mm_sink.add_(tgt[i][1])
-                gradsink.done(ctx.sinks[i][0])
-                gradsink.done(ctx.sinks[i][1])
-            else:
-                dw[i], db[i] = tgt[i]
+            gradsink.done_all(ctx.sinks[i])
             if dres[i] is not None and ctx.res_handoffs[i] is not None:
                 ctx.res_handoffs[i].extra.append(dres[i])
                 dres[i] = None
@@ -526,10 +501,7 @@ class _BnPoolFn(torch.autograd.Function):
         ctx.save_for_backward(x, weight, stats, bias, idx)
         ctx.dims = (B, C, H, W, Bs, ldx)
         ctx.hd = _lib.handle(x.device)
-        ctx.sinks = None
-        if gradsink.claim(ctx, weight, ctx.needs_input_grad[1]):
-            gradsink.claim(ctx, bias, True)
-            ctx.sinks = (weight, bias)
+        ctx.sinks = gradsink.claim_affine(ctx, weight, bias, ctx.needs_input_grad[1])
         return y, yp
 
     @staticmethod
@@ -553,14 +525,7 @@ class _BnPoolFn(torch.autograd.Function):
         dyp, lddyp = _c2d.nhwc_pitch(dyp)
         dx = torch.empty((B, C, H, W), dtype=_c2d.HALF[0], device=x.device, memory_format=CL)
         ws = _lib.workspace.get(int(L.mm_bn2d_ws_bytes(C)), x.device)
-        if ctx.sinks is not None:
-            wp, bp = ctx.sinks
-            dw = db = None
-            dwt, dbt, acc = wp._mm_sink, bp._mm_sink, 1
-        else:
-            dw = dwt = torch.empty(C, dtype=F32, device=x.device)
-            db = dbt = torch.empty(C, dtype=F32, device=x.device)
-            acc = 0
+        dwt, dbt, acc, dw, db = gradsink.affine_targets(ctx.sinks, C, x.device)
         if BN_POOL[0] == "fwd":  # the separate kernels: the pooled gradient scattered to a full-resolution map, then mm_bn2d_bwd
             dxp = torch.empty((B, C, H, W), dtype=_c2d.HALF[0], device=x.device, memory_format=CL)
             check(L.mm_maxpool3x3s2_bwd(ptr(dyp), lddyp, None, 0, ptr(idx), B, H, W, C, ptr(dxp), stream()), "maxpool_bwd")
@@ -576,9 +541,7 @@ class _BnPoolFn(torch.autograd.Function):
             check(L.mm_bn2d_bwd_pool(ptr(x), ldx, ptr(dyp), lddyp, ptr(idx), B, H, W, Bs, ptr(dy2), lddy2, C, ptr(weight), ptr(bias),
                                      ptr(stats[0]), ptr(stats[1]), ptr(dx), C, ptr(dwt), ptr(dbt), acc, ptr(ws), ws.numel(), stream()),
                   "bn2d_bwd_pool")
-        if ctx.sinks is not None:
-            gradsink.done(wp)
-            gradsink.done(bp)
+        gradsink.done_all(ctx.sinks)
         return dx, dw, db, None, None, None, None, None, None, None, None
 
 

@@ -215,26 +215,16 @@ def _apply_os_bf16(x, weight, w_kcc, table, cout, transpose, kflip):
     return out
 
 
-def _dw_bf16(x, dout, rb, src, dst, cin, cout, sink=None):
-    L = _lib.lib()
-    dW = sink if sink is not None else torch.empty((rb.K, cin, cout), dtype=F32, device=x.device)
-    ws = _lib.workspace.get(int(L.mm_spconv_dw_ws_bytes(rb.offsets_ptr, rb.K, cin, cout)), x.device)
-    check((L.mm_spconv_dw_f16 if x.dtype == F16 else L.mm_spconv_dw_bf16)(
-        ptr(x), x.stride(0), cin, ptr(dout), dout.stride(0), cout, ptr(src), ptr(dst), rb.offsets_ptr, rb.K,
-        ptr(dW), 0 if sink is None else 1, ENGINE_MODE[0], ptr(ws), ws.numel(), stream()), "spconv_dw_16")
-    return dW
-
-
 def _dw(x, dout, rb, src, dst, cin, cout, sink=None):
-    """dW [K, cin, cout]; with ``sink`` (the parameter's slice of the gradient arena) the kernel accumulates into it."""
+    """dW [K, cin, cout] (fp32) of fp32, bf16 or IEEE fp16 rows; with ``sink`` (the parameter's slice of the gradient arena) the kernel
+    accumulates into it."""
     L = _lib.lib()
     dW = sink if sink is not None else torch.empty((rb.K, cin, cout), dtype=F32, device=x.device)
     ws = _lib.workspace.get(int(L.mm_spconv_dw_ws_bytes(rb.offsets_ptr, rb.K, cin, cout)), x.device)
-    check(
-        L.mm_spconv_dw(ptr(x), x.stride(0), cin, ptr(dout), dout.stride(0), cout, ptr(src), ptr(dst), rb.offsets_ptr, rb.K,
-                       ptr(dW), 0 if sink is None else 1, ENGINE_MODE[0], ptr(ws), ws.numel(), stream()),
-        "spconv_dw",
-    )
+    fn = {BF16: L.mm_spconv_dw_bf16, F16: L.mm_spconv_dw_f16}.get(x.dtype, L.mm_spconv_dw)
+    check(fn(ptr(x), x.stride(0), cin, ptr(dout), dout.stride(0), cout, ptr(src), ptr(dst), rb.offsets_ptr, rb.K,
+             ptr(dW), 0 if sink is None else 1, ENGINE_MODE[0], ptr(ws), ws.numel(), stream()),
+          "spconv_dw_16" if x.dtype in H16 else "spconv_dw")
     return dW
 
 
@@ -246,11 +236,12 @@ def _dw(x, dout, rb, src, dst, cin, cout, sink=None):
 DW_BATCH = [os.environ.get("MM_SPCONV_DW_BATCH", "1") != "0"]
 
 
-class _DwBatch:
+class _DwBatch(gradsink.DeferredSums):
+    """Items: (partial, sink, ne, K, blk_start row, param)."""
+
     def __init__(self):
-        self.expected = 0  # forward calls with a sink whose backward has not run yet (early trigger only, see flush)
-        self.items = []    # (partial, sink, ne, K, blk_start row, param)
-        self.cb_queued = False
+        super().__init__()
+        self.expected = 0  # forward calls with a sink whose backward has not run yet (the early trigger, see add)
         self.row_ints = None
 
     def rows(self):
@@ -258,40 +249,26 @@ class _DwBatch:
             self.row_ints = (int(_lib.lib().mm_spconv_dw_desc_bytes()) - 32) // 4
         return self.row_ints
 
-    def add(self, partial, sink, ne, K, row, param):
-        self.items.append((partial, sink, ne, K, row, param))
-        if not self.cb_queued:
-            self.cb_queued = True
-            torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
+    def _dests(self, it):
+        return (it[1].data_ptr(),)
+
+    def _params(self, it):
+        return (it[5],)
+
+    def add(self, item):
+        """The sums run as soon as the last sparse convolution that went forward with a sink has issued its slabs."""
+        super().add(item)
         self.expected -= 1
         if self.expected == 0:
             self.flush()
 
     def _end_of_backward(self):
-        self.cb_queued = False
         self.expected = 0  # heals a forward that never saw its backward
-        self.flush()
+        super()._end_of_backward()
 
-    def flush(self):
-        items, self.items = self.items, []
-        if not items:
-            return
-        # A weight that went forward twice (the literal two-call sequence of the two domains, train.py:186-292; gradient accumulation)
-        # has two slab sets that ADD into one gradient: they must not share a launch - two workgroups would read-modify-write the
-        # same words (round 6: found as run-to-run differences of the 3D gradients in that mode; the joint-domain step uses every
-        # weight once).  A new launch starts whenever a destination repeats, as conv2d._WgBatch does.
-        groups, seen = [[]], set()
-        for it in items:
-            dst = it[1].data_ptr()
-            if dst in seen:
-                groups.append([])
-                seen = set()
-            seen.add(dst)
-            groups[-1].append(it)
-        for g in groups:
-            self._launch(g)
-        for it in items:
-            gradsink.done(it[5])
+    def reset(self):
+        super().reset()
+        self.expected = 0
 
     def _launch(self, items):
         L = _lib.lib()
@@ -393,16 +370,7 @@ class SparseConvFunction(torch.autograd.Function):
         ctx.act16 = act16
         if act16:
             out = _timed("fwd", rb, cin, cout, lambda: _apply_os_bf16(x, weight, w, table, cout, False, False), 2)
-            ctx.save_for_backward(x, w)
-            ctx.rb, ctx.mode, ctx.n_in, ctx.wshape = rb, mode, n_in, weight.shape
-            ctx.weight = weight
-            ctx.wparam = weight if (weight.dtype == F32 and weight.is_contiguous()
-                                    and gradsink.claim(ctx, weight, ctx.needs_input_grad[1])) else None
-            ctx.dw_batched = ctx.wparam is not None and DW_BATCH[0]
-            if ctx.dw_batched:
-                _DWB.expected += 1
-            return out
-        if _os_usable(table, x, cin, cout) and table.n_dst == n_out:
+        elif _os_usable(table, x, cin, cout) and table.n_dst == n_out:
             out = _timed("fwd", rb, acin, cout, lambda: _apply_os(x, weight, w, table, cout, False, False))
         elif mode in ("subm", "down"):
             out = _timed("fwd", rb, acin, cout, lambda: _apply(x, w, rb, rb.rin, rb.rout, n_out, cout, False, False, False, weight=weight))
@@ -434,9 +402,9 @@ class SparseConvFunction(torch.autograd.Function):
                 a, b = (rb.rout, rb.rin) if mode == "up" else (rb.rin, rb.rout)
                 if ctx.dw_batched:
                     pr = _timed("dW", rb, cin, cout, lambda: _dw_partial(x, dout, rb, a, b, cin, cout, sink, ctx.wparam, True), 2)
-                    _DWB.add(pr[0], sink, cin * cout, rb.K, pr[1], ctx.wparam)
+                    _DWB.add((pr[0], sink, cin * cout, rb.K, pr[1], ctx.wparam))
                     return dx, None, None, None, None, None, None
-                dw = _timed("dW", rb, cin, cout, lambda: _dw_bf16(x, dout, rb, a, b, cin, cout, sink), 2)
+                dw = _timed("dW", rb, cin, cout, lambda: _dw(x, dout, rb, a, b, cin, cout, sink), 2)
                 if sink is not None:
                     gradsink.done(ctx.wparam)
                     dw = None
@@ -496,7 +464,7 @@ class SparseConvFunction(torch.autograd.Function):
                 dw = weight_grad(True)
         if dw is not None:
             if batched:
-                _DWB.add(dw[0], sink, cin * cout, rb.K, dw[1], ctx.wparam)
+                _DWB.add((dw[0], sink, cin * cout, rb.K, dw[1], ctx.wparam))
                 dw = None
             elif sink is not None:
                 gradsink.done(ctx.wparam)
@@ -588,10 +556,7 @@ class BatchNormActFunction(torch.autograd.Function):
                 )
             ctx.save_for_backward(x, weight, bias, stats)
             ctx.leak = leak
-            ctx.sinks = None
-            if weight is not None and bias is not None and gradsink.claim(ctx, weight, ctx.needs_input_grad[1]):
-                gradsink.claim(ctx, bias, True)
-                ctx.sinks = (weight, bias)
+            ctx.sinks = gradsink.claim_affine(ctx, weight, bias, ctx.needs_input_grad[1])
         elif act16 and weight is not None:
             _bn16_fwd(L, hd.h, x, C, N, N, C, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var), False, eps, momentum, leak, ptr(y), C,
                       None)
@@ -616,14 +581,7 @@ class BatchNormActFunction(torch.autograd.Function):
         N, C = x.shape
         dx = torch.empty_like(x)
         ws = _lib.workspace.get(int(L.mm_bn_ws_bytes(C)) + 8 * C, x.device)
-        if ctx.sinks is not None:
-            wp, bp = ctx.sinks
-            dw = db = None
-            dwt, dbt, acc = wp._mm_sink, bp._mm_sink, 1
-        else:
-            dw = dwt = torch.empty(C, dtype=F32, device=x.device) if weight is not None else None
-            db = dbt = torch.empty(C, dtype=F32, device=x.device) if bias is not None else None
-            acc = 0
+        dwt, dbt, acc, dw, db = gradsink.affine_targets(ctx.sinks, C, x.device, weight is not None, bias is not None)
         if _lib.BARRIER_LISTENERS and ctx.hd.get(_lib.OPT_BN3D_FUSED) & 2:
             # the row kernels decide inside the library whether they take the single-launch form: assume so when the handle allows it
             _lib.before_barrier_kernel(True, sparse=True)
@@ -632,9 +590,7 @@ class BatchNormActFunction(torch.autograd.Function):
         else:
             check(_bn_entry(L, x.dtype, ctx.hd.h)[2](ptr(x), C, ptr(dy), C, N, ctx.Ns, C, ptr(weight), ptr(bias), ptr(stats[0]), ptr(stats[1]), ctx.leak,
                                            ptr(dx), C, ptr(dwt), ptr(dbt), acc, ptr(ws), ws.numel(), stream()), "bn_bwd")
-        if ctx.sinks is not None:
-            gradsink.done(wp)
-            gradsink.done(bp)
+        gradsink.done_all(ctx.sinks)
         return dx, dw, db, None, None, None, None, None, None, None
 
 class BatchNormActJoinFunction(torch.autograd.Function):
@@ -679,9 +635,7 @@ class BatchNormActJoinFunction(torch.autograd.Function):
         ctx.sinks = None
         if training:
             ctx.save_for_backward(weight, bias, *stats, *xs)
-            if gradsink.claim(ctx, weight, ctx.needs_input_grad[0]):
-                gradsink.claim(ctx, bias, True)
-                ctx.sinks = (weight, bias)
+            ctx.sinks = gradsink.claim_affine(ctx, weight, bias, ctx.needs_input_grad[0])
         return y
 
     @staticmethod
@@ -695,14 +649,7 @@ class BatchNormActJoinFunction(torch.autograd.Function):
         es = 2 if ctx.act16 else 4
         dy = _c(dy.to(xs[0].dtype if ctx.act16 else F32))
         N, C = dy.shape
-        if ctx.sinks is not None:
-            wp, bp = ctx.sinks
-            dw = db = None
-            dwt, dbt, acc = wp._mm_sink, bp._mm_sink, 1
-        else:
-            dw = dwt = torch.empty(C, dtype=F32, device=dy.device)
-            db = dbt = torch.empty(C, dtype=F32, device=dy.device)
-            acc = 0
+        dwt, dbt, acc, dw, db = gradsink.affine_targets(ctx.sinks, C, dy.device)
         bwd = _bn_entry(L, xs[0].dtype, ctx.hd.h)[2]
         if _lib.BARRIER_LISTENERS and ctx.hd.get(_lib.OPT_BN3D_FUSED) & 2:
             _lib.before_barrier_kernel(True, sparse=True)
@@ -718,9 +665,7 @@ class BatchNormActJoinFunction(torch.autograd.Function):
                           ctx.leak, ptr(dx), c, ptr(dwt) + 4 * off, ptr(dbt) + 4 * off, acc, ptr(ws), ws.numel(), stream()), "bn_bwd")
             dxs.append(dx)
             off += c
-        if ctx.sinks is not None:
-            gradsink.done(wp)
-            gradsink.done(bp)
+        gradsink.done_all(ctx.sinks)
         return (dw, db, None, None, None, None, None, None, None, *dxs)
 
 

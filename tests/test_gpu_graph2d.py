@@ -166,8 +166,11 @@ def test_captured_forward_always_repacks_the_weights():
 def test_deferred_weight_gradient_sums_survive_a_backward_pass_that_raised():
     """the autograd engine skips the end-of-backward callbacks of a pass that raised, so conv2d._WgBatch.flush
     never ran; FlatAdamW.zero_grad -> reset() must also re-arm the callback, else no later backward queues it and the 2D convolution
-    weight gradients stay zero.  An eager step with a backward that raises, then ordinary steps: equal to a trainer that skipped it."""
-    from mm2d3d_amd import conv2d as c2, graph2d
+    weight gradients stay zero.  An eager step with a backward that raises, then ordinary steps: equal to a trainer that skipped it.
+    The 3D branch's batch (scn.ops._DwBatch, the same gradsink.DeferredSums) is left in the same stuck state, its early-trigger count
+    offset as well."""
+    from mm2d3d_amd import conv2d as c2, graph2d, scn
+    from mm2d3d_amd.scn import ops
     from mm2d3d_amd.synthetic import make_batch
 
     dev = torch.device("cuda:0")
@@ -185,10 +188,10 @@ def test_deferred_weight_gradient_sums_survive_a_backward_pass_that_raised():
         def backward(ctx, g):
             raise RuntimeError("boom")
 
-    was, wb = graph2d.ENABLED[0], c2.WGRAD_BATCH[0]
+    was, wb, db = graph2d.ENABLED[0], c2.WGRAD_BATCH[0], ops.DW_BATCH[0]
     try:
         graph2d.ENABLED[0] = False
-        c2.WGRAD_BATCH[0] = True
+        c2.WGRAD_BATCH[0] = ops.DW_BATCH[0] = True
         ga = _trainer(dev, n2, n3, 0.0)
         for o in ga.optimizers:
             o.zero_grad()
@@ -200,6 +203,9 @@ def test_deferred_weight_gradient_sums_survive_a_backward_pass_that_raised():
         # a backward that raised after queuing work: emulate the engine's skipped callback (what ADVICE describes) and recover
         c2._WGB.cb_queued = True
         c2._WGB.items.append(None)
+        ops._DWB.cb_queued = True
+        ops._DWB.items.append(None)
+        ops._DWB.expected = 3
         la = [float(ga.fit_step(mk(i)).detach()) for i in range(1, 4)]
         eb = _trainer(dev, n2b, n3b, 0.0)
         for o in eb.optimizers:
@@ -210,6 +216,8 @@ def test_deferred_weight_gradient_sums_survive_a_backward_pass_that_raised():
         _same_state(ga, eb)
         w = next(p for n, p in n2.named_parameters() if n.endswith("layer2.1.conv1.weight"))
         assert float(w.grad.abs().sum()) > 0
+        w3 = next(m.weight for m in n3.modules() if isinstance(m, scn.Convolution))
+        assert hasattr(w3, "_mm_sink") and float(w3.grad.abs().sum()) > 0
     finally:
-        graph2d.ENABLED[0], c2.WGRAD_BATCH[0] = was, wb
+        graph2d.ENABLED[0], c2.WGRAD_BATCH[0], ops.DW_BATCH[0] = was, wb, db
         graph2d.reset()
