@@ -142,6 +142,19 @@ int mm_collect_points(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_
 int mm_collect_points_f64(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bound, const int64_t* locs, const int64_t* img_indices,
                           const int64_t* labels, const float* image, int C, int H, int W, const double* points, int64_t* img_indices_out,
                           int64_t* labels_out, float* feats_out, double* points_out, mm_stream_t stream);
+/* device-count forms, for a caller that must not wait for the stream (mm2d3d_amd/pipeline.py): the launch covers n_total = the
+ * batch's point count, the size every output is allocated at; the kept total is read on the device from counts[B] (counts =
+ * the [B+1] words of mm_voxelize_batch) and rows at or beyond it are left untouched.  extra_in / extra_out: n_extra (<= 3) host
+ * arrays of device pointers to per-point arrays of extra_bytes-wide elements (1, 2, 4 or 8: the pseudo labels), gathered in
+ * the same launch: extra_out[j][p] = extra_in[j][keep[p]] */
+int mm_collect_points_dev(const int32_t* keep, const int32_t* counts_dev, int B, int64_t n_total, const int64_t* locs,
+                          const int64_t* img_indices, const int64_t* labels, const float* image, int C, int H, int W, const float* points,
+                          int64_t* img_indices_out, int64_t* labels_out, float* feats_out, float* points_out,
+                          const void* const* extra_in, void* const* extra_out, int n_extra, int extra_bytes, mm_stream_t stream);
+int mm_collect_points_f64_dev(const int32_t* keep, const int32_t* counts_dev, int B, int64_t n_total, const int64_t* locs,
+                              const int64_t* img_indices, const int64_t* labels, const float* image, int C, int H, int W,
+                              const double* points, int64_t* img_indices_out, int64_t* labels_out, float* feats_out, double* points_out,
+                              const void* const* extra_in, void* const* extra_out, int n_extra, int extra_bytes, mm_stream_t stream);
 
 /* ---------------------------------------------------------------- camera-image preparation (csrc/imageprep.hip)
  * The image half of the loaders' per-sample code for a whole batch, bit-exact with PIL + numpy: the crop and the

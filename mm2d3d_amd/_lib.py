@@ -53,6 +53,8 @@ _PROTOS = {
     "mm_voxelize_batch_f64": (i32, [vp, vp, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mm_collect_points": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mm_collect_points_f64": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "mm_collect_points_dev": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "mm_collect_points_f64_dev": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "mm_image_prepare": (i32, [vp, i64, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
     "mm_jpeg_ws_bytes": (sz, [i32, i64, i64, i64, i64, i64]),
     "mm_jpeg_decode": (i32, [vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, i64, vp, vp, sz, vp]),

@@ -210,15 +210,13 @@ __global__ __launch_bounds__(T) void k_proj_fill(const int32_t* __restrict__ win
   if (seg2d) seg2d[p] = w >= 0 ? (double)labels[w] : -100.0;
 }
 
-// the per-point arrays of the kept rows: image indices, labels, RGB features img[b, :, r, c], points (P = their type)
+// the per-point arrays of one kept row p: image indices, labels, RGB features img[b, :, r, c], points (P = their type)
 template <typename P>
-__global__ __launch_bounds__(T) void k_collect(const int32_t* __restrict__ keep, const int32_t* __restrict__ n_keep, int64_t n_bound,
-                                                const int64_t* __restrict__ locs, const int64_t* __restrict__ img_indices,
-                                                const int64_t* __restrict__ labels, const float* __restrict__ image, int C, int H, int W,
-                                                const P* __restrict__ points, int64_t* __restrict__ idx_out,
-                                                int64_t* __restrict__ lab_out, float* __restrict__ feats, P* __restrict__ pts_out) {
-  const int64_t p = (int64_t)blockIdx.x * T + threadIdx.x;
-  if (p >= n_bound || p >= (int64_t)*n_keep) return;
+__device__ inline void collect_row(int64_t p, const int32_t* __restrict__ keep, const int64_t* __restrict__ locs,
+                                   const int64_t* __restrict__ img_indices, const int64_t* __restrict__ labels,
+                                   const float* __restrict__ image, int C, int H, int W, const P* __restrict__ points,
+                                   int64_t* __restrict__ idx_out, int64_t* __restrict__ lab_out, float* __restrict__ feats,
+                                   P* __restrict__ pts_out) {
   const int i = keep[p];
   const int64_t r = img_indices[(int64_t)i * 2 + 0], c = img_indices[(int64_t)i * 2 + 1];
   idx_out[p * 2 + 0] = r;
@@ -232,6 +230,56 @@ __global__ __launch_bounds__(T) void k_collect(const int32_t* __restrict__ keep,
   if (feats) {
     const int64_t b = locs[p * 4 + 3];
     for (int ch = 0; ch < C; ch++) feats[p * C + ch] = image[((b * C + ch) * H + r) * W + c];
+  }
+}
+
+// host-count form: the caller knows an upper bound n_bound that it sized the outputs by (normally the kept count itself)
+template <typename P>
+__global__ __launch_bounds__(T) void k_collect(const int32_t* __restrict__ keep, const int32_t* __restrict__ n_keep, int64_t n_bound,
+                                                const int64_t* __restrict__ locs, const int64_t* __restrict__ img_indices,
+                                                const int64_t* __restrict__ labels, const float* __restrict__ image, int C, int H, int W,
+                                                const P* __restrict__ points, int64_t* __restrict__ idx_out,
+                                                int64_t* __restrict__ lab_out, float* __restrict__ feats, P* __restrict__ pts_out) {
+  const int64_t p = (int64_t)blockIdx.x * T + threadIdx.x;
+  if (p >= n_bound || p >= (int64_t)*n_keep) return;
+  collect_row<P>(p, keep, locs, img_indices, labels, image, C, H, W, points, idx_out, lab_out, feats, pts_out);
+}
+
+// up to three per-point side arrays (the pseudo labels of a batch) gathered by `keep` next to the fixed outputs;
+// `bytes` = element width of all of them (1, 2, 4 or 8)
+struct CollectExtra {
+  const void* in[3];
+  void* out[3];
+  int n, bytes;
+};
+
+template <typename E>
+__device__ inline void gather_extra(const CollectExtra& x, int64_t p, int64_t i) {
+  for (int j = 0; j < x.n; j++) ((E*)x.out[j])[p] = ((const E*)x.in[j])[i];
+}
+
+// device-count form: launched over the batch's total point count n_total (the size the outputs were allocated at), the kept
+// total is counts[B] of mm_voxelize_batch, read here; rows at or beyond it are not written.  Nothing about the launch depends
+// on a number the host would have to read back first.
+template <typename P>
+__global__ __launch_bounds__(T) void k_collect_dev(const int32_t* __restrict__ keep, const int32_t* __restrict__ counts, int B,
+                                                    int64_t n_total, const int64_t* __restrict__ locs,
+                                                    const int64_t* __restrict__ img_indices, const int64_t* __restrict__ labels,
+                                                    const float* __restrict__ image, int C, int H, int W, const P* __restrict__ points,
+                                                    int64_t* __restrict__ idx_out, int64_t* __restrict__ lab_out,
+                                                    float* __restrict__ feats, P* __restrict__ pts_out, CollectExtra extra) {
+  const int64_t p = (int64_t)blockIdx.x * T + threadIdx.x;
+  int64_t kept = counts[B];
+  kept = kept < n_total ? kept : n_total;  // never past the allocation, whatever the count word holds
+  if (p >= kept) return;
+  collect_row<P>(p, keep, locs, img_indices, labels, image, C, H, W, points, idx_out, lab_out, feats, pts_out);
+  const int64_t i = keep[p];
+  switch (extra.bytes) {
+    case 1: gather_extra<uint8_t>(extra, p, i); break;
+    case 2: gather_extra<uint16_t>(extra, p, i); break;
+    case 4: gather_extra<uint32_t>(extra, p, i); break;
+    case 8: gather_extra<uint64_t>(extra, p, i); break;
+    default: break;
   }
 }
 
@@ -312,6 +360,31 @@ int collect_points(const int32_t* keep, const int32_t* n_keep_dev, int64_t n_bou
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
+
+template <typename P>
+int collect_points_dev(const int32_t* keep, const int32_t* counts_dev, int B, int64_t n_total, const int64_t* locs,
+                       const int64_t* img_indices, const int64_t* labels, const float* image, int C, int H, int W, const P* points,
+                       int64_t* img_indices_out, int64_t* labels_out, float* feats_out, P* points_out, const void* const* extra_in,
+                       void* const* extra_out, int n_extra, int extra_bytes, hipStream_t s) {
+  MM_CHECK_ARG(keep && counts_dev && B > 0 && n_total >= 0 && locs && img_indices && img_indices_out, "collect_points_dev: bad arguments");
+  MM_CHECK_ARG(!labels_out || labels, "collect_points_dev: labels_out needs the labels");
+  MM_CHECK_ARG(!feats_out || image, "collect_points_dev: feats need the image");
+  MM_CHECK_ARG(!points_out || points, "collect_points_dev: points_out needs the points");
+  MM_CHECK_ARG(n_extra >= 0 && n_extra <= 3 && (n_extra == 0 || (extra_in && extra_out)), "collect_points_dev: at most 3 extra arrays");
+  MM_CHECK_ARG(n_extra == 0 || extra_bytes == 1 || extra_bytes == 2 || extra_bytes == 4 || extra_bytes == 8,
+               "collect_points_dev: extra arrays hold 1-, 2-, 4- or 8-byte elements");
+  CollectExtra x = {};
+  x.n = n_extra, x.bytes = n_extra ? extra_bytes : 0;
+  for (int j = 0; j < n_extra; j++) {
+    MM_CHECK_ARG(extra_in[j] && extra_out[j], "collect_points_dev: null extra array");
+    x.in[j] = extra_in[j], x.out[j] = extra_out[j];
+  }
+  if (n_total == 0) return MM_OK;
+  hipLaunchKernelGGL(k_collect_dev<P>, dim3((unsigned)mm_cdiv(n_total, T)), dim3(T), 0, s, keep, counts_dev, B, n_total, locs, img_indices,
+                     labels, image, C, H, W, points, img_indices_out, labels_out, feats_out, points_out, x);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -372,6 +445,26 @@ int mm_collect_points_f64(const int32_t* keep, const int32_t* n_keep_dev, int64_
                           int64_t* labels_out, float* feats_out, double* points_out, hipStream_t s) {
   return collect_points<double>(keep, n_keep_dev, n_bound, locs, img_indices, labels, image, C, H, W, points, img_indices_out, labels_out,
                                 feats_out, points_out, s);
+}
+
+// device-count forms of the two above, for a caller that must not wait for the stream: counts = the [B+1] words of
+// mm_voxelize_batch (counts[B] = kept total, read on the device), the launch covers n_total = the batch's point count, the
+// size every output is allocated at; rows >= counts[B] are left untouched.  extra_in / extra_out: n_extra (<= 3) per-point
+// arrays of extra_bytes-wide elements (the pseudo labels), gathered by `keep` in the same launch: out[j][p] = in[j][keep[p]]
+int mm_collect_points_dev(const int32_t* keep, const int32_t* counts_dev, int B, int64_t n_total, const int64_t* locs,
+                          const int64_t* img_indices, const int64_t* labels, const float* image, int C, int H, int W, const float* points,
+                          int64_t* img_indices_out, int64_t* labels_out, float* feats_out, float* points_out,
+                          const void* const* extra_in, void* const* extra_out, int n_extra, int extra_bytes, hipStream_t s) {
+  return collect_points_dev<float>(keep, counts_dev, B, n_total, locs, img_indices, labels, image, C, H, W, points, img_indices_out,
+                                   labels_out, feats_out, points_out, extra_in, extra_out, n_extra, extra_bytes, s);
+}
+
+int mm_collect_points_f64_dev(const int32_t* keep, const int32_t* counts_dev, int B, int64_t n_total, const int64_t* locs,
+                              const int64_t* img_indices, const int64_t* labels, const float* image, int C, int H, int W,
+                              const double* points, int64_t* img_indices_out, int64_t* labels_out, float* feats_out, double* points_out,
+                              const void* const* extra_in, void* const* extra_out, int n_extra, int extra_bytes, hipStream_t s) {
+  return collect_points_dev<double>(keep, counts_dev, B, n_total, locs, img_indices, labels, image, C, H, W, points, img_indices_out,
+                                    labels_out, feats_out, points_out, extra_in, extra_out, n_extra, extra_bytes, s);
 }
 
 }  // extern "C"

@@ -333,6 +333,17 @@ class _Scenes:
             batch["pseudo_label_3d"] = torch.from_numpy(cat("pseudo_label_3d")).to(device) if has3d else []
         return batch
 
+    def begin_gpu_batch(self, indices, device="cuda", want_seg2d=False, image="host", decode_threads=4, queue=True):
+        """The batch of ``gpu_batch(indices, ...)`` without a host wait on the way (mm2d3d_amd/pipeline.py): runs the host
+        phase here (front ends, draws in ``gpu_batch``'s RNG order, file reads, decodes, tables, all packed into pinned staging
+        blocks), then - unless ``queue=False`` - enqueues uploads, kernels and one read-back on the current stream.  Returns the
+        :class:`pipeline.PendingBatch`: ``queue()`` (idempotent), ``result()`` -> the batch dict, bit-identical to
+        ``gpu_batch``'s.  :class:`pipeline.BatchStream` keeps such batches in flight ahead of ``fit_step``."""
+        from .pipeline import PendingBatch
+
+        pending = PendingBatch(self, indices, device, want_seg2d, image, decode_threads)
+        return pending.queue() if queue else pending
+
 
 class NuScenesLidarSegSCN(_Scenes):
     """lib/dataset/nuscenes_dataloader.py:172-369."""
