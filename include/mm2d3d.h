@@ -382,6 +382,19 @@ int mm_ce_fwd(const float* logits, int ld, const int64_t* labels, const float* w
 int mm_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* weight, int64_t N, int C,
               int64_t ignore_index, const float* stats, const float* grad_out, float* dlogits, int ld_d,
               mm_stream_t stream);
+/* Two cross entropies over ONE logits tensor: rows [0, P) against (labels0, weight0), rows [P, N) against (labels1 [N - P],
+ * weight1), each a weighted mean over its own counted rows (the joined [source | target] pass: supervised loss on the source
+ * rows, pseudo-label loss on the target rows).  A NULL labels pointer = an unlabelled segment: loss 0, sum_w 0, zero gradient
+ * rows.  zero_if_empty bit s: segment s reports loss 0 instead of 0/0 when its counted weights sum to 0.  P == 0 and P == N are
+ * legal.  stats[4] = loss0, sum_w0, loss1, sum_w1.  The backward writes every one of the N rows exactly once; a row of segment s
+ * gets grad_out[s] * w[y] / sum_w_s * (softmax - onehot).  No atomics: bit-stable run to run. */
+size_t mm_ce2_ws_bytes(void);
+int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+               const int64_t* labels1, const float* weight1, int64_t ignore_index, int zero_if_empty, float* stats,
+               void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+               const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* stats,
+               const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
 /* mean_i sum_c softmax(tgt)_ic (log softmax(tgt)_ic - log softmax(pred)_ic)  (EXP/train.py:157-184) */
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws,
               size_t ws_bytes, mm_stream_t stream);

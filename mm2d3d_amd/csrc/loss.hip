@@ -94,6 +94,96 @@ __global__ __launch_bounds__(T) void k_ce_bwd(const float* __restrict__ logits, 
   for (int c = 0; c < C; c++) d[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
 }
 
+// ---- two-segment cross entropy: rows [0, P) against (labels0, weight0), rows [P, N) against (labels1, weight1), each segment its
+// own weighted mean.  The joined [source | target] pass keeps a head's logits in ONE tensor; this reads it once per direction and
+// writes its gradient once (no slice gradients to zero-fill, copy and add).  Row arithmetic and reduction order are k_ce_fwd's.
+// A NULL labels pointer = an unlabelled segment.  partial[b] = (sum w*nll, sum w) of segment 0, then of segment 1.
+__global__ __launch_bounds__(T) void k_ce2_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
+                                                const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
+                                                const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
+                                                double* __restrict__ partial) {
+  __shared__ double red[T];
+  double sl0 = 0.0, sw0 = 0.0, sl1 = 0.0, sw1 = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
+    const bool tail = i >= P;
+    const int64_t* labels = tail ? labels1 : labels0;
+    if (!labels) continue;
+    int64_t y = labels[tail ? i - P : i];
+    if (y == ignore || y < 0 || y >= C) continue;
+    const float* weight = tail ? weight1 : weight0;
+    const float* x = logits + i * ld;
+    float m = x[0];
+    for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; c++) s += expf(x[c] - m);
+    float nll = (m + logf(s)) - x[y];
+    float w = weight ? weight[y] : 1.f;
+    if (tail) {
+      sl1 += (double)(w * nll);
+      sw1 += (double)w;
+    } else {
+      sl0 += (double)(w * nll);
+      sw0 += (double)w;
+    }
+  }
+  double a0 = block_sum(sl0, red);
+  double b0 = block_sum(sw0, red);
+  double a1 = block_sum(sl1, red);
+  double b1 = block_sum(sw1, red);
+  if (threadIdx.x == 0) {
+    double* o = partial + 4 * (int64_t)blockIdx.x;
+    o[0] = a0, o[1] = b0, o[2] = a1, o[3] = b1;
+  }
+}
+
+// labelled: bit s = segment s has labels; zero_if_empty: bit s = a segment whose weights sum to 0 reports loss 0 instead of 0/0
+__global__ __launch_bounds__(64) void k_ce2_finalize(const double* __restrict__ partial, int nb, int labelled, int zero_if_empty,
+                                                      float* __restrict__ out /*[4]: loss0, sum_w0, loss1, sum_w1*/) {
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < nb; i += 64) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] += partial[4 * i + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) v[k] = wave_sum64(v[k]);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      double a = v[2 * s], b = v[2 * s + 1];
+      bool zero = !((labelled >> s) & 1) || (((zero_if_empty >> s) & 1) && b == 0.0);
+      out[2 * s] = zero ? 0.f : (float)(a / b);  // 0/0 = nan, as k_ce_finalize
+      out[2 * s + 1] = (float)b;
+    }
+  }
+}
+
+// every row written once: segment s: gout[s] * w[y] / sum_w_s * (softmax - onehot); ignored and unlabelled rows: zeros
+__global__ __launch_bounds__(T) void k_ce2_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
+                                                const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
+                                                const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
+                                                const float* __restrict__ stats, const float* __restrict__ gout,
+                                                float* __restrict__ dlogits, int ld_d) {
+  int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
+  if (i >= N) return;
+  const bool tail = i >= P;
+  const int64_t* labels = tail ? labels1 : labels0;
+  int64_t y = labels ? labels[tail ? i - P : i] : ignore;
+  float* d = dlogits + i * ld_d;
+  if (!labels || y == ignore || y < 0 || y >= C) {
+    for (int c = 0; c < C; c++) d[c] = 0.f;
+    return;
+  }
+  const float* weight = tail ? weight1 : weight0;
+  const float* x = logits + i * ld;
+  float m = x[0];
+  for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
+  float s = 0.f;
+  for (int c = 0; c < C; c++) s += expf(x[c] - m);
+  float k = gout[tail] * (weight ? weight[y] : 1.f) / stats[2 * tail + 1];
+  float inv = 1.f / s;
+  for (int c = 0; c < C; c++) d[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
+}
+
 // partial[b] = sum_i sum_c q_ic (log q_ic - log p_ic)
 __global__ __launch_bounds__(T) void k_kl_fwd(const float* __restrict__ pred, int ld_p, const float* __restrict__ tgt,
                                                int ld_t, int64_t N, int C, double* __restrict__ partial) {
@@ -249,6 +339,39 @@ int mm_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* w
   if (N == 0) return MM_OK;
   hipLaunchKernelGGL(k_ce_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, labels, weight, N, C, ignore_index, stats,
                      grad_out, dlogits, ld_d);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+size_t mm_ce2_ws_bytes() { return mm_align((size_t)MAX_PART * 4 * sizeof(double)) + 256; }
+
+// stats[4] = loss and weight sum of rows [0, P), then of rows [P, N); see include/mm2d3d.h
+int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+               const int64_t* labels1, const float* weight1, int64_t ignore_index, int zero_if_empty, float* stats, void* ws,
+               size_t ws_bytes, hipStream_t s) {
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C, "ce2: bad C");
+  MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N, "ce2: the split must lie in [0, N]");
+  if (ws_bytes < (size_t)MAX_PART * 4 * sizeof(double)) {
+    mm_set_error("ce2: workspace too small");
+    return MM_ERR_WORKSPACE;
+  }
+  int nb = loss_blocks(N);
+  hipLaunchKernelGGL(k_ce2_fwd, dim3(nb), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index,
+                     (double*)ws);
+  hipLaunchKernelGGL(k_ce2_finalize, dim3(1), dim3(64), 0, s, (const double*)ws, nb, (labels0 ? 1 : 0) | (labels1 ? 2 : 0),
+                     zero_if_empty, stats);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+               const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* stats, const float* grad_out,
+               float* dlogits, int ld_d, hipStream_t s) {
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C && ld_d >= C, "ce2: bad C");
+  MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N, "ce2: the split must lie in [0, N]");
+  if (N == 0) return MM_OK;
+  hipLaunchKernelGGL(k_ce2_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1,
+                     ignore_index, stats, grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

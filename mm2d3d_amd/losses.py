@@ -47,21 +47,105 @@ class _CrossEntropyFn(torch.autograd.Function):
 _WEIGHT_CACHE = {}  # (class weights, device) -> device tensor
 
 
-def cross_entropy(pred, gt, weight=None, ignore_index=-100):
+def _device_weight(weight, device):
     if isinstance(weight, (list, tuple)):
         # the class weights of a config come as a Python list (config.yaml:45): uploaded ONCE per device.  torch.tensor(list,
         # device=cuda) is a pageable host-to-device copy - the host waits until the stream has reached it, i.e. for the whole
         # forward pass queued before the loss: 3.3 ms per call in the host profile of round 5, twice per step.
-        key = (tuple(float(v) for v in weight), pred.device)
+        key = (tuple(float(v) for v in weight), device)
         hit = _WEIGHT_CACHE.get(key)
         if hit is None:
             if len(_WEIGHT_CACHE) > 64:
                 _WEIGHT_CACHE.clear()
-            hit = _WEIGHT_CACHE[key] = torch.tensor(weight, dtype=F32, device=pred.device)
+            hit = _WEIGHT_CACHE[key] = torch.tensor(weight, dtype=F32, device=device)
         weight = hit
     elif weight is not None:
-        weight = weight.to(device=pred.device, dtype=F32).contiguous()
-    return _CrossEntropyFn.apply(pred, gt, weight, ignore_index)
+        weight = weight.to(device=device, dtype=F32).contiguous()
+    return weight
+
+
+def cross_entropy(pred, gt, weight=None, ignore_index=-100):
+    return _CrossEntropyFn.apply(pred, gt, _device_weight(weight, pred.device), ignore_index)
+
+
+class _CrossEntropyPairFn(torch.autograd.Function):
+    """Rows [0, split) of ``logits`` against (labels0, weight0), rows [split, N) against (labels1, weight1): one forward call,
+    and ONE backward launch that writes the whole gradient from both upstream gradients (csrc/loss.hip k_ce2_*)."""
+
+    @staticmethod
+    def forward(ctx, logits, split, labels0, weight0, labels1, weight1, ignore_index, zero_bits):
+        _lib.require_cuda(logits, "pred")
+        L = _lib.lib()
+        ctx.in_dtype = logits.dtype
+        logits = logits.to(F32)
+        N, C = logits.shape
+        if logits.stride(1) != 1 or (N > 1 and logits.stride(0) < C):
+            logits = logits.contiguous()  # a row-pitched view (stride(1) == 1) is read in place, as pselab._logits does
+        ld = logits.stride(0) if N > 1 else C
+        stats = torch.empty(4, dtype=F32, device=logits.device)
+        ws = _lib.workspace.get(int(L.mm_ce2_ws_bytes()), logits.device)
+        check(L.mm_ce2_fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                           zero_bits, ptr(stats), ptr(ws), ws.numel(), stream()), "ce2_fwd")
+        ctx.save_for_backward(logits, labels0, weight0, labels1, weight1, stats)
+        ctx.args = (ld, split, ignore_index)
+        return stats[0], stats[2]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        L = _lib.lib()
+        logits, labels0, weight0, labels1, weight1, stats = ctx.saved_tensors
+        ld, split, ignore_index = ctx.args
+        N, C = logits.shape
+        d = torch.empty((N, C), dtype=F32, device=logits.device)
+        g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
+        check(L.mm_ce2_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                           ptr(stats), ptr(g), ptr(d), C, stream()), "ce2_bwd")
+        if ctx.in_dtype != F32:
+            d = d.to(ctx.in_dtype)
+        return d, None, None, None, None, None, None, None
+
+
+def cross_entropy_pair(pred, split, gt_head=None, gt_tail=None, weight_head=None, weight_tail=None, ignore_index=-100,
+                       zero_if_empty=(False, True)):
+    """``(loss_head, loss_tail)``: the cross entropy of rows ``[0, split)`` of ``pred`` [N, C] against ``gt_head`` and of rows
+    ``[split, N)`` against ``gt_tail`` - each ``cross_entropy``'s weighted mean over its own counted rows - from one pass over
+    ``pred`` per direction (the joined [source | target] step: supervised loss on the source rows, pseudo-label loss on the target
+    rows, ``train_kwargs["lambda_pl"]``).  ``pred`` may be a row-pitched view (``stride(1) == 1``).
+
+    ``gt_* = None``: that segment is unlabelled - loss 0, zero gradient rows.  ``split`` may be 0 or N.  Labels outside
+    ``[0, C)`` are skipped like ``ignore_index``.
+
+    ``zero_if_empty[s]``: a segment in which nothing is counted (every label ignored, or no rows) gives loss ``0.0`` and a zero
+    gradient.  This DEVIATES from ``F.cross_entropy`` (and from ``cross_entropy``), which return nan = 0/0: a target batch whose
+    pseudo labels were all refined away must not poison the step, so the tail's default is True; the head keeps torch's nan."""
+    if pred.dim() != 2:
+        raise ValueError("cross_entropy_pair: pred must be [N, C]")
+    N, split = int(pred.shape[0]), int(split)
+    if not 0 <= split <= N:
+        raise ValueError(f"cross_entropy_pair: split {split} outside [0, {N}]")
+
+    def labels(gt, n, which):
+        if gt is None:
+            return None
+        gt = gt.to(device=pred.device, dtype=torch.int64).contiguous()
+        if gt.dim() != 1 or gt.shape[0] != n:
+            raise ValueError(f"cross_entropy_pair: {which} has shape {tuple(gt.shape)}, its segment has {n} rows")
+        # an empty tensor has no address, and no address means "unlabelled" to the library: a labelled segment without rows
+        # (0/0 unless zero_if_empty) passes one label that no row reads
+        return gt if n else gt.new_full((1,), ignore_index)
+
+    gt_head, gt_tail = labels(gt_head, split, "gt_head"), labels(gt_tail, N - split, "gt_tail")
+    C = int(pred.shape[1])
+
+    def weights(w, which):
+        w = _device_weight(w, pred.device)
+        if w is not None and w.numel() != C:
+            raise ValueError(f"cross_entropy_pair: {which} has {w.numel()} entries for {C} classes")
+        return w
+
+    bits = (1 if zero_if_empty[0] else 0) | (2 if zero_if_empty[1] else 0)
+    return _CrossEntropyPairFn.apply(pred, split, gt_head, weights(weight_head, "weight_head"), gt_tail,
+                                     weights(weight_tail, "weight_tail"), int(ignore_index), bits)
 
 
 class _KLFn(torch.autograd.Function):

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib, domains
 from .ddp import GradAllReducer, ranks_share_a_gpu
-from .losses import Loss, cross_modal_loss
+from .losses import CrossEntropy, Loss, cross_entropy_pair, cross_modal_loss
 from .metrics import SegIoU
 
 
@@ -29,6 +29,20 @@ class TrainModel(nn.Module):
         self.loss = loss
         self.lambda_xm_src = train_kwargs.get("lambda_xm_src", 1.0)
         self.lambda_xm_trg = train_kwargs.get("lambda_xm_trg", 0.1)
+        # Self-training (the second round: pselab.export_pseudo_labels -> the loaders' ``pselab_paths=`` -> here): with
+        # ``lambda_pl`` > 0 each main head also learns from the pseudo labels of the TARGET batch, loss_2d += lambda_pl * pl2d and
+        # loss_3d += lambda_pl * pl3d, logged as ``{stage}/pl_loss_tgt_2d`` / ``_3d``.  pl* = unweighted cross entropy of the head's
+        # target rows, ignore_index -100 (a refined-away point), mean over the counted rows.  The class weights are left out on
+        # purpose: they describe the SOURCE label distribution.  A target batch whose pseudo labels are all -100 contributes loss 0
+        # and a zero gradient (losses.cross_entropy_pair), not torch's 0/0.  ``pseudo_labels``: "own" = the 2D head learns from
+        # ``pseudo_label_2d`` and the 3D head from ``pseudo_label_3d``; "ensemble" = both from ``pseudo_label_ensemble``.
+        # 0.0 (default): the step is exactly the step without the option - pseudo-label keys of the batch are ignored.
+        self.lambda_pl = float(train_kwargs.get("lambda_pl", 0.0))
+        if not self.lambda_pl >= 0.0:
+            raise ValueError(f"train_kwargs['lambda_pl'] must be >= 0, not {train_kwargs['lambda_pl']!r}")
+        self.pseudo_labels = train_kwargs.get("pseudo_labels", "own")
+        if self.pseudo_labels not in ("own", "ensemble"):
+            raise ValueError(f"train_kwargs['pseudo_labels'] must be 'own' or 'ensemble', not {self.pseudo_labels!r}")
         self.broadcast_buffers = bool(int(train_kwargs.get("broadcast_buffers", os.environ.get("MM_DDP_BROADCAST_BUFFERS", "1"))))  # torch DDP default (run.py:264-268)
         # One pass per network over [source scenes | target scenes] instead of one per domain: half the launches, twice
         # the rows per launch.  The batch-norm layers keep per-domain statistics (mm2d3d_amd/domains.py), so the
@@ -187,9 +201,35 @@ class TrainModel(nn.Module):
         return (self.joint_domains and self.training and src["img"].is_cuda and src["img"].shape[1:] == trg["img"].shape[1:]
                 and src["depth"].shape[1:] == trg["depth"].shape[1:])
 
+    def _pseudo_labels(self, trg):
+        """(labels for the 2D head, labels for the 3D head) of a target batch, checked on the host before anything is queued."""
+        keys = ("pseudo_label_ensemble",) * 2 if self.pseudo_labels == "ensemble" else ("pseudo_label_2d", "pseudo_label_3d")
+        n = int(trg["x"][0].shape[0])
+        out = []
+        for k in keys:
+            if k not in trg:
+                raise KeyError(f"lambda_pl > 0 but the target batch has no '{k}': build the target dataset with pselab_paths= "
+                               "(the file pselab.export_pseudo_labels writes)")
+            v = trg[k]
+            if k == "pseudo_label_3d" and isinstance(v, (list, tuple)) and len(v) == 0:
+                raise ValueError(f"the pseudo-label file has no 3D entries ('{k}' is empty): train with pseudo_labels=\"ensemble\"")
+            if not torch.is_tensor(v) or v.dim() != 1 or int(v.shape[0]) != n:
+                raise ValueError(f"'{k}' holds {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__} labels, the target batch "
+                                 f"has {n} point rows")
+            out.append(v)
+        return out
+
+    def _single_cross_entropy(self):
+        """(registry weight, class weights) if the "segmentation" target of the loss registry is one ``cross_entropy`` entry."""
+        sel = [(w, l) for w, t, l in self.loss._losses if t == "segmentation"]
+        if len(sel) == 1 and type(sel[0][1]) is CrossEntropy:
+            return sel[0][0], sel[0][1].other_args.get("weight")
+        return None
+
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
+        pseudo = self._pseudo_labels(trg) if self.lambda_pl > 0 else None
         if self._can_join(src, trg):
             pre = self._pipelined if self._pipelined is not None and self._matches(self._pipelined, batch) else None
             self._pipelined = None
@@ -257,8 +297,20 @@ class TrainModel(nn.Module):
                 else:
                     p3d, _, aux3d = self(both, model_name=n3d)
             l2d, a2d, l3d, a3d = p2d["seg_logit"], aux2d["seg_logit_avg"], p3d["seg_logit"], aux3d["seg_logit_point"]
-            seg2d = self.loss("segmentation", pred=l2d[:P], gt=src["seg_label"])
-            seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
+            single = self._single_cross_entropy() if pseudo is not None else None
+            if single is not None:
+                # one pass over each head's [source | target] logits: source labels with the entry's class weights, pseudo labels
+                # without; one backward launch writes the head's whole gradient
+                (rw, cw), gt = single, src["seg_label"]
+                seg2d, pl2d = cross_entropy_pair(l2d, P, gt, pseudo[0], weight_head=cw)
+                seg3d, pl3d = cross_entropy_pair(l3d, P, gt, pseudo[1], weight_head=cw)
+                seg2d, seg3d = rw * seg2d, rw * seg3d
+            else:
+                seg2d = self.loss("segmentation", pred=l2d[:P], gt=src["seg_label"])
+                seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
+                if pseudo is not None:
+                    pl2d = cross_entropy_pair(l2d, P, None, pseudo[0])[1]
+                    pl3d = cross_entropy_pair(l3d, P, None, pseudo[1])[1]
             xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
         else:
@@ -272,6 +324,9 @@ class TrainModel(nn.Module):
             p3d, _, aux3d = self(trg, model_name=n3d)
             xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
                                                aux3d["seg_logit_point"])
+            if pseudo is not None:
+                pl2d = cross_entropy_pair(p2d["seg_logit"], 0, None, pseudo[0])[1]
+                pl3d = cross_entropy_pair(p3d["seg_logit"], 0, None, pseudo[1])[1]
         self.last_logs = {
             f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
@@ -279,6 +334,10 @@ class TrainModel(nn.Module):
         }
         loss_2d = seg2d + self.lambda_xm_src * xs2d + self.lambda_xm_trg * xt2d
         loss_3d = seg3d + self.lambda_xm_src * xs3d + self.lambda_xm_trg * xt3d
+        if pseudo is not None:
+            self.last_logs[f"{stage}/pl_loss_tgt_2d"], self.last_logs[f"{stage}/pl_loss_tgt_3d"] = pl2d, pl3d
+            loss_2d = loss_2d + self.lambda_pl * pl2d
+            loss_3d = loss_3d + self.lambda_pl * pl3d
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
