@@ -19,7 +19,7 @@ All four share one per-sample pipeline here (the reference repeats it four times
 with every numpy RNG draw in the reference's order, so a seeded run picks the same crops / flips / rotations
 (tests/test_loader_golden.py compares with fixtures produced by the reference's own classes, tests/golden/loader_*.npz).
 ``gpu_batch(indices)`` runs the front end on the host and hands the per-point work of the whole batch to the HIP chain
-(mm2d3d_amd/dataprep.prepare_batch -> csrc/dataprep.hip); it returns the same batch dict with device tensors.
+(mm2d3d_amd/dataprep.py -> csrc/dataprep.hip); it returns the same batch dict with device tensors.
 ``gpu_batch(indices, image="gpu")`` also moves the image half (crop, resize, colour jitter, float conversion, fliplr,
 normalisation) to the GPU (mm2d3d_amd/imageprep.py -> csrc/imageprep.hip); only the decode stays on the host.
 
@@ -36,11 +36,12 @@ import json
 import os
 import pickle
 from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import imageprep, label_maps, projection
+from . import dataprep, imageprep, label_maps, projection
 from .color_jitter import ColorJitter
 from .voxelize import augment_and_scale_3d, voxelize_points
 
@@ -261,18 +262,43 @@ class _Scenes:
         Float64 points (VirtualKITTI with ``camera_coords``: the reference's camera-frame points are float64) are voxelised
         with numpy's float64 arithmetic by the fp64 kernels; the batch's ``points`` and ``min_values`` are then float64,
         as in the host path."""
-        from . import dataprep
-
         if image not in ("host", "gpu"):
             raise ValueError(f"gpu_batch: image must be 'host' or 'gpu', not {image!r}")
-        on_gpu = image == "gpu"
-        scenes, intrinsics, works, jitter, flips = [], [], [], [], []
+        d = self._draw_scenes(indices, image == "gpu")
+        for sc, draws in zip(d.scenes, zip(d.flips, d.rots, d.us)):
+            sc["draws"] = draws
+        img, checks = None, []
+        if image == "gpu":
+            lut = imageprep.lut(self._to_float, self._normalise)
+            img = dataprep.prepare_images([w.image for w in d.works], d.jitter, d.flips, [lut] * len(d.works), device, decode_threads,
+                                          timing, checks)
+        t, rots, flips = dataprep._prepare(d.scenes, self.scale, self.full_scale, {}, 0.0, want_seg2d, torch.device(device),
+                                           self.use_rgb, img)
+        for check in checks:  # the JPEG decoder's status words, after _prepare's own read-back has waited for the stream
+            check()
+        t["points"] = torch.cat(dataprep._per_scene(t["points"], t["counts"]), 0)
+        if t["seg2d"] is not None:
+            t["seg2d"] = t["seg2d"].float()
+        kept_rows = t["keep"].cpu().numpy() if self.output_orig else None
+        pselab = None
+        if self.has_pselab and self.pselab_data is not None:
+            keep = t["keep"].cpu().numpy()  # rows of the concatenated post-crop scenes that passed the range mask
+            pselab = {key: torch.from_numpy(rows[keep]).to(device) for key, rows in self._pselab_rows(indices, d.works).items()}
+        return dataprep.finish_batch(t, rots, flips, d.intrinsics, d.works if self.output_orig else None, kept_rows, pselab)
+
+    def _draw_scenes(self, indices, on_gpu):
+        """The scene loop of both GPU loaders (``gpu_batch``, :class:`pipeline.PendingBatch`): per scene the front end, the
+        colour-jitter draw (``on_gpu``: drawn, applied by csrc/imageprep.hip; else applied here with the float conversion and
+        the normalisation), the fliplr draw and the 3D draws, in the RNG order of ``__getitem__``.  ``on_gpu`` also makes the
+        front end record the image work (:class:`imageprep.ImagePlan`, in ``works[i].image``) without doing it.  Returns
+        lists per scene and ``HW``; ``scenes`` are what :func:`dataprep.prepare_batch` reads, without "img" when ``on_gpu``."""
+        d = SimpleNamespace(scenes=[], works=[], intrinsics=[], flips=[], rots=[], us=[], jitter=[], HW=None)
         self._plan_images = on_gpu
         try:
             for i in indices:
                 w = self._front(i)
                 if on_gpu:
-                    jitter.append(self.color_jitter.draw() if self.color_jitter is not None else None)  # where _float_image draws
+                    d.jitter.append(self.color_jitter.draw() if self.color_jitter is not None else None)  # where _float_image draws
                     W, H = w.image.size
                 else:
                     arr = self._float_image(w.image)
@@ -287,58 +313,31 @@ class _Scenes:
                 if w.label is None:
                     raise ValueError("gpu_batch needs labelled scenes (the 2D label map and seg_label are part of the batch)")
                 # the kernel truncates float32 pixel coordinates; truncating here first keeps float64 inputs (VirtualKITTI) exact
-                sc = dict(points=np.ascontiguousarray(w.points), points_img=np.trunc(w.pimg), depth=w.cam[:, 2], seg_label=w.label,
-                          draws=(flip, rot, u))
+                sc = dict(points=np.ascontiguousarray(w.points), points_img=np.trunc(w.pimg), depth=w.cam[:, 2], seg_label=w.label)
                 if not on_gpu:
                     sc["img"] = np.ascontiguousarray(np.moveaxis(self._normalise(arr), -1, 0))  # commutes with the flip the GPU applies
-                scenes.append(sc)
-                intrinsics.append(intr)
-                works.append(w)
-                flips.append(flip)
+                d.scenes.append(sc)
+                d.works.append(w)
+                d.intrinsics.append(intr)
+                d.flips.append(flip)
+                d.rots.append(rot)
+                d.us.append(u)
+                d.HW = (H, W)
         finally:
             self._plan_images = False
-        img, checks = None, []
-        if on_gpu:
-            lut = imageprep.lut(self._to_float, self._normalise)
-            img = dataprep.prepare_images([w.image for w in works], jitter, flips, [lut] * len(works), device, decode_threads, timing,
-                                          checks)
-        batch = dataprep.prepare_batch(scenes, self.scale, self.full_scale, None, 0.0, want_seg2d, device, use_rgb=self.use_rgb, img=img)
-        for check in checks:  # the JPEG decoder's status words, after prepare_batch's own read-back has waited for the stream
-            check()
-        batch["intrinsics"] = torch.from_numpy(np.stack(intrinsics))
-        batch["points"] = torch.cat(batch["points"], 0) if batch["points"] else batch["points"]
-        batch["coords"] = batch["x"][0][:, :3]
-        batch["rotation_matrices"] = torch.from_numpy(np.stack(batch["rotation_matrices"]))
-        if "seg_labels_2d" in batch:
-            batch["seg_labels_2d"] = batch["seg_labels_2d"].float()
-        if self.output_orig:  # labels before the range mask and the mask itself, per scene
-            kept = batch["keep"].cpu().numpy()
-            off = np.concatenate([[0], np.cumsum([len(w.points) for w in works])])
-            masks = []
-            for b, w in enumerate(works):
-                m = np.zeros(len(w.points), dtype=bool)
-                m[kept[(kept >= off[b]) & (kept < off[b + 1])] - off[b]] = True
-                masks.append(m)
-            batch["orig_seg_label"] = [w.label for w in works]
-            batch["orig_points_idx"] = masks
-        if self.has_pselab and self.pselab_data is not None:
-            keep = batch["keep"].cpu().numpy()  # rows of the concatenated post-crop scenes that passed the range mask
+        return d
 
-            def cat(key):
-                return np.concatenate([np.asarray(self.pselab_data[i][key])[w.keep] for i, w in zip(indices, works)])[keep]
-
-            batch["pseudo_label_2d"] = torch.from_numpy(cat("pseudo_label_2d")).to(device)
-            batch["pseudo_label_ensemble"] = torch.from_numpy(cat("pseudo_label_ensemble")).to(device)
-            has3d = self.pselab_data[indices[0]]["pseudo_label_3d"] is not None
-            batch["pseudo_label_3d"] = torch.from_numpy(cat("pseudo_label_3d")).to(device) if has3d else []
-        return batch
+    def _pselab_rows(self, indices, works):
+        """The pseudo-label arrays the dataset has, by key: the rows of the batch's concatenated post-crop scenes."""
+        first = self.pselab_data[indices[0]]
+        return {key: np.concatenate([np.asarray(self.pselab_data[i][key])[w.keep] for i, w in zip(indices, works)])
+                for key in dataprep.PSELAB_KEYS if first[key] is not None}
 
     def begin_gpu_batch(self, indices, device="cuda", want_seg2d=False, image="host", decode_threads=4, queue=True):
-        """The batch of ``gpu_batch(indices, ...)`` without a host wait on the way (mm2d3d_amd/pipeline.py): runs the host
-        phase here (front ends, draws in ``gpu_batch``'s RNG order, file reads, decodes, tables, all packed into pinned staging
-        blocks), then - unless ``queue=False`` - enqueues uploads, kernels and one read-back on the current stream.  Returns the
-        :class:`pipeline.PendingBatch`: ``queue()`` (idempotent), ``result()`` -> the batch dict, bit-identical to
-        ``gpu_batch``'s.  :class:`pipeline.BatchStream` keeps such batches in flight ahead of ``fit_step``."""
+        """The batch of ``gpu_batch(indices, ...)``, bit for bit, without a host wait on the way (mm2d3d_amd/pipeline.py): runs
+        the host phase here, then - unless ``queue=False`` - enqueues uploads, kernels and one read-back on the current stream.
+        Returns the :class:`pipeline.PendingBatch`: ``queue()`` (idempotent), ``result()`` -> the batch dict.
+        :class:`pipeline.BatchStream` keeps such batches in flight ahead of ``fit_step``."""
         from .pipeline import PendingBatch
 
         pending = PendingBatch(self, indices, device, want_seg2d, image, decode_threads)

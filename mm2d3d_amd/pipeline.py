@@ -2,16 +2,16 @@
 
 ``ds.gpu_batch(indices)`` is written for an idle GPU: it uploads from pageable memory and reads the kept counts back before it
 sizes its outputs, and each of those waits for everything queued on the stream - inside a training loop, for the whole previous
-step.  The same batch is produced here without a host wait:
+step.  The same batch is produced here without a host wait, from the same parts (mm2d3d_amd/dataprep.py):
 
-    host phase     no stream call, any thread    the scene loop of ``gpu_batch`` (``_front``, jitter, flip and 3D draws in the
-                                                 same RNG order), file reads, JPEG headers, PIL decodes, the kernels' tables;
-                                                 every host array packed into two pinned staging blocks (small arrays, image bytes)
-    queue phase    caller's thread and stream    two ``non_blocking`` uploads (the device arrays are views into them), the kernel
-                                                 chain of ``gpu_batch`` with the collect step in its device-count form, outputs
-                                                 allocated at the batch's point count, ONE read-back into pinned memory + an event
-    result phase   caller's thread               waits for that event, raises the loader's errors, narrows the outputs to the kept
-                                                 count (row-prefix views), builds the batch dict of ``gpu_batch``
+    host phase     no stream call, any thread    ``ds._draw_scenes`` (the scene loop, its RNG draws), ``scene_arrays``, the JPEG
+                                                 read helpers, PIL decodes, the kernels' tables; every host array packed into
+                                                 two pinned staging blocks (small arrays, image bytes)
+    queue phase    caller's thread and stream    two ``non_blocking`` uploads (the device arrays are views into them), the
+                                                 ``_launch_*`` chain with ``collect_points_dev``, outputs allocated at the
+                                                 batch's point count, ONE read-back into pinned memory + an event
+    result phase   caller's thread               waits for that event, ``check_projection`` / ``check_jpeg_status``, narrows the
+                                                 outputs to the kept count (row-prefix views), ``finish_batch``
 
 ``ds.begin_gpu_batch(indices)`` returns the :class:`PendingBatch`; :class:`BatchStream` runs the host phases on one worker thread
 and keeps ``depth`` batches queued ahead of the one it yields.  Everything is queued on the current stream: the single-launch
@@ -20,13 +20,15 @@ batch norms of the training step need the CUs they expect, so no side stream is 
 from __future__ import annotations
 
 import collections
-import os
 import queue as _queue
 import threading
 import time
 
 import numpy as np
 import torch
+
+from . import dataprep, imageprep, jpeg
+from .dataprep import collect_points_dev  # noqa: F401  (also importable from here)
 
 ALIGN = 16  # bytes: every sub-array of a staging block starts at a multiple (int64 / float64 views need 8)
 
@@ -145,8 +147,6 @@ _TORCH_DTYPE = {np.dtype(k): v for k, v in {
     np.uint8: torch.uint8, np.int8: torch.int8, np.int16: torch.int16, np.int32: torch.int32, np.int64: torch.int64,
     np.float32: torch.float32, np.float64: torch.float64, np.bool_: torch.bool}.items()}
 
-_PSELAB_KEYS = ("pseudo_label_2d", "pseudo_label_ensemble", "pseudo_label_3d")
-
 
 # ---------------------------------------------------------------------------------------------------- one batch
 class PendingBatch:
@@ -174,83 +174,33 @@ class PendingBatch:
 
     # ------------------------------------------------------------------ host phase
     def _host(self):
-        from . import dataprep, imageprep
-
-        ds, on_gpu = self.ds, self.on_gpu
-        scenes, works, jitter = [], [], []
-        self.intrinsics, self.flips, self.rots = [], [], []
-        us = []
-        ds._plan_images = on_gpu
-        try:
-            for i in self.indices:  # the scene loop of _Scenes.gpu_batch, draw for draw
-                w = ds._front(i)
-                if on_gpu:
-                    jitter.append(ds.color_jitter.draw() if ds.color_jitter is not None else None)
-                    W, H = w.image.size
-                else:
-                    arr = ds._float_image(w.image)
-                    H, W = arr.shape[:2]
-                flip = bool(np.random.rand() < ds.fliplr)
-                rot, u = dataprep.augmentation_draws(**ds._augmentation())
-                intr = w.intr
-                if flip:
-                    intr = intr.copy()
-                    intr[0, 2] = W - intr[0, 2]
-                    intr[1, 2] = H - intr[0, 1]
-                if w.label is None:
-                    raise ValueError("gpu_batch needs labelled scenes (the 2D label map and seg_label are part of the batch)")
-                sc = dict(points=np.ascontiguousarray(w.points), points_img=np.trunc(w.pimg), depth=w.cam[:, 2], seg_label=w.label)
-                if not on_gpu:
-                    sc["img"] = np.ascontiguousarray(np.moveaxis(ds._normalise(arr), -1, 0))
-                scenes.append(sc)
-                works.append(w)
-                self.intrinsics.append(intr)
-                self.flips.append(flip)
-                self.rots.append(rot)
-                us.append(u)
-        finally:
-            ds._plan_images = False
-        self.works = works
+        ds, sm = self.ds, self.small
+        drawn = ds._draw_scenes(self.indices, self.on_gpu)
+        scenes, self.works, self.intrinsics, self.flips, self.rots, self.HW = [getattr(drawn, k) for k in (
+            "scenes", "works", "intrinsics", "flips", "rots", "HW")]
         B = self.B = len(scenes)
         if B == 0:
             raise ValueError("begin_gpu_batch: no scenes")
-        self.HW = (H, W)
-        lengths = [int(s["points"].shape[0]) for s in scenes]
-        self.off = np.zeros(B + 1, np.int32)
-        np.cumsum(lengths, out=self.off[1:])
+        self.off = dataprep.scene_offsets([int(s["points"].shape[0]) for s in scenes])
         self.n = int(self.off[B])
-        self.transl = any(u is not None for u in us)
-        if self.transl and not all(u is not None for u in us):
-            raise ValueError("voxelize_batch: translation must be drawn for every scene of the batch or for none")
-        f64 = [np.asarray(s["points"]).dtype == np.float64 for s in scenes]
-        if any(f64) and not all(f64):
-            raise ValueError("prepare_batch: the scenes of one batch must all have float64 points or none (the reference voxelises "
-                             "float64 and float32 points with different arithmetic)")
-        self.f64 = any(f64)
-        cat = lambda key, dt: np.concatenate([np.asarray(s[key]) for s in scenes], 0).astype(dt)
-        sm = self.small
-        sm.add("off", self.off)
-        sm.add("rot", np.stack([np.asarray(r, np.float32).reshape(9) for r in self.rots]))
-        sm.add("u", np.stack([np.asarray(u if u is not None else np.zeros(3), np.float64) for u in us]))
-        sm.add("flip", np.array([1 if f else 0 for f in self.flips], np.uint8))
-        sm.add("points", cat("points", np.float64 if self.f64 else np.float32).reshape(self.n, 3))
-        sm.add("pimg", cat("points_img", np.float32).reshape(self.n, 2))
-        sm.add("depth", cat("depth", np.float32))
-        sm.add("labels", cat("seg_label", np.int64))
+        rot, u, self.transl = dataprep.draw_tables(self.rots, drawn.us)
+        arrays = tuple(dataprep.scene_arrays(scenes))
+        self.f64 = arrays[0].dtype == np.float64
+        flip = np.array([1 if f else 0 for f in self.flips], np.uint8)
+        for name, array in zip(("off", "rot", "u", "flip", "points", "pimg", "depth", "labels"), (self.off, rot, u, flip) + arrays):
+            sm.add(name, array)
         self.pselab = []
         if ds.has_pselab and ds.pselab_data is not None:
-            for key in _PSELAB_KEYS:
-                if ds.pselab_data[self.indices[0]][key] is None:
-                    continue
-                rows = np.concatenate([np.asarray(ds.pselab_data[i][key])[w.keep] for i, w in zip(self.indices, works)])
+            for key, rows in ds._pselab_rows(self.indices, self.works).items():
                 if rows.shape != (self.n,):
                     raise AssertionError("pseudo labels and points of a batch have different lengths")
                 self.pselab.append(key)
                 sm.add(key, rows)
             if len({sm.layout[k][1] for k in self.pselab}) > 1:
                 raise TypeError("begin_gpu_batch: the pseudo-label arrays of a dataset must share one dtype")
-        if on_gpu:
-            self._host_images([w.image for w in works], jitter, imageprep.lut(ds._to_float, ds._normalise))
+        self.gpu_idx, self.jpeg_paths = [], []
+        if self.on_gpu:
+            self._host_images([w.image for w in self.works], drawn.jitter, imageprep.lut(ds._to_float, ds._normalise))
         else:
             self.images.add("img", np.stack([s["img"] for s in scenes]).astype(np.float32))
             self.images.seal()
@@ -258,40 +208,23 @@ class PendingBatch:
         self._state = "hosted"
 
     def _host_images(self, plans, jitter, lut):
-        """The host half of ``dataprep.prepare_images``: files, headers, decodes and tables; nothing is launched."""
-        from . import dataprep, imageprep, jpeg
-
+        """The host half of ``dataprep.prepare_images`` into the staging blocks; nothing is launched."""
         B, sm, im = self.B, self.small, self.images
-        sizes = [p.image.size[0] * p.image.size[1] * 3 for p in plans]
+        sizes = self.sizes = dataprep.source_sizes(plans)
         self.src_bytes = int(sum(sizes))
-        src_offs = dataprep.source_offsets(plans)
-        self.gpu_idx, headers, files, data_offs = [], [None] * B, None, None
+        src_offs = self.src_offs = dataprep.source_offsets(plans)
+        headers = [None] * B
         if dataprep.GPU_JPEG:
-            paths = [jpeg.jpeg_file(p.image) for p in plans]
-            fsz = [os.path.getsize(f) if f is not None else 0 for f in paths]
-            data_offs = np.concatenate([[0], np.cumsum(fsz)]).astype(np.int64)
+            paths, data_offs = dataprep.jpeg_files(plans)
             files = np.empty(max(int(data_offs[-1]), 1), np.uint8)
-            for i, f in enumerate(paths):
-                if f is None:
-                    continue
-                buf = files[data_offs[i] : data_offs[i + 1]]
-                jpeg.read_into(f, buf)
-                try:
-                    headers[i] = jpeg.parse(buf, f)
-                except ValueError as e:  # PIL decides on the host, as in read_jpegs
-                    headers[i] = jpeg.JpegHeader()
-                    headers[i].reason = f"header: {e}"
-            self.gpu_idx = [i for i, h in enumerate(headers) if h is not None and h.reason is None]
-        on_gpu = set(self.gpu_idx)
-        self.host_idx = [i for i in range(B) if i not in on_gpu]
+            headers = dataprep.read_jpeg_files(paths, data_offs, files)
+        self.gpu_idx, self.host_idx = dataprep.split_decoders(headers)
         self.jpeg_paths = [dataprep.jpeg_path(plans[i]) for i in self.gpu_idx]
         if self.gpu_idx:
-            self.data_bytes = int(files.size)
-            im.reserve("jpeg", np.uint8, (self.data_bytes,))  # first: at the block's own (allocator) alignment
-            desc, huff, qt, self.jpeg_totals = jpeg.build_tables([headers[i] for i in self.gpu_idx], [data_offs[i] for i in self.gpu_idx],
-                                                                 [src_offs[i] for i in self.gpu_idx])
-            self.jpeg_desc = desc
-            sm.add("jpeg_desc", desc)
+            im.reserve("jpeg", np.uint8, (files.size,))  # first: at the block's own (allocator) alignment
+            self.jpeg_desc, huff, qt, self.jpeg_totals = jpeg.build_tables(
+                [headers[i] for i in self.gpu_idx], [data_offs[i] for i in self.gpu_idx], [src_offs[i] for i in self.gpu_idx])
+            sm.add("jpeg_desc", self.jpeg_desc)
             sm.add("jpeg_huff", huff)
             sm.add("jpeg_qt", qt)
         hplans = [plans[i] for i in self.host_idx]
@@ -301,13 +234,10 @@ class PendingBatch:
         if self.gpu_idx:
             im.host("jpeg")[...] = files
         self.host_offs = imageprep.decode_into(hplans, im.host("decoded"), self.decode_threads) if hplans else []
-        self.sizes, self.src_offs = sizes, src_offs
-        desc, coef, factors, luts, self.tmp_bytes = imageprep.build_tables(plans, jitter, self.flips, [lut] * B, src_offs)
-        self.img_desc, self.coef_size = desc, int(coef.size)
-        sm.add("img_desc", desc)
-        sm.add("img_coef", coef)
-        sm.add("img_fac", factors)
-        sm.add("img_lut", luts)
+        *tables, self.tmp_bytes = imageprep.build_tables(plans, jitter, self.flips, [lut] * B, src_offs)
+        self.img_desc = tables[0]
+        for name, array in zip(("img_desc", "img_coef", "img_fac", "img_lut"), tables):
+            sm.add(name, array)
 
     def cancel(self):
         """Gives the staging blocks back without queuing anything (a batch that is dropped after its host phase)."""
@@ -323,10 +253,6 @@ class PendingBatch:
             if self._state in ("queued", "done"):
                 return self
             raise RuntimeError(f"PendingBatch.queue: the batch is {self._state}")
-        from . import _lib
-        from ._lib import check, ptr, stream
-
-        L = _lib.lib()
         dev = torch.device(self.device)
         B, n, (H, W), sm, im = self.B, self.n, self.HW, self.small, self.images
         STAGING.reclaim()
@@ -342,8 +268,7 @@ class PendingBatch:
         self._state = "queued"
         d = lambda name: sm.device(sm_d, name)
         # the read-back block: kept counts [B+1] | projection error word | JPEG status words | keep rows (output_orig)
-        nj = len(self.gpu_idx) if self.on_gpu else 0
-        keep_host = bool(self.ds.output_orig)
+        nj, keep_host = len(self.gpu_idx), bool(self.ds.output_orig)
         nk = max(n, 1)
         rb = torch.empty(B + 2 + nj + (nk if keep_host else 0), dtype=torch.int32, device=dev)
         counts, err, status = rb[: B + 1], rb[B + 1 : B + 2], rb[B + 2 : B + 2 + nj]
@@ -353,12 +278,8 @@ class PendingBatch:
         if self.on_gpu:
             if self.gpu_idx:
                 src = torch.empty(max(self.src_bytes, 1), dtype=torch.uint8, device=dev)
-                n_iv, n_sub, n_blk, n_plane = self.jpeg_totals
-                ws = _lib.workspace.get(int(L.mm_jpeg_ws_bytes(nj, self.data_bytes, n_iv, n_sub, n_blk, n_plane)), dev, "jpeg")
-                huff, qt = d("jpeg_huff"), d("jpeg_qt")
-                check(L.mm_jpeg_decode(ptr(im.device(im_d, "jpeg")), self.data_bytes, ptr(d("jpeg_desc")), self.jpeg_desc.ctypes.data, nj,
-                                       ptr(huff), huff.shape[0], ptr(qt), qt.shape[0], ptr(src), src.numel(), ptr(status), ptr(ws),
-                                       ws.numel(), stream()), "jpeg_decode")
+                dataprep._launch_jpeg_decode(im.device(im_d, "jpeg"), d("jpeg_desc"), self.jpeg_desc, d("jpeg_huff"), d("jpeg_qt"),
+                                             self.jpeg_totals, src, status)
                 if self.host_idx:
                     dec = im.device(im_d, "decoded")
                     for j, i in enumerate(self.host_idx):
@@ -370,31 +291,26 @@ class PendingBatch:
             mid = torch.empty(B * H * W * 3, dtype=torch.uint8, device=dev)
             sums = torch.empty(B, dtype=torch.int64, device=dev)
             img = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-            check(L.mm_image_prepare(ptr(src), self.src_bytes, ptr(d("img_desc")), self.img_desc.ctypes.data, B, H, W, ptr(d("img_coef")),
-                                     self.coef_size, ptr(d("img_fac")), ptr(d("img_lut")), ptr(tmp), tmp.numel(), ptr(mid), ptr(sums),
-                                     ptr(img), stream()), "image_prepare")
+            dataprep._launch_image_prepare(src, self.src_bytes, d("img_desc"), self.img_desc, d("img_coef"), d("img_fac"), d("img_lut"),
+                                           tmp, mid, sums, img)
         else:
             img = im.device(im_d, "img")
             if any(self.flips):
                 img = torch.stack([t.flip(-1) if f else t for t, f in zip(img, self.flips)])
         C = img.shape[1]
-        # ---- voxelisation and projection: the kernels of prepare_batch, unchanged
+        # ---- voxelisation and projection
         pts, off_d, labels = d("points"), d("off"), d("labels")
         pdt = pts.dtype
         locs = torch.empty((nk, 4), dtype=torch.int64, device=dev)
         minv = torch.empty((B, 3), dtype=pdt, device=dev)
         offset = torch.empty((B, 3), dtype=torch.float64, device=dev)
-        ws_bytes, run = (L.mm_voxelize_ws_bytes_f64, L.mm_voxelize_batch_f64) if self.f64 else (L.mm_voxelize_ws_bytes, L.mm_voxelize_batch)
-        ws = _lib.workspace.get(int(ws_bytes(n, B)), dev)
-        check(run(ptr(pts), ptr(off_d), self.off.ctypes.data, B, ptr(d("rot")), ptr(d("u")), 1 if self.transl else 0, float(self.ds.scale),
-                  int(self.ds.full_scale), ptr(locs), ptr(keep), ptr(counts), ptr(minv), ptr(offset), ptr(ws), ws.numel(), stream()),
-              "voxelize_batch")
+        dataprep._launch_voxelize(pts, off_d, self.off, d("rot"), d("u"), self.transl, self.ds.scale, self.ds.full_scale, locs, keep,
+                                  counts, minv, offset)
         idx_all = torch.empty((nk, 2), dtype=torch.int64, device=dev)
         depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
         seg2d = torch.empty((B, H, W), dtype=torch.float64, device=dev) if self.want_seg2d else None
         winner = torch.empty(B * H * W, dtype=torch.int32, device=dev)
-        check(L.mm_project_batch(ptr(d("pimg")), ptr(d("depth")), ptr(labels), ptr(off_d), self.off.ctypes.data, B, H, W, ptr(d("flip")),
-                                 ptr(idx_all), ptr(depth), ptr(seg2d), ptr(winner), ptr(err), stream()), "project_batch")
+        dataprep._launch_project(d("pimg"), d("depth"), labels, off_d, self.off, d("flip"), idx_all, depth, seg2d, winner, err)
         # ---- collect: launched over the point count, the kept total is read on the device
         idx = torch.empty((nk, 2), dtype=torch.int64, device=dev)
         lab = torch.empty(nk, dtype=torch.int64, device=dev)
@@ -402,9 +318,8 @@ class PendingBatch:
         pkept = torch.empty((nk, 3), dtype=pdt, device=dev)
         pl_in = [d(k) for k in self.pselab]
         pl_out = [torch.empty(nk, dtype=t.dtype, device=dev) for t in pl_in]
-        out = collect_points_dev(keep, counts, B, n, locs, idx_all, labels, img.contiguous() if feats is not None else None, H, W, pts, idx,
-                                 lab, feats, pkept, pl_in, pl_out)
-        del out
+        collect_points_dev(keep, counts, B, n, locs, idx_all, labels, img.contiguous() if feats is not None else None, H, W, pts, idx, lab,
+                           feats, pkept, pl_in, pl_out)
         if not self.ds.use_rgb:
             feats = torch.ones((n, 1), dtype=torch.float32, device=dev)
         if seg2d is not None:
@@ -418,9 +333,9 @@ class PendingBatch:
             self._ev[1].record()
         self.event = torch.cuda.Event()
         self.event.record()
-        self._dev = dict(locs=locs, keep=keep, idx=idx, lab=lab, feats=feats, pkept=pkept, img=img, depth=depth, seg2d=seg2d, minv=minv,
-                         offset=offset, pselab=pl_out, rb=rb, blocks=(sm_d, im_d))
-        self._rb_layout = (nj, keep_host)
+        self._dev = dict(locs=locs, feats=feats, seg_label=lab, img=img, depth=depth, seg2d=seg2d, img_indices=idx, points=pkept,
+                         min_values=minv, offsets=offset, keep=keep)
+        self._held = (pl_out, rb, sm_d, im_d)  # what the queued kernels read and write stays allocated until result()
         return self
 
     # ------------------------------------------------------------------ result phase
@@ -440,89 +355,22 @@ class PendingBatch:
         self._rb_buf = self._rb_host = None
         if self.timing:
             self.gpu_ms = self._ev[0].elapsed_time(self._ev[1])
-        B, d = self.B, self._dev
-        nj, keep_host = self._rb_layout
-        counts, kept = r[:B].tolist(), int(r[B])
+        B, t = self.B, self._dev
+        nj, keep_host, kept = len(self.gpu_idx), bool(self.ds.output_orig), int(r[B])
         self._state = "failed"
-        if int(r[B + 1]) != 0:
-            raise AssertionError("projected point outside the image (nuscenes_dataloader.py:279-283)")
-        bad = [(p, s) for p, s in zip(self.jpeg_paths if nj else [], r[B + 2 : B + 2 + nj].tolist()) if s]
-        if bad:
-            raise RuntimeError("JPEG decode failed (entropy-coded data; include/mm2d3d.h MM_JPG_ST_* bits): " +
-                               ", ".join(f"{p} (status {s})" for p, s in bad))
-        bounds = np.concatenate([[0], np.cumsum(counts)])
-        locs, idx, pkept = d["locs"][:kept], d["idx"][:kept], d["pkept"][:kept]
-        batch = {
-            "x": [locs, d["feats"][:kept] if self.ds.use_rgb else d["feats"]],
-            "seg_label": d["lab"][:kept],
-            "img": d["img"],
-            "depth": d["depth"],
-            "img_indices": [idx[bounds[i] : bounds[i + 1]] for i in range(B)],
-            "points": pkept,
-            "min_values": d["minv"], "offsets": d["offset"], "rotation_matrices": torch.from_numpy(np.stack(self.rots)),
-            "fliplr": list(self.flips),
-            "keep": d["keep"][:kept],
-        }
-        if d["seg2d"] is not None:
-            batch["seg_labels_2d"] = d["seg2d"]
-        batch["intrinsics"] = torch.from_numpy(np.stack(self.intrinsics))
-        batch["coords"] = locs[:, :3]
-        if keep_host:
-            rows = r[B + 2 + nj : B + 2 + nj + kept]
-            masks = []
-            for b, w in enumerate(self.works):
-                m = np.zeros(len(w.points), dtype=bool)
-                m[rows[(rows >= self.off[b]) & (rows < self.off[b + 1])] - self.off[b]] = True
-                masks.append(m)
-            batch["orig_seg_label"] = [w.label for w in self.works]
-            batch["orig_points_idx"] = masks
+        dataprep.check_projection(r[B + 1])
+        dataprep.check_jpeg_status(self.jpeg_paths, r[B + 2 : B + 2 + nj].tolist())
+        for key in ("locs", "seg_label", "img_indices", "points", "keep") + (("feats",) if self.ds.use_rgb else ()):
+            t[key] = t[key][:kept]  # outputs were allocated at the batch's point count
+        pselab = None
         if self.ds.has_pselab and self.ds.pselab_data is not None:
-            got = dict(zip(self.pselab, d["pselab"]))
-            for key in _PSELAB_KEYS:
-                batch[key] = got[key][:kept] if key in got else []
+            pselab = {key: rows[:kept] for key, rows in zip(self.pselab, self._held[0])}
+        batch = dataprep.finish_batch(dict(t, counts=r[:B].tolist()), self.rots, self.flips, self.intrinsics,
+                                      self.works if keep_host else None, r[B + 2 + nj : B + 2 + nj + kept], pselab)
+        self._held = None
         self._dev = self.works = None
         self._result, self._state = batch, "done"
         return batch
-
-
-def collect_points_dev(keep, counts, B, n_total, locs, idx_all, labels, image, H, W, points, idx_out, lab_out, feats_out, points_out,
-                       extra_in=(), extra_out=()):
-    """``mm_collect_points_dev`` / ``_f64_dev`` (csrc/dataprep.hip): the collect step of ``prepare_batch`` launched over
-    ``n_total`` rows with the kept total read from ``counts[B]`` on the device; ``extra_in`` -> ``extra_out``: up to three
-    per-point arrays of one dtype gathered by ``keep`` in the same launch.  Any of labels / feats / points outputs may be None."""
-    import ctypes
-
-    from . import _lib
-
-    L = _lib.lib()
-    _lib.require_cuda(keep, "keep")
-    if points.dtype not in (torch.float32, torch.float64):
-        raise TypeError("collect_points_dev: points must be float32 or float64")
-    if len(extra_in) != len(extra_out) or len(extra_in) > 3:
-        raise ValueError("collect_points_dev: at most three extra arrays, one output each")
-    for a, b in zip(extra_in, extra_out):
-        if a.dtype != b.dtype or a.dtype != extra_in[0].dtype or a.numel() < n_total or b.numel() < n_total or not (
-                a.is_contiguous() and b.is_contiguous()):
-            raise ValueError("collect_points_dev: extra arrays must be contiguous, of one dtype and hold n_total elements")
-    for t, rows in ((keep, 1), (locs, 4), (idx_all, 2), (idx_out, 2), (lab_out, 1), (points, 3), (points_out, 3)):
-        if t is not None and t.numel() < n_total * rows:
-            raise ValueError("collect_points_dev: an array is shorter than n_total rows")
-    if counts.numel() < B + 1:
-        raise ValueError("collect_points_dev: counts holds B + 1 words")
-    C = 0
-    if feats_out is not None:
-        C = int(image.shape[1])
-        if feats_out.numel() < n_total * C:
-            raise ValueError("collect_points_dev: feats_out is shorter than n_total rows")
-    ne = len(extra_in)
-    arr = ctypes.c_void_p * max(ne, 1)
-    ein, eout = arr(*[t.data_ptr() for t in extra_in]), arr(*[t.data_ptr() for t in extra_out])
-    fn = L.mm_collect_points_f64_dev if points.dtype == torch.float64 else L.mm_collect_points_dev
-    _lib.check(fn(_lib.ptr(keep), _lib.ptr(counts), int(B), int(n_total), _lib.ptr(locs), _lib.ptr(idx_all), _lib.ptr(labels), _lib.ptr(image),
-                  C, int(H), int(W), _lib.ptr(points), _lib.ptr(idx_out), _lib.ptr(lab_out), _lib.ptr(feats_out), _lib.ptr(points_out),
-                  ctypes.cast(ein, ctypes.c_void_p), ctypes.cast(eout, ctypes.c_void_p), ne, extra_in[0].element_size() if ne else 0,
-                  _lib.stream()), "collect_points_dev")
-    return idx_out
 
 
 # ---------------------------------------------------------------------------------------------------- the stream

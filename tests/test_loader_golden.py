@@ -122,16 +122,17 @@ def test_bottom_crop_takes_the_image_bottom_and_keeps_only_points_inside():
     assert len(s["pseudo_label_2d"]) == len(s["coords"])
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", GPU_CASES)
-def test_gpu_batch_equals_the_reference_batch(name):
-    """The same index list through ``gpu_batch`` (front end on the host, per-point work in csrc/dataprep.hip): every tensor
-    of the reference's collated batch, bit for bit."""
+def _reference_fixture(name):
+    """(fixture, dataset, constructor keywords, index list) with numpy's and torch's RNGs under the fixture's seed."""
     z = np.load(os.path.join(G, f"loader_{name}.npz"))
     ds, kw = _dataset(name)
     np.random.seed(int(z["seed"]))
     torch.manual_seed(int(z["seed"]))
-    b = ds.gpu_batch([int(i) for i in z["indices"]], want_seg2d=True)
+    return z, ds, kw, [int(i) for i in z["indices"]]
+
+
+def _assert_equals_the_reference_batch(b, z, kw):
+    """Every tensor of the reference's collated batch ``z`` is in the device batch ``b``, bit for bit."""
     host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
     _same(host(b["x"][0]), z["batch/x0"], "locs")
     _same(host(b["x"][1]), z["batch/x1"], "feats")
@@ -149,6 +150,26 @@ def test_gpu_batch_equals_the_reference_batch(name):
             assert b["pseudo_label_3d"] == []
         else:
             _same(host(b["pseudo_label_3d"]), z["batch/pseudo_label_3d"], "pseudo_label_3d")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", GPU_CASES)
+def test_gpu_batch_equals_the_reference_batch(name):
+    """The same index list through ``gpu_batch`` (front end on the host, per-point work in csrc/dataprep.hip): every tensor
+    of the reference's collated batch, bit for bit."""
+    z, ds, kw, idx = _reference_fixture(name)
+    _assert_equals_the_reference_batch(ds.gpu_batch(idx, want_seg2d=True), z, kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("image", ["host", "gpu"])
+@pytest.mark.parametrize("name", GPU_CASES)
+def test_pending_batch_equals_the_reference_batch(name, image):
+    """The pipelined loader on its own against the reference: it shares its scene loop, launchers and batch finisher with
+    ``gpu_batch`` (mm2d3d_amd/dataprep.py), so a mistake there would pass the loader-against-loader comparison of
+    tests/test_gpu_pipeline.py."""
+    z, ds, kw, idx = _reference_fixture(name)
+    _assert_equals_the_reference_batch(ds.begin_gpu_batch(idx, want_seg2d=True, image=image).result(), z, kw)
 
 
 @pytest.mark.gpu

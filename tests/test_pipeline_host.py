@@ -1,5 +1,6 @@
 """Host side of the pipelined loader (mm2d3d_amd/pipeline.py) without a GPU: the host phase draws what ``ds[i]`` draws, the
 staging blocks hold what was packed at 16-byte offsets, and ``BatchStream`` orders host phases, queues and yields as documented."""
+import os
 import threading
 
 import numpy as np
@@ -43,6 +44,79 @@ def test_host_phase_leaves_the_rng_states_of_the_host_loader(name, image):
         assert p.f64 == (name == "vkitti_rand_crop")
     finally:
         p.cancel()
+
+
+@pytest.mark.parametrize("image", ["host", "gpu"])
+@pytest.mark.parametrize("name", RNG_CASES)
+def test_scene_loop_leaves_the_rng_states_of_the_host_loader(name, image):
+    """``_Scenes._draw_scenes``, the scene loop of ``gpu_batch`` and of the pipelined loader, on its own."""
+    ds, _ = tlg._dataset(name)
+    idx = _indices(name)
+    np.random.seed(11)
+    torch.manual_seed(11)
+    [ds[i] for i in idx]
+    want = _rng_states()
+    np.random.seed(11)
+    torch.manual_seed(11)
+    d = ds._draw_scenes(idx, image == "gpu")
+    _same_rng(want, _rng_states())
+    assert ds._plan_images is False
+    assert all(len(v) == len(idx) for v in (d.scenes, d.works, d.intrinsics, d.flips, d.rots, d.us))
+    assert len(d.jitter) == (len(idx) if image == "gpu" else 0)
+    H, W = d.HW
+    assert all(("img" not in s) if image == "gpu" else (s["img"].shape == (3, H, W)) for s in d.scenes)
+
+
+@pytest.mark.parametrize("on_gpu", [False, True])
+def test_scene_loop_resets_the_image_plans_when_a_scene_raises(on_gpu):
+    ds, _ = tlg._dataset("skitti_rand_crop")
+    idx = _indices("skitti_rand_crop")
+    ds.data[idx[1]] = dict(ds.data[idx[1]], seg_labels=None)  # an unlabelled scene (a test split), after a labelled one
+    with pytest.raises(ValueError) as e:
+        ds._draw_scenes(idx, on_gpu)
+    assert str(e.value) == "gpu_batch needs labelled scenes (the 2D label map and seg_label are part of the batch)"
+    assert ds._plan_images is False
+
+
+def test_jpeg_read_helpers_fill_a_caller_buffer_as_read_jpegs_fills_its_own(tmp_path):
+    from PIL import Image
+
+    from mm2d3d_amd import imageprep, jpeg
+
+    ds, _ = tlg._dataset("nuscenes_train")
+    paths = [os.path.join(tlg.MINI, "nuscenes", d["camera_path"]) for d in ds.data]
+    cut = str(tmp_path / "cut.jpg")
+    with open(paths[0], "rb") as f:
+        data = f.read()
+    with open(cut, "wb") as f:
+        f.write(data)
+    paths.insert(1, cut)
+    plans = [imageprep.ImagePlan(Image.open(p)) for p in paths]  # PIL has read the headers: the plans know format and size
+    with open(cut, "wb") as f:
+        f.write(data[: jpeg.parse(data).entropy[0] - 20])  # the file now ends inside its header
+    pinned, offs, want = dataprep.read_jpegs(plans)
+    files, file_offs = dataprep.jpeg_files(plans)
+    assert files == paths
+    assert file_offs.dtype == np.int64 and list(file_offs) == [0] + list(np.cumsum([os.path.getsize(p) for p in paths]))
+    tlg._same(file_offs[:-1], offs, "offsets")
+    total = int(file_offs[-1])
+    buf = np.full(total + 7, 0xAB, np.uint8)
+    got = dataprep.read_jpeg_files(files, file_offs, buf)
+    contents = []
+    for p in paths:
+        with open(p, "rb") as f:
+            contents.append(f.read())
+    assert bytes(buf[:total]) == b"".join(contents) and bytes(pinned.numpy()[:total]) == b"".join(contents)
+    assert bool((buf[total:] == 0xAB).all())  # nothing written past the files
+    assert len(got) == len(want) == len(paths)
+    for g, w in zip(got, want):
+        for field in jpeg.JpegHeader.__slots__:
+            assert repr(getattr(g, field)) == repr(getattr(w, field)), field
+    assert got[1].reason.startswith("header:") and "cut.jpg" in got[1].reason
+    assert [h.reason for i, h in enumerate(got) if i != 1] == [None] * (len(paths) - 1)
+    assert got[0].size == Image.open(paths[0]).size and got[0].entropy is not None
+    assert dataprep.split_decoders(got) == ([i for i in range(len(paths)) if i != 1], [1])
+    assert dataprep.split_decoders([None, got[0], None]) == ([1], [0, 2])
 
 
 @pytest.mark.parametrize("name,image", [("nuscenes_train", "gpu"), ("skitti_bottom_crop", "host"), ("vkitti_rand_crop", "gpu"),
