@@ -491,6 +491,26 @@ int mm_adam_step_dev(float* p, const float* g, float* m, float* v, float* vmax, 
 int mm_rmsprop_step_dev(float* p, const float* g, float* sq, float* gavg, float* buf, int64_t n, const void* coef_dev,
                         mm_stream_t stream);
 
+/* ---------------------------------------------------------------- mean-teacher weights over the flat arenas (csrc/optim.hip)
+ * An exponential moving average of the weights (mm2d3d_amd/ema.py WeightEMA), gated ON THE DEVICE by the decision that gated the
+ * optimiser update of the same step, so a skipped step is neither averaged in nor counted.  table_dev: nrows rows of
+ * mm_ema_row_bytes() bytes in device memory, one per tensor pair:
+ *     { float* dst; float* src; int64 n; int64 first; }
+ * dst = the teacher's tensor, src = the live one, n = elements (0 is legal), first = the number of the row's first workgroup =
+ * the sum of ceil(n / 1024) over the rows before it; nblocks = that sum over all rows.  A workgroup finds its row by binary
+ * search over ``first``; a thread owns four consecutive elements and uses 16-byte accesses when both pointers of the row are
+ * 16-byte aligned and the four elements fit.  The pairs must not overlap.
+ *   mm_ema_update  dst = lerp(dst, src, w) in fp32 (d = src - dst; w < 0.5 ? dst + w*d : src - d*(1 - w)), w = (float)(1 - decay_t),
+ *                  decay_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay in double, t = *step_dev (device int64) when step_dev
+ *                  is not NULL, else t_host: the optimiser's count of TAKEN steps after this step's update.  Nothing is written
+ *                  when any of skip_dev[0 .. nskip) (nskip 0 .. 16) is nonzero, or when coef_dev is not NULL and the coefficients
+ *                  it points to (mm_optim_coef_bytes, written by mm_*_prepare) say "skip".  0 <= decay < 1.
+ *   mm_ema_swap    exchanges the CONTENTS of dst and src of every row (pointers stay: parameters are views into the arenas). */
+int mm_ema_row_bytes(void);
+int mm_ema_update(const void* table_dev, int nrows, int64_t nblocks, double decay, int warmup, int64_t t_host, const int64_t* step_dev,
+                  const void* coef_dev, const int* skip_dev, int nskip, mm_stream_t stream);
+int mm_ema_swap(const void* table_dev, int nrows, int64_t nblocks, mm_stream_t stream);
+
 /* ---------------------------------------------------------------- gradient clipping for the flat optimisers (csrc/clip.hip)
  * torch.nn.utils.clip_grad_norm_ (norm_type 2) / clip_grad_value_ on the TRUE gradient g * grad_scale / scale of arenas that hold
  * loss-scaled, un-averaged gradients (Lightning's gradient_clip_val / gradient_clip_algorithm, EXP/run.py:262-288).  No read-back.

@@ -128,6 +128,9 @@ _PROTOS = {
     "mm_sgd_step_dev": (i32, [vp, vp, vp, i64, i32, vp, vp]),
     "mm_adam_step_dev": (i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     "mm_rmsprop_step_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp]),
+    "mm_ema_row_bytes": (i32, []),
+    "mm_ema_update": (i32, [vp, i32, i64, f64, i32, i64, vp, vp, vp, i32, vp]),
+    "mm_ema_swap": (i32, [vp, i32, i64, vp]),
     "mm_grad_sqnorm_ws_bytes": (sz, [i64]),
     "mm_grad_sqnorm": (i32, [vp, i64, vp, i64, vp, vp]),
     "mm_clip_finalize": (i32, [vp, vp, i32, vp, f64, f64, vp, vp, vp]),

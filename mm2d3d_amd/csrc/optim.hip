@@ -336,3 +336,125 @@ int mm_amp_update(float* scale_dev, int* tracker_dev, const int* found_dev, int 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- mean-teacher weights
+// e <- lerp(e, p, 1 - decay) over a device table of tensor pairs (mm2d3d_amd/ema.py WeightEMA: the optimisers' arenas and the
+// modules' floating-point buffers), ONE launch for every pair, gated by the decision the optimiser update of the same step was
+// gated by: the caller's skip words and OptCoef::skip of a device-counted step.  These kernels live in this file only because they
+// read OptCoef::skip.  Within a row the contract is k_optim's: a thread owns four consecutive elements, 16-byte accesses when both
+// pointers of the row are 16-byte aligned and the four elements fit, else element by element.
+namespace {
+struct EmaRow {
+  float* dst;      // the teacher's tensor
+  float* src;      // the live tensor
+  long long n;     // elements (0 is legal: the row owns no workgroup)
+  long long first; // number of the row's first workgroup: the sum of cdiv(n, 4 T) over the rows before it
+};
+
+// The row of this workgroup: the last one whose first workgroup is <= blockIdx.x (rows without elements share their successor's
+// number and are never the last).  Returns the thread's first element in the row, or -1 when it owns none.
+__device__ __forceinline__ long long ema_locate(const EmaRow* __restrict__ table, int nrows, EmaRow& r) {
+  const long long b = blockIdx.x;
+  int lo = 0, hi = nrows;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (table[mid].first <= b)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  r = table[lo];
+  const long long local = b - r.first;
+  if (local < 0) return -1;
+  const long long i = (local * T + threadIdx.x) * 4;
+  return i < r.n ? i : -1;
+}
+
+__device__ __forceinline__ bool ema_vec(const EmaRow& r, long long i) {
+  return ((((uintptr_t)r.dst | (uintptr_t)r.src) & 15) == 0) && i + 4 <= r.n;
+}
+
+// torch's lerp(e, p, w) in fp32: exact at both ends (p == e leaves e as it is; w = 1 gives p)
+__device__ __forceinline__ float ema_lerp(float e, float p, float w) {
+  const float d = p - e;
+  return w < 0.5f ? e + w * d : p - d * (1.f - w);
+}
+
+__global__ __launch_bounds__(T) void k_ema_update(const EmaRow* __restrict__ table, int nrows, double decay, int warmup,
+                                                   long long t_host, const long long* __restrict__ step,
+                                                   const OptCoef* __restrict__ dc, const int* __restrict__ skip, int nskip) {
+  for (int i = 0; i < nskip; i++)  // uniform, decided on the device
+    if (skip[i]) return;
+  if (dc && dc->skip) return;
+  double dt = decay;
+  if (warmup) {
+    const double t = (double)(step ? step[0] : t_host);  // taken steps, this one included
+    dt = fmin(decay, (1.0 + t) / (10.0 + t));
+  }
+  const float w = (float)(1.0 - dt);
+  EmaRow r;
+  const long long i = ema_locate(table, nrows, r);
+  if (i < 0) return;
+  if (ema_vec(r, i)) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 P = *(const f4*)(r.src + i);
+    f4 E = *(f4*)(r.dst + i);
+#pragma unroll
+    for (int j = 0; j < 4; j++) E[j] = ema_lerp(E[j], P[j], w);
+    *(f4*)(r.dst + i) = E;
+    return;
+  }
+  for (int j = 0; j < 4 && i + j < r.n; j++) r.dst[i + j] = ema_lerp(r.dst[i + j], r.src[i + j], w);
+}
+
+__global__ __launch_bounds__(T) void k_ema_swap(const EmaRow* __restrict__ table, int nrows) {
+  EmaRow r;
+  const long long i = ema_locate(table, nrows, r);
+  if (i < 0) return;
+  if (ema_vec(r, i)) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 P = *(f4*)(r.src + i), E = *(f4*)(r.dst + i);
+    *(f4*)(r.src + i) = E;
+    *(f4*)(r.dst + i) = P;
+    return;
+  }
+  for (int j = 0; j < 4 && i + j < r.n; j++) {
+    const float pj = r.src[i + j];
+    r.src[i + j] = r.dst[i + j];
+    r.dst[i + j] = pj;
+  }
+}
+
+int ema_check_table(const void* table_dev, int nrows, int64_t nblocks) {
+  MM_CHECK_ARG(nrows >= 0 && nblocks >= 0 && nblocks <= 0x7fffffffLL, "ema: bad table size");
+  MM_CHECK_ARG(nblocks == 0 || (nrows >= 1 && table_dev), "ema: workgroups without a table");
+  return MM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mm_ema_row_bytes(void) { return (int)sizeof(EmaRow); }
+
+int mm_ema_update(const void* table_dev, int nrows, int64_t nblocks, double decay, int warmup, int64_t t_host, const int64_t* step_dev,
+                  const void* coef_dev, const int* skip_dev, int nskip, hipStream_t s) {
+  if (int rc = ema_check_table(table_dev, nrows, nblocks)) return rc;
+  MM_CHECK_ARG(decay >= 0.0 && decay < 1.0, "ema_update: decay outside [0, 1)");
+  MM_CHECK_ARG(t_host >= 0, "ema_update: t < 0");
+  MM_CHECK_ARG(nskip >= 0 && nskip <= 16 && (nskip == 0 || skip_dev), "ema_update: bad skip words");
+  if (nblocks == 0) return MM_OK;
+  hipLaunchKernelGGL(k_ema_update, dim3((unsigned)nblocks), dim3(T), 0, s, (const EmaRow*)table_dev, nrows, decay, warmup ? 1 : 0,
+                     (long long)t_host, (const long long*)step_dev, (const OptCoef*)coef_dev, skip_dev, nskip);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_ema_swap(const void* table_dev, int nrows, int64_t nblocks, hipStream_t s) {
+  if (int rc = ema_check_table(table_dev, nrows, nblocks)) return rc;
+  if (nblocks == 0) return MM_OK;
+  hipLaunchKernelGGL(k_ema_swap, dim3((unsigned)nblocks), dim3(T), 0, s, (const EmaRow*)table_dev, nrows);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+}  // extern "C"

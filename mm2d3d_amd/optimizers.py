@@ -212,6 +212,7 @@ class _FlatOptimizer(optim.Optimizer):
             # first device-counted step, or the first after plain steps / a restored checkpoint: the host counter is the truth until now
             step_dev.fill_(int(self._step))
         self._dev_step = step_dev
+        self._dev_coef = coef_dev  # gate_coef(): the rows this step's decision is written to
         self._opt_called = True  # what torch's lr schedulers look at to tell "step() before scheduler.step()"
         from . import conv2d as _c2d
 
@@ -225,6 +226,21 @@ class _FlatOptimizer(optim.Optimizer):
             first = False
             for lo, hi in self._touched_ranges(a):
                 self._scaled(L, group, a, lo, hi, coef_dev[gi])
+
+    # ------------------------------------------------------------------ what the last step decided (mm2d3d_amd/ema.py)
+    def gate_coef(self):
+        """The device coefficient row (csrc/optim.hip OptCoef) of the last step when that step was device-counted: its ``skip``
+        field is the decision the update was gated by (non-finite gradients of any optimiser of the step, the caller's skip
+        words).  None after a plain step, which has no such row: its skip words alone gated it."""
+        if getattr(self, "_dev_step", None) is None:
+            return None
+        gi = next((i for i, a in enumerate(self._arenas) if a is not None), None)
+        return None if gi is None else self._dev_coef[gi]
+
+    def step_counter(self):
+        """The count of taken steps: the device counter (int64[1]) while device-counted steps lead, else the host's int."""
+        dev = getattr(self, "_dev_step", None)
+        return self._step if dev is None else dev
 
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):

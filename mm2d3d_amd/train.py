@@ -43,6 +43,19 @@ class TrainModel(nn.Module):
         self.pseudo_labels = train_kwargs.get("pseudo_labels", "own")
         if self.pseudo_labels not in ("own", "ensemble"):
             raise ValueError(f"train_kwargs['pseudo_labels'] must be 'own' or 'ensemble', not {self.pseudo_labels!r}")
+        # Mean-teacher weights (mm2d3d_amd/ema.py): with ``ema_decay`` set, an exponential moving average of every arena of the
+        # optimisers and every floating-point buffer follows the step in one launch, gated on the device by the decision the
+        # optimiser update was gated by (a skipped step is neither averaged in nor counted).  ``ema_warmup``: decay_t =
+        # min(decay, (1 + t) / (10 + t)) over the taken steps t.  ``ema_eval``: validation, test and ``predict_step`` (so
+        # pselab.export_pseudo_labels too) compute with the teacher; the student's weights come back afterwards.  The checkpoint
+        # gains "ema" (the WeightEMA state) and "ema_state_dict" (the teacher under the keys of "state_dict").  None (default):
+        # nothing is allocated and the step is launch for launch the step without the option; ``trainer.ema`` is None.
+        self.ema_decay = train_kwargs.get("ema_decay")
+        if self.ema_decay is not None and not 0.0 <= float(self.ema_decay) < 1.0:
+            raise ValueError(f"train_kwargs['ema_decay'] must be None or in [0, 1), not {self.ema_decay!r}")
+        self.ema_warmup = bool(train_kwargs.get("ema_warmup", False))
+        self.ema_eval = bool(train_kwargs.get("ema_eval", False))
+        self.ema = None
         self.broadcast_buffers = bool(int(train_kwargs.get("broadcast_buffers", os.environ.get("MM_DDP_BROADCAST_BUFFERS", "1"))))  # torch DDP default (run.py:264-268)
         # One pass per network over [source scenes | target scenes] instead of one per domain: half the launches, twice
         # the rows per launch.  The batch-norm layers keep per-domain statistics (mm2d3d_amd/domains.py), so the
@@ -168,6 +181,10 @@ class TrainModel(nn.Module):
         # torch DDP broadcasts rank 0's parameters when it wraps a model (run.py:262-268): replicas start identical whatever
         # each rank's seed was
         self.reducer.sync_parameters(src=0)
+        if self.ema_decay is not None:
+            from .ema import WeightEMA
+
+            self.ema = WeightEMA(self.optimizers, self.model, float(self.ema_decay), warmup=self.ema_warmup)
         if self.gc_freeze:
             # Everything built so far (modules, parameters, optimiser state, torch itself) is long-lived.  Left in the collector's
             # oldest generation it is re-traversed by every full collection (87 ms measured for one pass here, during which the
@@ -429,9 +446,22 @@ class TrainModel(nn.Module):
             self._ious[stage] = SegIoU(num_classes, device)
         return self._ious[stage]
 
+    def _teacher(self):
+        """``ema_eval``: the context in which the model computes with the teacher's weights (built with the optimisers)."""
+        import contextlib
+
+        if not self.ema_eval or self.ema_decay is None:
+            return contextlib.nullcontext()
+        if self.ema is None:
+            if not self._opt_factories:
+                raise RuntimeError("ema_eval: the teacher lives beside the optimisers' arenas and this trainer has no optimisers; to "
+                                   "evaluate a saved teacher, load the checkpoint's \"ema_state_dict\" as its \"state_dict\"")
+            self.configure_optimizers()
+        return self.ema.applied()
+
     @torch.no_grad()
     def _generic_step_val(self, batch, stage):
-        with self._use():
+        with self._use(), self._teacher():
             return self._generic_step_val_impl(batch, stage)
 
     def _generic_step_val_impl(self, batch, stage):
@@ -459,7 +489,7 @@ class TrainModel(nn.Module):
         the model in eval mode; no epoch-end hook follows it, so call ``trainer.model.train()`` before training goes on."""
         from . import pselab
 
-        with self._use():
+        with self._use(), self._teacher():
             self.model.eval()
             p2d, _, _, _ = self(batch, model_name=self.modules_name[0])
             p3d, _, _ = self(batch, model_name=self.modules_name[1])
@@ -498,6 +528,10 @@ class TrainModel(nn.Module):
                 "optimizer_states": [o.state_dict() for o in self.optimizers],
                 "lr_schedulers": [s.state_dict() if s is not None else None for s in self.schedulers],
                 "global_step": self.global_step, **self.best,
+                # the mean teacher: its own state, and its weights under the keys of "state_dict" (loadable in its place)
+                **({"ema": self.ema.state_dict(),
+                    "ema_state_dict": {self._ckpt_key(k): v for k, v in self.ema.teacher_state_dict().items()}}
+                   if self.ema is not None else {}),
                 # Lightning's key for the GradScaler of a ``precision: 16`` run
                 **({"native_amp_scaling_state": self.scaler.state_dict()} if self.scaler is not None else {})}
 
@@ -534,6 +568,11 @@ class TrainModel(nn.Module):
             if s is not None and sd is not None:
                 s.load_state_dict(sd)
         self.global_step = ckpt.get("global_step", 0)
+        if self.ema is not None:
+            if ckpt.get("ema") is not None:
+                self.ema.load_state_dict(ckpt["ema"])
+            else:
+                self.ema.reset()  # a checkpoint without a teacher: it starts from the loaded weights
         # the loss scale resumes where it was; the scaler itself is rebuilt by the next fit_step (its device step counters start
         # from the optimisers' restored step counts)
         self._scaler_state = ckpt.get("native_amp_scaling_state")
@@ -624,6 +663,8 @@ class TrainModel(nn.Module):
                     o.step(grad_scale=self.reducer.grad_scale, skip_words=skip)
                 else:
                     o.step()
+        if self.ema is not None:
+            self.ema.update(skip_words=skip)
         for s in self.schedulers:
             if s is not None:
                 s.step()
