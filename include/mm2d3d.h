@@ -435,6 +435,17 @@ int mm_eval_confusion(const float* logits2d, int ld2, const float* logits3d, int
 int mm_pselab_predict(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, float* probs_2d,
                       uint8_t* label_2d, float* probs_3d, uint8_t* label_3d, float* probs_ensemble, uint8_t* label_ensemble,
                       mm_stream_t stream);
+/* The labels a mean teacher gives a target batch inside the training step: ONE launch over N rows of both logit matrices, each row
+ * through the device expression of mm_pselab_predict (an online label is the label an export would have written).  ensemble == 0:
+ * label_2d = argmax of the 2D softmax with its confidence, label_3d = the 3D one; ensemble != 0: both outputs get the argmax of the
+ * softmax average and its confidence.  thr >= 0: a label whose confidence p does not satisfy p >= thr (float32; a non-finite
+ * confidence fails it) becomes ignore_label; thr < 0 keeps every label.  prob_2d / prob_3d (fp32 [N], may be NULL) receive the
+ * confidences; kept (may be NULL) receives the number of kept labels per output in kept[0] / kept[1]: zeroed on the stream here,
+ * summed per workgroup and added with 64-bit integer atomics (exact in any order).  logits [N, C] fp32 with row pitches >= C,
+ * C <= 32; N == 0 launches nothing and writes nothing. */
+int mm_teacher_labels(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, float thr,
+                      int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d, float* prob_3d,
+                      unsigned long long* kept, mm_stream_t stream);
 /* lib/utils/refine_pseudo_labels.py, exact: for every class c of [0, C) that occurs n_c > 0 times, med_c = the element of rank
  * (n_c - 1) / 2 (ascending, 0-based: torch.median's lower median) among the probs of that class, thr_c = min(med_c, 0.9f);
  * labels_out[i] = ignore_label where labels[i] == c and probs[i] < thr_c, else labels[i].  Labels outside [0, C) pass through.

@@ -114,6 +114,7 @@ _PROTOS = {
     "mm_lift_scatter_key": (i32, [vp, i32, vp, vp, i64, i32, i32, i64, i64, i64, i64, vp, vp]),
     "mm_eval_confusion": (i32, [vp, i32, vp, i32, vp, i64, i32, i64, vp, vp]),
     "mm_pselab_predict": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mm_teacher_labels": (i32, [vp, i32, vp, i32, i64, i32, i32, f32, i64, vp, vp, vp, vp, vp, vp]),
     "mm_pselab_refine_ws_bytes": (sz, [i32]),
     "mm_pselab_refine": (i32, [vp, vp, i64, i32, i64, vp, vp, sz, vp]),
     "mm_grad_nonfinite": (i32, [vp, i64, vp, vp]),

@@ -1,5 +1,7 @@
 // Pseudo labels for the self-training round (EXP/train.py:297-339 -> the files lib/dataset/*_dataloader.py read back):
 //   mm_pselab_predict   per point: max and argmax of softmax(2D logits), of softmax(3D logits) and of their average
+//   mm_teacher_labels   the same per-point expression, written as the int64 training labels of both heads (a mean teacher that
+//                       labels the target batch inside the step), with an optional confidence threshold and kept counts
 //   mm_pselab_refine    lib/utils/refine_pseudo_labels.py, exact: per class the lower median of the confidences by a
 //                       most-significant-digit radix select (four 8-bit passes over the order-preserving uint32 image of the
 //                       floats), threshold min(median, 0.9f), labels below it become ignore_label
@@ -43,6 +45,55 @@ __global__ __launch_bounds__(PT) void k_pselab_predict(const float* __restrict__
     y3[i] = (uint8_t)r.ib;
     pe[i] = r.pe;
     ye[i] = (uint8_t)r.ie;
+  }
+}
+
+// ---- online labels of a mean teacher (mm2d3d_amd/train.py pseudo_label_source="teacher"): the staging and the per-row expression
+// of k_pselab_predict, written as the int64 labels cross_entropy_pair reads.  ENS: both outputs take the softmax average.
+// thr >= 0: a label whose confidence is not >= thr (a NaN confidence included) becomes `ignore`.  kept[2]: labels that were
+// kept, per output - a ballot per wave, the two waves' counts through two words of the tile (its rows are dead by then), one
+// 64-bit integer atomic per workgroup and counter.
+template <bool ENS>
+__global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3,
+                                                        int64_t N, int C, float thr, int64_t ignore, int64_t* __restrict__ y2,
+                                                        int64_t* __restrict__ y3, float* __restrict__ p2, float* __restrict__ p3,
+                                                        unsigned long long* __restrict__ kept) {
+  extern __shared__ float tile[];  // [2][PT][pitch]
+  const int pitch = C | 1;
+  const int64_t row0 = (int64_t)blockIdx.x * PT;
+  const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
+  float* ta = tile;
+  float* tb = tile + PT * pitch;
+  for (int e = threadIdx.x; e < rows * C; e += PT) {
+    const int r = e / C, c = e - r * C;
+    ta[r * pitch + c] = l2[(row0 + r) * ld2 + c];
+    tb[r * pitch + c] = l3[(row0 + r) * ld3 + c];
+  }
+  __syncthreads();
+  bool k2 = false, k3 = false;
+  if ((int)threadIdx.x < rows) {
+    const MMPointPred r = mm_point_predict<true>(ta + threadIdx.x * pitch, tb + threadIdx.x * pitch, C);
+    const float pa = ENS ? r.pe : r.pa, pb = ENS ? r.pe : r.pb;
+    const int ia = ENS ? r.ie : r.ia, ib = ENS ? r.ie : r.ib;
+    k2 = thr < 0.f || pa >= thr;
+    k3 = thr < 0.f || pb >= thr;
+    const int64_t i = row0 + threadIdx.x;
+    y2[i] = k2 ? (int64_t)ia : ignore;
+    y3[i] = k3 ? (int64_t)ib : ignore;
+    if (p2) p2[i] = pa;
+    if (p3) p3[i] = pb;
+  }
+  if (!kept) return;  // uniform
+  const unsigned n2 = (unsigned)__popcll(__ballot(k2)), n3 = (unsigned)__popcll(__ballot(k3));
+  __syncthreads();  // every lane has read its rows
+  unsigned* cnt = (unsigned*)tile;  // [PT / 64][2]
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) cnt[2 * wave] = n2, cnt[2 * wave + 1] = n3;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned n = 0;
+    for (int w = 0; w < PT / 64; w++) n += cnt[2 * w + threadIdx.x];
+    if (n) atomicAdd(&kept[threadIdx.x], (unsigned long long)n);
   }
 }
 
@@ -180,6 +231,29 @@ int mm_pselab_predict(const float* logits2d, int ld2, const float* logits3d, int
   else
     hipLaunchKernelGGL(k_pselab_predict<false>, grid, dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, probs_2d, label_2d, probs_3d,
                        label_3d, probs_ensemble, label_ensemble);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_teacher_labels(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, float thr,
+                      int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d, float* prob_3d,
+                      unsigned long long* kept, hipStream_t s) {
+  static_assert(PT % 64 == 0, "k_teacher_labels counts per 64-lane wave");
+  MM_CHECK_ARG(C > 0 && C <= MM_PRED_MAXC, "teacher_labels: bad C");
+  MM_CHECK_ARG(N >= 0 && N <= (int64_t)PT * 0x7fffffff, "teacher_labels: bad N");
+  if (N == 0) return MM_OK;
+  MM_CHECK_ARG(logits2d && logits3d, "teacher_labels: null logits");
+  MM_CHECK_ARG(label_2d && label_3d, "teacher_labels: null labels");
+  MM_CHECK_ARG(ld2 >= C && ld3 >= C, "teacher_labels: row pitch below C");
+  if (kept) MM_HIP(hipMemsetAsync(kept, 0, 2 * sizeof(unsigned long long), s));
+  const dim3 grid((unsigned)mm_cdiv(N, PT));
+  const size_t lds = (size_t)2 * PT * (C | 1) * sizeof(float);  // <= 33 KB
+  if (ensemble)
+    hipLaunchKernelGGL(k_teacher_labels<true>, grid, dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, thr, ignore_label, label_2d,
+                       label_3d, prob_2d, prob_3d, kept);
+  else
+    hipLaunchKernelGGL(k_teacher_labels<false>, grid, dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, thr, ignore_label, label_2d,
+                       label_3d, prob_2d, prob_3d, kept);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -9,15 +9,33 @@ data-parallel bucket countdown) are fired by hand once the LAST contribution of 
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 
 def claim(ctx, param, needs_grad):
     """Call in Function.forward.  Returns True when backward should write into ``param._mm_sink``."""
-    use = bool(needs_grad) and hasattr(param, "_mm_sink")
+    use = bool(needs_grad) and not _SUSPENDED[0] and hasattr(param, "_mm_sink")
     if use:
         param._mm_pending += 1
     return use
+
+
+_SUSPENDED = [0]
+
+
+@contextlib.contextmanager
+def suspended():
+    """Forwards inside claim nothing.  For a forward under no_grad BETWEEN ``zero_grad`` and the step's backward (the mean teacher's,
+    train.py ``pseudo_label_source="teacher"``): ``needs_input_grad`` is set there all the same, the grad mode cannot be read inside
+    ``Function.forward`` (it is always off there), and no backward would ever release the claim - the parameter's hooks would
+    not fire at the end of the student's backward, and a captured backward would miss its sunk gradients."""
+    _SUSPENDED[0] += 1
+    try:
+        yield
+    finally:
+        _SUSPENDED[0] -= 1
 
 
 _COLLECT = [None]

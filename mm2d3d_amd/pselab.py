@@ -6,6 +6,9 @@ pseudo_label_3d / probs_ensemble / pseudo_label_ensemble``, each ``[n_points]`` 
 its class (uint8) of the 2D network, of the 3D network and of their average (train.py:297-339).  This module writes them:
 
     predict(logits_2d, logits_3d)            the six per-point tensors of one batch, one kernel (mm_pselab_predict)
+    teacher_labels(logits_2d, logits_3d)     the same per-point expression as int64 training labels of both heads, with an
+                                             optional confidence threshold (mm_teacher_labels): what a mean teacher gives the
+                                             target batch inside the training step (train.py pseudo_label_source="teacher")
     PseudoLabelWriter(path)                  collects scenes, ``close()`` writes the file
     export_pseudo_labels(trainer, dataset, path)   walks a dataset through ``TrainModel.predict_step`` into a writer
     refine_pseudo_labels(probs, labels)      lib/utils/refine_pseudo_labels.py on the GPU (mm_pselab_refine), exact: what the
@@ -28,11 +31,11 @@ MAX_CLASSES = 32  # csrc/pointpred.h MM_PRED_MAXC
 
 
 # ---------------------------------------------------------------------------------------------------- prediction
-def _logits(t, name):
+def _logits(t, name, who="predict"):
     _lib.require_cuda(t, name)
     t = t.detach()
     if t.dim() != 2:
-        raise ValueError(f"pselab.predict: {name} must be [N, C]")
+        raise ValueError(f"pselab.{who}: {name} must be [N, C]")
     if t.dtype != torch.float32:
         t = t.float()
     if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
@@ -64,6 +67,33 @@ def predict(logits_2d, logits_3d=None):
     if b is not None:
         out["probs_3d"], out["pseudo_label_3d"] = probs[1], labels[1]
         out["probs_ensemble"], out["pseudo_label_ensemble"] = probs[2], labels[2]
+    return out
+
+
+@torch.no_grad()
+def teacher_labels(logits_2d, logits_3d, ensemble=False, threshold=None, ignore_label=-100, with_probs=False):
+    """The int64 training labels a teacher's logits give both heads, in one launch (mm_teacher_labels): per row the expression
+    of :func:`predict`, so ``label_2d`` / ``label_3d`` are ``pseudo_label_2d`` / ``pseudo_label_3d`` of an export, or with
+    ``ensemble`` both ``pseudo_label_ensemble``.  ``threshold``: a label whose confidence is not ``>= threshold`` (float32)
+    becomes ``ignore_label``; ``None`` keeps all.  Returns ``dict(label_2d, label_3d, kept)``, ``kept`` an int64 ``[2]`` device
+    tensor with the labels kept per output; ``with_probs`` adds ``prob_2d`` / ``prob_3d``, the confidences the labels were
+    judged by.  Row-pitched views are read in place."""
+    a, b = _logits(logits_2d, "logits_2d", "teacher_labels"), _logits(logits_3d, "logits_3d", "teacher_labels")
+    if b.shape != a.shape or b.device != a.device:
+        raise ValueError("pselab.teacher_labels: logits_2d and logits_3d must have the same shape and device")
+    N, C = a.shape
+    labels = torch.empty((2, N), dtype=torch.int64, device=a.device)
+    probs = torch.empty((2, N), dtype=torch.float32, device=a.device) if with_probs else None
+    kept = torch.zeros(2, dtype=torch.int64, device=a.device) if N == 0 else torch.empty(2, dtype=torch.int64, device=a.device)
+    pitch = lambda t: t.stride(0) if N > 1 else C
+    with torch.cuda.device(a.device):
+        check(_lib.lib().mm_teacher_labels(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)),
+                                           -1.0 if threshold is None else float(threshold), int(ignore_label), ptr(labels[0]),
+                                           ptr(labels[1]), ptr(probs[0]) if with_probs else None, ptr(probs[1]) if with_probs else None,
+                                           ptr(kept), stream()), "teacher_labels")
+    out = {"label_2d": labels[0], "label_3d": labels[1], "kept": kept}
+    if with_probs:
+        out["prob_2d"], out["prob_3d"] = probs[0], probs[1]
     return out
 
 

@@ -56,6 +56,23 @@ class TrainModel(nn.Module):
         self.ema_warmup = bool(train_kwargs.get("ema_warmup", False))
         self.ema_eval = bool(train_kwargs.get("ema_eval", False))
         self.ema = None
+        # Where the pseudo labels come from (consulted only with ``lambda_pl`` > 0).  "batch" (default): the batch's
+        # ``pseudo_label_*`` keys, as above.  "teacher": the mean teacher labels the target batch inside the step - before the
+        # student's forward the model computes the target rows in eval mode with the teacher's weights (``ema.applied()``, no_grad)
+        # and ONE launch turns the two logit matrices into the int64 labels of both heads (pselab.teacher_labels; "own" / "ensemble"
+        # as above); after the step the teacher follows the student as always.  ``pseudo_label_*`` keys of the batch are ignored.
+        # ``pl_threshold`` (teacher source only): None keeps every label, a float in (0, 1] refuses labels whose confidence is
+        # below it, "median" applies the loaders' refinement rule over this batch's target rows (per class min(lower median, 0.9),
+        # mm_pselab_refine per output).  What was used: ``last_teacher`` = dict(label_2d, label_3d, kept) and the logged
+        # ``train/pl_kept_2d`` / ``_3d`` (kept share of the target rows), all device tensors.
+        self.pseudo_label_source = train_kwargs.get("pseudo_label_source", "batch")
+        if self.pseudo_label_source not in ("batch", "teacher"):
+            raise ValueError(f"train_kwargs['pseudo_label_source'] must be 'batch' or 'teacher', not {self.pseudo_label_source!r}")
+        self.pl_threshold = train_kwargs.get("pl_threshold")
+        thr = self.pl_threshold
+        if not (thr is None or thr == "median" or (isinstance(thr, (int, float)) and not isinstance(thr, bool) and 0.0 < thr <= 1.0)):
+            raise ValueError(f"train_kwargs['pl_threshold'] must be None, 'median' or a number in (0, 1], not {thr!r}")
+        self.last_teacher = None
         self.broadcast_buffers = bool(int(train_kwargs.get("broadcast_buffers", os.environ.get("MM_DDP_BROADCAST_BUFFERS", "1"))))  # torch DDP default (run.py:264-268)
         # One pass per network over [source scenes | target scenes] instead of one per domain: half the launches, twice
         # the rows per launch.  The batch-norm layers keep per-domain statistics (mm2d3d_amd/domains.py), so the
@@ -129,6 +146,14 @@ class TrainModel(nn.Module):
         # keeps refilling them; what exactly keeps them from ever draining at that size was not found.
         # Never under data parallelism.
         self.overlap_branches = int(train_kwargs.get("overlap_branches", os.environ.get("MM_OVERLAP_BRANCHES", "0")))
+        if self.pseudo_label_source == "teacher":
+            # checked whatever lambda_pl is: a schedule that starts at 0 must not hide a configuration that cannot run later
+            why = ("ema_decay is None (the teacher is the EMA of the weights)" if self.ema_decay is None else
+                   "overlap_metadata is on" if self.overlap_metadata else
+                   f"overlap_branches is {self.overlap_branches}" if self.overlap_branches != 0 else None)
+            if why is not None:
+                raise ValueError(f"train_kwargs['pseudo_label_source'] = 'teacher' is refused: {why}; the teacher pass runs on the "
+                                 "step's one stream (the side-stream modes are experimental and not extended to it)")
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -236,6 +261,43 @@ class TrainModel(nn.Module):
             out.append(v)
         return out
 
+    @torch.no_grad()
+    def _teacher_labels(self, batch_2d, batch_3d, first_row=0):
+        """``pseudo_label_source="teacher"``: ([labels for the 2D head, labels for the 3D head], kept share [2]) of the target rows,
+        computed by the teacher before the student's forward is queued.  ``batch_2d``: the target images; ``batch_3d``: a dict the
+        3D net may write to (Net3DSeg.forward replaces ``x[1]`` by the gated features) whose point rows ``[first_row:]`` are the
+        target's - in the joined step the [source | target] tensors, whose coordinate tensor carries the step's sparse metadata:
+        nothing is built a second time and no host read is added.  Eval mode draws no dropout mask and updates no running
+        statistic; every module's mode is put back as it was.  ``applied()`` marks the packed 16-bit weights stale twice
+        (conv2d.PARAM_EPOCH): the eager eval trunk repacks on first use, the student's graphs repack as their first node anyway."""
+        from . import gradsink, pselab
+
+        if self.ema is None:
+            raise RuntimeError("pseudo_label_source='teacher': the teacher is built with the optimisers (fit_step does it; before a "
+                               "bare training_step call configure_optimizers() first)")
+        n2d, n3d = self.modules_name[0], self.modules_name[1]
+        modes = [(m, m.training) for m in self.model.modules()]
+        try:
+            with self.ema.applied(), gradsink.suspended():  # no backward follows this forward: it claims no gradient sink
+                self.model.eval()
+                l2 = self(batch_2d, model_name=n2d)[0]["seg_logit"]
+                l3 = self(batch_3d, model_name=n3d)[0]["seg_logit"][first_row:]
+                ens, median = self.pseudo_labels == "ensemble", self.pl_threshold == "median"
+                # "median": threshold 0 refuses exactly the rows without a confidence (non-finite logits give NaN, or the
+                # ensemble's -1): mm_pselab_refine wants finite probabilities, and passes -100 through without reading them
+                out = pselab.teacher_labels(l2, l3, ensemble=ens, threshold=0.0 if median else self.pl_threshold, with_probs=median)
+                y2, y3, kept = out["label_2d"], out["label_3d"], out["kept"]
+                if median:  # the loaders' refinement over this batch: an exact radix select per output (mm_pselab_refine)
+                    C = int(l2.shape[1])
+                    y2 = pselab.refine_pseudo_labels(out["prob_2d"], y2, num_classes=C, device=l2.device)
+                    y3 = y2 if ens else pselab.refine_pseudo_labels(out["prob_3d"], y3, num_classes=C, device=l2.device)
+                    kept = torch.stack([(y2 != -100).sum(), (y3 != -100).sum()])
+        finally:
+            for m, was in modes:
+                m.training = was
+        self.last_teacher = {"label_2d": y2, "label_3d": y3, "kept": kept}
+        return [y2, y3], kept.to(torch.float32) / max(int(l2.shape[0]), 1)
+
     def _single_cross_entropy(self):
         """(registry weight, class weights) if the "segmentation" target of the loss registry is one ``cross_entropy`` entry."""
         sel = [(w, l) for w, t, l in self.loss._losses if t == "segmentation"]
@@ -246,7 +308,9 @@ class TrainModel(nn.Module):
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
-        pseudo = self._pseudo_labels(trg) if self.lambda_pl > 0 else None
+        teacher = self.lambda_pl > 0 and self.pseudo_label_source == "teacher"
+        pseudo = self._pseudo_labels(trg) if self.lambda_pl > 0 and not teacher else None
+        kept = None
         if self._can_join(src, trg):
             pre = self._pipelined if self._pipelined is not None and self._matches(self._pipelined, batch) else None
             self._pipelined = None
@@ -255,6 +319,14 @@ class TrainModel(nn.Module):
             else:
                 both, B = self._join(src, trg)
             P = src["x"][0].shape[0]  # point rows [0, P) are the source's
+            if teacher:
+                # the teacher's 3D pass runs over the joined rows with the step's own sparse metadata: attached by prefetch(), else
+                # built here once through prepare(), which attaches it for the student's InputLayer to find
+                prep = getattr(self.model[n3d], "prepare", None)
+                if prep is not None and getattr(both["x"][0], "_mm_metadata", None) is None:
+                    with domains.split(B):
+                        prep(both)
+                pseudo, kept = self._teacher_labels({k: trg[k] for k in ("img", "depth", "img_indices")}, {"x": list(both["x"])}, P)
             with domains.split(B):
                 dev = both["img"].device
                 step_start = torch.cuda.current_stream(dev).record_event()
@@ -331,6 +403,9 @@ class TrainModel(nn.Module):
             xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
         else:
+            if teacher:
+                own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
+                pseudo, kept = self._teacher_labels(own, own)
             p2d, _, _, aux2d = self(src, model_name=n2d)
             p3d, _, aux3d = self(src, model_name=n3d)
             seg2d = self.loss("segmentation", pred=p2d["seg_logit"], gt=src["seg_label"])
@@ -355,6 +430,8 @@ class TrainModel(nn.Module):
             self.last_logs[f"{stage}/pl_loss_tgt_2d"], self.last_logs[f"{stage}/pl_loss_tgt_3d"] = pl2d, pl3d
             loss_2d = loss_2d + self.lambda_pl * pl2d
             loss_3d = loss_3d + self.lambda_pl * pl3d
+        if kept is not None:
+            self.last_logs[f"{stage}/pl_kept_2d"], self.last_logs[f"{stage}/pl_kept_3d"] = kept[0], kept[1]
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
