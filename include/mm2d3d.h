@@ -395,6 +395,28 @@ int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
 int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* stats,
                const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
+/* Two-segment cross entropy with a SOFT tail (mean-teacher targets).  Rows [0, P) of logits [N, C] are the head of mm_ce2_*:
+ * int64 labels0, optional class weights, ignore_index, labels outside [0, C) skipped, weighted mean (0/0 = nan when nothing is
+ * counted); labels0 == NULL = an unlabelled head, loss 0 and zero gradient rows.  Rows [P, N) are compared with the teacher
+ * logits ta [N - P, C] (row pitch ld_a) and, if tb != NULL, tb [N - P, C] (row pitch ld_b):
+ *   target      q = softmax(ta / T), or with tb the ensemble q = 0.5 * (softmax(ta / T) + softmax(tb / T));
+ *   confidence  always at T = 1: max_c softmax(ta)_c, or with tb max_c 0.5 * (softmax(ta) + softmax(tb))_c - the float32 values
+ *               pa / pe of the device function behind mm_pselab_predict and mm_teacher_labels, bit for bit;
+ *   kept        a row is kept iff confidence >= thr in float32 (thr in [0, 1]; 0 = the caller gave no threshold), so a teacher
+ *               row with non-finite logits (a NaN confidence, or the ensemble's -1) is never kept;
+ *   loss        (1 / K) * sum over the K kept rows of sum_c q_c * (logsumexp(x) - x_c); K == 0 gives loss 0 and a zero gradient.
+ *               There is NO T^2 factor: a caller who wants the gradient scale of the distillation literature multiplies by T^2.
+ * stats[4] = head loss, head weight sum, tail loss, K as a float (read by the backward); kept (may be NULL) receives K as an exact
+ * int64.  The backward writes every one of the N rows exactly once: head rows as mm_ce2_bwd with grad_out[0], kept tail rows
+ * grad_out[1] / K * (softmax(x) - q) with q recomputed from the teacher logits (no [N, C] buffer is saved), all other rows zeros.
+ * ta may be NULL only when P == N.  C <= 32.  No atomics; fp64 partial sums combined in a fixed order: bit-stable run to run. */
+size_t mm_ce2s_ws_bytes(void);
+int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                float* stats, int64_t* kept, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                const float* stats, const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
 /* mean_i sum_c softmax(tgt)_ic (log softmax(tgt)_ic - log softmax(pred)_ic)  (EXP/train.py:157-184) */
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws,
               size_t ws_bytes, mm_stream_t stream);

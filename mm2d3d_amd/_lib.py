@@ -103,6 +103,9 @@ _PROTOS = {
     "mm_ce2_ws_bytes": (sz, []),
     "mm_ce2_fwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, i32, vp, vp, sz, vp]),
     "mm_ce2_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
+    "mm_ce2s_ws_bytes": (sz, []),
+    "mm_ce2s_fwd": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, sz, vp]),
+    "mm_ce2s_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, i32, vp]),
     "mm_kl_fwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, sz, vp]),
     "mm_kl_bwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, i32, vp]),
     "mm_lift_gather": (i32, [vp, i64, vp, i64, i32, vp, vp]),

@@ -184,6 +184,200 @@ __global__ __launch_bounds__(T) void k_ce2_bwd(const float* __restrict__ logits,
   for (int c = 0; c < C; c++) d[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
 }
 
+// ---- two-segment cross entropy with a SOFT tail (mean-teacher targets): rows [0, P) as k_ce2_* against (labels0, weight0), rows
+// [P, N) against the distribution q of the teacher logits ta (and tb: the ensemble), softened by the temperature, kept or not by
+// the row's confidence at temperature 1 - pa / pe of mm_point_predict, the value mm_teacher_labels judges the row by.
+// Staging: a workgroup is ONE wave and owns tiles of ST rows; the [rows, C] blocks of the (up to three) matrices are copied into
+// LDS with consecutive lanes on consecutive addresses, then each lane reads its own row from LDS, rows pitched to C | 1 words so
+// that the 64 lanes fall on distinct banks (the pattern of k_teacher_labels in pselab.hip).  3 x 64 x 33 words = 25,344 bytes at
+// C = 32: six workgroups per CU by LDS.  Sums: per lane fp64 over its rows in ascending order, a fixed shuffle tree per workgroup,
+// then k_ce2s_finalize over the workgroups' partials in a fixed order; the kept count is an integer carried in fp64 (exact below
+// 2^53).  No atomics of any kind.
+constexpr int ST = 64;          // rows per tile = lanes of the one wave
+constexpr int S_MAX_PART = 2048;
+
+__device__ inline void stage_rows(float* __restrict__ dst, const float* __restrict__ src, int64_t ld, int rows, int C, int pitch) {
+  for (int e = threadIdx.x; e < rows * C; e += ST) {
+    const int r = e / C, c = e - r * C;
+    dst[r * pitch + c] = src[(int64_t)r * ld + c];
+  }
+}
+
+// sum_c softmax(t * inv_t)_c * v_c over one teacher row (tm = its maximum), v_c = lse - x_c
+__device__ inline float soft_dot(const float* t, float tm, float inv_t, const float* x, float lse, int C) {
+  float s = 0.f, n = 0.f;
+  for (int c = 0; c < C; c++) {
+    const float e = expf((t[c] - tm) * inv_t);
+    s += e;
+    n += e * (lse - x[c]);
+  }
+  return n / s;
+}
+
+// partial[b] = (sum w*nll, sum w) of the head, (sum of the kept rows' soft cross entropies, kept rows) of the tail
+template <bool HAS_B>
+__global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
+                                                  const int64_t* __restrict__ labels0, const float* __restrict__ weight0, int64_t ignore,
+                                                  const float* __restrict__ ta, int ld_a, const float* __restrict__ tb, int ld_b,
+                                                  float inv_t, float thr, double* __restrict__ partial) {
+  extern __shared__ float tile[];  // [HAS_B ? 3 : 2][ST][pitch]
+  const int pitch = C | 1;
+  float* sx = tile;
+  float* sa = tile + ST * pitch;
+  float* sb = tile + 2 * ST * pitch;  // never touched without HAS_B
+  double sl0 = 0.0, sw0 = 0.0, sl1 = 0.0;
+  long long k1 = 0;
+  const int64_t ntiles = (N + ST - 1) / ST;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t row0 = t * ST;
+    const int rows = (int)((N - row0) < (int64_t)ST ? (N - row0) : (int64_t)ST);
+    // the tile's tail rows are [h, rows): teacher row (row0 + r - P)
+    const int h = (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
+    __syncthreads();  // the previous tile's rows have been read
+    stage_rows(sx, logits + row0 * ld, ld, rows, C, pitch);
+    if (h < rows) {
+      const int64_t t0 = row0 + h - P;
+      stage_rows(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
+      if (HAS_B) stage_rows(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
+    }
+    __syncthreads();
+    const int r = threadIdx.x;
+    const float* x = sx + r * pitch;
+    if (r < h) {
+      const int64_t y = labels0 ? labels0[row0 + r] : ignore;
+      if (labels0 && y != ignore && y >= 0 && y < C) {
+        float m = x[0];
+        for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
+        float s = 0.f;
+        for (int c = 0; c < C; c++) s += expf(x[c] - m);
+        const float nll = (m + logf(s)) - x[y];
+        const float w = weight0 ? weight0[y] : 1.f;
+        sl0 += (double)(w * nll);
+        sw0 += (double)w;
+      }
+    } else if (r < rows) {
+      const float* a = sa + r * pitch;
+      const float* b = sb + r * pitch;
+      const MMPointPred pr = mm_point_predict<HAS_B>(a, b, C);
+      if ((HAS_B ? pr.pe : pr.pa) >= thr) {  // a NaN confidence (or the ensemble's -1 of a non-finite row) is never kept
+        float m = x[0];
+        for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
+        float s = 0.f;
+        for (int c = 0; c < C; c++) s += expf(x[c] - m);
+        const float lse = m + logf(s);
+        float v = soft_dot(a, a[pr.ia], inv_t, x, lse, C);
+        if (HAS_B) v = 0.5f * (v + soft_dot(b, b[pr.ib], inv_t, x, lse, C));
+        sl1 += (double)v;
+        k1 += 1;
+      }
+    }
+  }
+  const double a0 = wave_sum64(sl0), b0 = wave_sum64(sw0), a1 = wave_sum64(sl1), b1 = wave_sum64((double)k1);
+  if (threadIdx.x == 0) {
+    double* o = partial + 4 * (int64_t)blockIdx.x;
+    o[0] = a0, o[1] = b0, o[2] = a1, o[3] = b1;
+  }
+}
+
+// head: a / b (0/0 = nan, as k_ce_finalize) or 0 when unlabelled; tail: the mean over the K kept rows, 0 when K == 0
+__global__ __launch_bounds__(64) void k_ce2s_finalize(const double* __restrict__ partial, int nb, int head_labelled,
+                                                       float* __restrict__ out /*[4]: loss0, sum_w0, loss1, K*/,
+                                                       int64_t* __restrict__ kept) {
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < nb; i += 64) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] += partial[4 * i + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) v[k] = wave_sum64(v[k]);
+  if (threadIdx.x == 0) {
+    out[0] = head_labelled ? (float)(v[0] / v[1]) : 0.f;
+    out[1] = (float)v[1];
+    out[2] = v[3] > 0.0 ? (float)(v[2] / v[3]) : 0.f;
+    out[3] = (float)v[3];
+    if (kept) kept[0] = (int64_t)v[3];  // integer-valued partials: exact
+  }
+}
+
+// One tile per workgroup, every row written once: the gradient rows are formed in place in the staged logits tile and leave it
+// with consecutive lanes on consecutive addresses.  Head: gout[0] * w[y] / sum_w * (softmax - onehot), as k_ce2_bwd; kept tail
+// rows: gout[1] / K * (softmax - q), q recomputed from the teacher rows; every other row: zeros.
+template <bool HAS_B>
+__global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
+                                                  const int64_t* __restrict__ labels0, const float* __restrict__ weight0, int64_t ignore,
+                                                  const float* __restrict__ ta, int ld_a, const float* __restrict__ tb, int ld_b,
+                                                  float inv_t, float thr, const float* __restrict__ stats,
+                                                  const float* __restrict__ gout, float* __restrict__ dlogits, int ld_d) {
+  extern __shared__ float tile[];  // [HAS_B ? 3 : 2][ST][pitch]
+  const int pitch = C | 1;
+  float* sx = tile;
+  float* sa = tile + ST * pitch;
+  float* sb = tile + 2 * ST * pitch;
+  const int64_t row0 = (int64_t)blockIdx.x * ST;
+  const int rows = (int)((N - row0) < (int64_t)ST ? (N - row0) : (int64_t)ST);
+  const int h = (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
+  stage_rows(sx, logits + row0 * ld, ld, rows, C, pitch);
+  if (h < rows) {
+    const int64_t t0 = row0 + h - P;
+    stage_rows(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
+    if (HAS_B) stage_rows(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
+  }
+  __syncthreads();
+  const int r = threadIdx.x;
+  if (r < rows) {
+    float* x = sx + r * pitch;
+    bool live;
+    int y = -1;
+    float k = 0.f;
+    MMPointPred pr;
+    const float* a = sa + r * pitch;
+    const float* b = sb + r * pitch;
+    if (r < h) {
+      const int64_t yl = labels0 ? labels0[row0 + r] : ignore;
+      live = labels0 && yl != ignore && yl >= 0 && yl < C;
+      if (live) {
+        y = (int)yl;
+        k = gout[0] * (weight0 ? weight0[y] : 1.f) / stats[1];
+      }
+    } else {
+      pr = mm_point_predict<HAS_B>(a, b, C);
+      live = (HAS_B ? pr.pe : pr.pa) >= thr;
+      if (live) k = gout[1] / stats[3];
+    }
+    if (!live) {
+      for (int c = 0; c < C; c++) x[c] = 0.f;
+    } else {
+      float m = x[0];
+      for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
+      float s = 0.f;
+      for (int c = 0; c < C; c++) s += expf(x[c] - m);
+      const float inv = 1.f / s;
+      if (r < h) {
+        for (int c = 0; c < C; c++) x[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
+      } else {
+        const float ma = a[pr.ia];
+        float za = 0.f, zb = 1.f, mb = 0.f;
+        for (int c = 0; c < C; c++) za += expf((a[c] - ma) * inv_t);
+        if (HAS_B) {
+          mb = b[pr.ib], zb = 0.f;
+          for (int c = 0; c < C; c++) zb += expf((b[c] - mb) * inv_t);
+        }
+        for (int c = 0; c < C; c++) {
+          float q = expf((a[c] - ma) * inv_t) / za;
+          if (HAS_B) q = 0.5f * (q + expf((b[c] - mb) * inv_t) / zb);
+          x[c] = k * (expf(x[c] - m) * inv - q);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  float* d = dlogits + row0 * ld_d;
+  for (int e = threadIdx.x; e < rows * C; e += ST) {
+    const int rr = e / C, c = e - rr * C;
+    d[(int64_t)rr * ld_d + c] = sx[rr * pitch + c];
+  }
+}
+
 // partial[b] = sum_i sum_c q_ic (log q_ic - log p_ic)
 __global__ __launch_bounds__(T) void k_kl_fwd(const float* __restrict__ pred, int ld_p, const float* __restrict__ tgt,
                                                int ld_t, int64_t N, int C, double* __restrict__ partial) {
@@ -372,6 +566,65 @@ int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
   if (N == 0) return MM_OK;
   hipLaunchKernelGGL(k_ce2_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1,
                      ignore_index, stats, grad_out, dlogits, ld_d);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+size_t mm_ce2s_ws_bytes() { return mm_align((size_t)S_MAX_PART * 4 * sizeof(double)) + 256; }
+
+static int ce2s_check(const float* logits, int ld, int64_t N, int64_t P, int C, const float* ta, int ld_a, const float* tb, int ld_b,
+                      float temperature, float thr) {
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C, "ce2s: bad C");
+  MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N && N <= (int64_t)ST * 0x7fffffff, "ce2s: the split must lie in [0, N]");
+  MM_CHECK_ARG(logits || N == 0, "ce2s: null logits");
+  MM_CHECK_ARG(ta || (P == N && !tb), "ce2s: tail rows without teacher logits");
+  MM_CHECK_ARG((!ta || ld_a >= C) && (!tb || ld_b >= C), "ce2s: teacher row pitch below C");
+  MM_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "ce2s: the temperature must be a finite number > 0");
+  MM_CHECK_ARG(thr >= 0.f && thr <= 1.f, "ce2s: the threshold must lie in [0, 1]");
+  return MM_OK;
+}
+
+// stats[4] = head loss, head weight sum, tail loss, kept rows K (as a float); kept[0] = K exactly; see include/mm2d3d.h
+int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr, float* stats,
+                int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr)) return rc;
+  MM_CHECK_ARG(stats, "ce2s: null stats");
+  if (ws_bytes < (size_t)S_MAX_PART * 4 * sizeof(double)) {
+    mm_set_error("ce2s: workspace too small");
+    return MM_ERR_WORKSPACE;
+  }
+  int64_t nt = mm_cdiv(N > 0 ? N : 1, (int64_t)ST);
+  const int nb = (int)(nt > S_MAX_PART ? S_MAX_PART : nt);
+  const size_t lds = (size_t)(tb ? 3 : 2) * ST * (C | 1) * sizeof(float);
+  const float inv_t = 1.f / temperature;
+  if (tb)
+    hipLaunchKernelGGL(k_ce2s_fwd<true>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
+                       ld_b, inv_t, thr, (double*)ws);
+  else
+    hipLaunchKernelGGL(k_ce2s_fwd<false>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
+                       ld_b, inv_t, thr, (double*)ws);
+  hipLaunchKernelGGL(k_ce2s_finalize, dim3(1), dim3(64), 0, s, (const double*)ws, nb, labels0 ? 1 : 0, stats, kept);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
+  if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr)) return rc;
+  MM_CHECK_ARG(ld_d >= C, "ce2s: gradient row pitch below C");
+  if (N == 0) return MM_OK;
+  MM_CHECK_ARG(stats && grad_out && dlogits, "ce2s: null stats, grad_out or dlogits");
+  const unsigned nb = (unsigned)mm_cdiv(N, (int64_t)ST);
+  const size_t lds = (size_t)(tb ? 3 : 2) * ST * (C | 1) * sizeof(float);
+  const float inv_t = 1.f / temperature;
+  if (tb)
+    hipLaunchKernelGGL(k_ce2s_bwd<true>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
+                       ld_b, inv_t, thr, stats, grad_out, dlogits, ld_d);
+  else
+    hipLaunchKernelGGL(k_ce2s_bwd<false>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
+                       ld_b, inv_t, thr, stats, grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

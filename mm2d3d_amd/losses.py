@@ -148,6 +148,107 @@ def cross_entropy_pair(pred, split, gt_head=None, gt_tail=None, weight_head=None
                                      weights(weight_tail, "weight_tail"), int(ignore_index), bits)
 
 
+def _row_pitched(t):
+    """fp32 [N, C] that the row kernels read in place: a row-pitched view (stride(1) == 1) stays, anything else is copied."""
+    t = t.to(F32)
+    N, C = t.shape
+    if t.stride(1) != 1 or (N > 1 and t.stride(0) < C):
+        t = t.contiguous()
+    return t, (t.stride(0) if N > 1 else C)
+
+
+class _CrossEntropySoftPairFn(torch.autograd.Function):
+    """Rows [0, split) of ``logits`` against (labels0, weight0), rows [split, N) against the softened distribution of the teacher
+    logits: one forward call, and ONE backward launch that writes the whole gradient, recomputing the teacher's distribution
+    (csrc/loss.hip k_ce2s_*)."""
+
+    @staticmethod
+    def forward(ctx, logits, split, labels0, weight0, ta, tb, temperature, thr, ignore_index):
+        _lib.require_cuda(logits, "pred")
+        L = _lib.lib()
+        ctx.in_dtype = logits.dtype
+        logits, ld = _row_pitched(logits)
+        ta, ld_a = _row_pitched(ta)
+        tb, ld_b = _row_pitched(tb) if tb is not None else (None, 0)
+        N, C = logits.shape
+        stats = torch.empty(4, dtype=F32, device=logits.device)
+        kept = torch.empty((), dtype=torch.int64, device=logits.device)
+        ws = _lib.workspace.get(int(L.mm_ce2s_ws_bytes()), logits.device)
+        check(L.mm_ce2s_fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                            temperature, thr, ptr(stats), ptr(kept), ptr(ws), ws.numel(), stream()), "ce2s_fwd")
+        ctx.save_for_backward(logits, labels0, weight0, ta, tb, stats)
+        ctx.args = (ld, ld_a, ld_b, split, temperature, thr, ignore_index)
+        ctx.mark_non_differentiable(kept)
+        return stats[0], stats[2], kept
+
+    @staticmethod
+    def backward(ctx, g0, g1, _):
+        L = _lib.lib()
+        logits, labels0, weight0, ta, tb, stats = ctx.saved_tensors
+        ld, ld_a, ld_b, split, temperature, thr, ignore_index = ctx.args
+        N, C = logits.shape
+        d = torch.empty((N, C), dtype=F32, device=logits.device)
+        g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
+        check(L.mm_ce2s_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                            temperature, thr, ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd")
+        if ctx.in_dtype != F32:
+            d = d.to(ctx.in_dtype)
+        return d, None, None, None, None, None, None, None, None
+
+
+def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, weight_head=None, temperature=1.0, threshold=None,
+                            ignore_index=-100):
+    """``(loss_head, loss_tail, kept)``: rows ``[0, split)`` of ``pred`` [N, C] against the labels ``gt_head`` exactly as in
+    :func:`cross_entropy_pair` (``None`` = unlabelled: loss 0, zero gradient rows), rows ``[split, N)`` against a teacher's
+    DISTRIBUTION - the consistency loss of mean-teacher training, of which hard pseudo labels are the limit.
+
+    ``teacher`` [N - split, C]: teacher logits, detached here.  The target is ``q = softmax(teacher / temperature)``, or with
+    ``teacher_other`` (same shape) the ensemble ``0.5 * (softmax(teacher / T) + softmax(teacher_other / T))``.  A row's confidence
+    is the largest probability of that target at temperature 1 - the float32 value ``pselab.teacher_labels`` judges the row by,
+    bit for bit - and with ``threshold`` in (0, 1] only rows whose confidence is ``>= threshold`` are kept; ``None`` keeps every
+    row whose teacher logits are finite.  ``loss_tail`` = mean over the kept rows of ``sum_c q_c * (logsumexp(x) - x_c)``, i.e.
+    KL(q || softmax(x)) plus the entropy of q; there is no ``T^2`` factor.  Nothing kept: loss 0 and a zero gradient.  ``kept``:
+    the number of kept rows, an int64 device scalar.
+
+    One autograd node and one backward launch write the whole gradient of ``pred``; all three matrices may be row-pitched views
+    (``stride(1) == 1``) and are read in place."""
+    who = "cross_entropy_soft_pair"
+    if pred.dim() != 2:
+        raise ValueError(f"{who}: pred must be [N, C]")
+    N, C, split = int(pred.shape[0]), int(pred.shape[1]), int(split)
+    if not 0 <= split <= N:
+        raise ValueError(f"{who}: split {split} outside [0, {N}]")
+    if C > 32:
+        raise ValueError(f"{who}: {C} classes, the row kernels take at most 32")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0.0 < float(temperature) < float("inf"):
+        raise ValueError(f"{who}: temperature must be a finite number > 0, not {temperature!r}")
+    if threshold is not None and (isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold <= 1.0):
+        raise ValueError(f"{who}: threshold must be None or a number in (0, 1], not {threshold!r}")
+
+    def logits(t, which):
+        if not torch.is_tensor(t) or tuple(t.shape) != (N - split, C):
+            got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"{who}: {which} is {got}, the tail has [{N - split}, {C}] logits")
+        t = t.detach().to(device=pred.device)
+        # an empty tensor has no address: an empty tail passes one row that no row of pred reads (as cross_entropy_pair's labels)
+        return t if N - split else t.new_zeros((1, C))
+
+    teacher = logits(teacher, "teacher")
+    if teacher_other is not None:
+        teacher_other = logits(teacher_other, "teacher_other")
+    if gt_head is not None:
+        gt_head = gt_head.to(device=pred.device, dtype=torch.int64).contiguous()
+        if gt_head.dim() != 1 or gt_head.shape[0] != split:
+            raise ValueError(f"{who}: gt_head has shape {tuple(gt_head.shape)}, its segment has {split} rows")
+        if not split:
+            gt_head = gt_head.new_full((1,), ignore_index)  # a labelled head without rows: 0/0, as cross_entropy_pair
+    weight_head = _device_weight(weight_head, pred.device)
+    if weight_head is not None and weight_head.numel() != C:
+        raise ValueError(f"{who}: weight_head has {weight_head.numel()} entries for {C} classes")
+    return _CrossEntropySoftPairFn.apply(pred, split, gt_head, weight_head, teacher, teacher_other, float(temperature),
+                                         0.0 if threshold is None else float(threshold), int(ignore_index))
+
+
 class _KLFn(torch.autograd.Function):
     """mean_i sum_c softmax(t)_ic * (log_softmax(t)_ic - log_softmax(p)_ic); gradient flows to p only (t is detached)."""
 

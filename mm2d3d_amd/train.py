@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib, domains
 from .ddp import GradAllReducer, ranks_share_a_gpu
-from .losses import CrossEntropy, Loss, cross_entropy_pair, cross_modal_loss
+from .losses import CrossEntropy, Loss, cross_entropy_pair, cross_entropy_soft_pair, cross_modal_loss
 from .metrics import SegIoU
 
 
@@ -73,6 +73,27 @@ class TrainModel(nn.Module):
         if not (thr is None or thr == "median" or (isinstance(thr, (int, float)) and not isinstance(thr, bool) and 0.0 < thr <= 1.0)):
             raise ValueError(f"train_kwargs['pl_threshold'] must be None, 'median' or a number in (0, 1], not {thr!r}")
         self.last_teacher = None
+        # What the target rows learn from (consulted only with ``lambda_pl`` > 0).  "hard" (default): int64 pseudo labels, as above,
+        # launch for launch the step without the option.  "soft": the teacher's DISTRIBUTION - each head's target rows take
+        # losses.cross_entropy_soft_pair against softmax(teacher logits / ``pl_temperature``) ("own": the 2D head the teacher's 2D
+        # logits, the 3D head its 3D logits; "ensemble": both heads the average of the two softmaxes), rows kept by their
+        # confidence at temperature 1 against ``pl_threshold`` (None or a float; "median" works on labels and is refused), mean
+        # over the kept rows, no T^2 factor.  Source "teacher": the teacher pass runs as above without the label launch, and
+        # ``last_teacher`` = dict(logit_2d, logit_3d, kept); source "batch": the target batch carries ``teacher_logit_2d`` /
+        # ``teacher_logit_3d`` [n, C] (a frozen teacher of the caller's own).  Both log ``train/pl_kept_2d`` / ``_3d``.
+        self.pl_targets = train_kwargs.get("pl_targets", "hard")
+        if self.pl_targets not in ("hard", "soft"):
+            raise ValueError(f"train_kwargs['pl_targets'] must be 'hard' or 'soft', not {self.pl_targets!r}")
+        T = train_kwargs.get("pl_temperature", 1.0)
+        if isinstance(T, bool) or not isinstance(T, (int, float)) or not 0.0 < T < float("inf"):
+            raise ValueError(f"train_kwargs['pl_temperature'] must be a finite number > 0, not {T!r}")
+        self.pl_temperature = float(T)
+        if self.pl_targets == "hard" and self.pl_temperature != 1.0:
+            raise ValueError(f"train_kwargs['pl_temperature'] = {T!r} with pl_targets='hard': an arg-max has no temperature "
+                             "(it would be silently meaningless); use pl_targets='soft'")
+        if self.pl_targets == "soft" and thr == "median":
+            raise ValueError("train_kwargs['pl_threshold'] = 'median' is refused with pl_targets='soft': the refinement works on "
+                             "labels; give a number in (0, 1] or None")
         self.broadcast_buffers = bool(int(train_kwargs.get("broadcast_buffers", os.environ.get("MM_DDP_BROADCAST_BUFFERS", "1"))))  # torch DDP default (run.py:264-268)
         # One pass per network over [source scenes | target scenes] instead of one per domain: half the launches, twice
         # the rows per launch.  The batch-norm layers keep per-domain statistics (mm2d3d_amd/domains.py), so the
@@ -261,6 +282,35 @@ class TrainModel(nn.Module):
             out.append(v)
         return out
 
+    def _teacher_logits(self, trg):
+        """``pl_targets="soft"`` with the batch source: (teacher logits for the 2D head, for the 3D head) of a target batch, checked
+        on the host before anything is queued."""
+        n = int(trg["x"][0].shape[0])
+        out = []
+        for k in ("teacher_logit_2d", "teacher_logit_3d"):
+            if k not in trg:
+                raise KeyError(f"lambda_pl > 0 with pl_targets='soft' but the target batch has no '{k}': give the teacher's logits "
+                               "[n, C] of the target rows, or train with pseudo_label_source='teacher'")
+            v = trg[k]
+            if not torch.is_tensor(v) or v.dim() != 2 or int(v.shape[0]) != n or not v.is_floating_point():
+                raise ValueError(f"'{k}' holds {(tuple(v.shape), v.dtype) if torch.is_tensor(v) else type(v).__name__}, the target "
+                                 f"batch has {n} point rows: float logits [{n}, C] are expected")
+            out.append(v)
+        if out[0].shape != out[1].shape:
+            raise ValueError(f"'teacher_logit_2d' is {tuple(out[0].shape)} and 'teacher_logit_3d' is {tuple(out[1].shape)}")
+        return out
+
+    def _soft_targets(self, l2, l3):
+        """Per head (teacher, teacher_other) of losses.cross_entropy_soft_pair: "own" = the head's own modality, "ensemble" = both."""
+        return [(l2, l3), (l2, l3)] if self.pseudo_labels == "ensemble" else [(l2, None), (l3, None)]
+
+    def _pl_pair(self, logits, split, gt_head, target, weight_head=None):
+        """(loss of the head rows, pseudo-label loss of the target rows, kept rows or None) of one head's logits."""
+        if self.pl_targets == "soft":
+            return cross_entropy_soft_pair(logits, split, gt_head, target[0], target[1], weight_head=weight_head,
+                                           temperature=self.pl_temperature, threshold=self.pl_threshold)
+        return (*cross_entropy_pair(logits, split, gt_head, target, weight_head=weight_head), None)
+
     @torch.no_grad()
     def _teacher_labels(self, batch_2d, batch_3d, first_row=0):
         """``pseudo_label_source="teacher"``: ([labels for the 2D head, labels for the 3D head], kept share [2]) of the target rows,
@@ -282,6 +332,12 @@ class TrainModel(nn.Module):
                 self.model.eval()
                 l2 = self(batch_2d, model_name=n2d)[0]["seg_logit"]
                 l3 = self(batch_3d, model_name=n3d)[0]["seg_logit"][first_row:]
+                if self.pl_targets == "soft":
+                    # no label launch: the loss calls read the logits themselves.  They now outlive the student's forward and
+                    # backward; both are tensors of their own (lifting's and the linear head's torch.empty outputs, l3 a row
+                    # slice of one) - neither a workspace nor a static graph buffer (eval forwards are eager): no copy is needed
+                    self.last_teacher = {"logit_2d": l2, "logit_3d": l3, "kept": None}  # "kept": filled by the loss calls
+                    return self._soft_targets(l2, l3), None
                 ens, median = self.pseudo_labels == "ensemble", self.pl_threshold == "median"
                 # "median": threshold 0 refuses exactly the rows without a confidence (non-finite logits give NaN, or the
                 # ensemble's -1): mm_pselab_refine wants finite probabilities, and passes -100 through without reading them
@@ -309,7 +365,10 @@ class TrainModel(nn.Module):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
         teacher = self.lambda_pl > 0 and self.pseudo_label_source == "teacher"
-        pseudo = self._pseudo_labels(trg) if self.lambda_pl > 0 and not teacher else None
+        soft = self.pl_targets == "soft"
+        pseudo = None
+        if self.lambda_pl > 0 and not teacher:
+            pseudo = self._soft_targets(*self._teacher_logits(trg)) if soft else self._pseudo_labels(trg)
         kept = None
         if self._can_join(src, trg):
             pre = self._pipelined if self._pipelined is not None and self._matches(self._pipelined, batch) else None
@@ -391,15 +450,15 @@ class TrainModel(nn.Module):
                 # one pass over each head's [source | target] logits: source labels with the entry's class weights, pseudo labels
                 # without; one backward launch writes the head's whole gradient
                 (rw, cw), gt = single, src["seg_label"]
-                seg2d, pl2d = cross_entropy_pair(l2d, P, gt, pseudo[0], weight_head=cw)
-                seg3d, pl3d = cross_entropy_pair(l3d, P, gt, pseudo[1], weight_head=cw)
+                seg2d, pl2d, k2 = self._pl_pair(l2d, P, gt, pseudo[0], cw)
+                seg3d, pl3d, k3 = self._pl_pair(l3d, P, gt, pseudo[1], cw)
                 seg2d, seg3d = rw * seg2d, rw * seg3d
             else:
                 seg2d = self.loss("segmentation", pred=l2d[:P], gt=src["seg_label"])
                 seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
                 if pseudo is not None:
-                    pl2d = cross_entropy_pair(l2d, P, None, pseudo[0])[1]
-                    pl3d = cross_entropy_pair(l3d, P, None, pseudo[1])[1]
+                    _, pl2d, k2 = self._pl_pair(l2d, P, None, pseudo[0])
+                    _, pl3d, k3 = self._pl_pair(l3d, P, None, pseudo[1])
             xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
         else:
@@ -417,8 +476,8 @@ class TrainModel(nn.Module):
             xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
                                                aux3d["seg_logit_point"])
             if pseudo is not None:
-                pl2d = cross_entropy_pair(p2d["seg_logit"], 0, None, pseudo[0])[1]
-                pl3d = cross_entropy_pair(p3d["seg_logit"], 0, None, pseudo[1])[1]
+                _, pl2d, k2 = self._pl_pair(p2d["seg_logit"], 0, None, pseudo[0])
+                _, pl3d, k3 = self._pl_pair(p3d["seg_logit"], 0, None, pseudo[1])
         self.last_logs = {
             f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
@@ -430,6 +489,11 @@ class TrainModel(nn.Module):
             self.last_logs[f"{stage}/pl_loss_tgt_2d"], self.last_logs[f"{stage}/pl_loss_tgt_3d"] = pl2d, pl3d
             loss_2d = loss_2d + self.lambda_pl * pl2d
             loss_3d = loss_3d + self.lambda_pl * pl3d
+        if pseudo is not None and soft:  # the rows the two loss calls kept: counted in their forward launches
+            counts = torch.stack((k2, k3))
+            kept = counts.to(torch.float32) / max(int(trg["x"][0].shape[0]), 1)
+            if teacher:
+                self.last_teacher["kept"] = counts
         if kept is not None:
             self.last_logs[f"{stage}/pl_kept_2d"], self.last_logs[f"{stage}/pl_kept_3d"] = kept[0], kept[1]
         return loss_2d + loss_3d
