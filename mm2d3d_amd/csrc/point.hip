@@ -364,23 +364,27 @@ int mm_linear_bwd(const float* x, int ld_x, const float* dy, int ld_dy, int64_t 
   if ((size_t)64 * (Cin + Cout) * 4 > 64 * 1024)
     MM_HIP(hipFuncSetAttribute((const void*)k_linear_bwd_w, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * (Cin + Cout) * 4));
   const bool fast = linear16_ok(x, ld_x, Cin, Cout);
+  const bool fast_dx = fast && ld_dx % 4 == 0 && ((uintptr_t)dx % 16) == 0;
+  int nb = (int)mm_cdiv(N > 0 ? N : 1, fast ? 4096 : 2048);  // the row-per-thread kernel streams 34 rows per thread at 558k rows
+  if (nb > MAX_PART) nb = MAX_PART;
+  if (fast && nb > 128) nb = 128;
+  const int ne = Cout * Cin + Cout;
+  // every argument and workspace check comes before the first launch: an error return has written nothing
+  if (dx && N && !fast_dx)
+    MM_CHECK_ARG((int64_t)(N * Cin) < (1ll << 32) - 4096, "k_linear_bwd_x: too many elements for 32-bit thread indices");
+  if (dw && ws_bytes < (size_t)nb * ne * sizeof(double) + (db ? 0 : Cout * sizeof(float))) {
+    mm_set_error("linear_bwd: workspace too small");
+    return MM_ERR_WORKSPACE;
+  }
   if (dx && N) {
-    if (fast && ld_dx % 4 == 0 && ((uintptr_t)dx % 16) == 0)
+    if (fast_dx) {
       hipLaunchKernelGGL(k_linear16_bwd_x, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, dy, ld_dy, N, Cout, w, dx, ld_dx, accumulate_dx);
-    else
-      MM_CHECK_ARG((int64_t)(N * Cin) < (1ll << 32) - 4096, "k_linear_bwd_x: too many elements for 32-bit thread indices");
+    } else {
       hipLaunchKernelGGL(k_linear_bwd_x, dim3((unsigned)mm_cdiv(N * Cin, T)), dim3(T), 0, s, dy, ld_dy, N, Cin, Cout, w, dx, ld_dx,
                          accumulate_dx);
+    }
   }
   if (dw) {
-    int nb = (int)mm_cdiv(N > 0 ? N : 1, fast ? 4096 : 2048);  // the row-per-thread kernel streams 34 rows per thread at 558k rows
-    if (nb > MAX_PART) nb = MAX_PART;
-    if (fast && nb > 128) nb = 128;
-    const int ne = Cout * Cin + Cout;
-    if (ws_bytes < (size_t)nb * ne * sizeof(double)) {
-      mm_set_error("linear_bwd: workspace too small");
-      return MM_ERR_WORKSPACE;
-    }
     double* partial = (double*)ws;
     if (fast)
       hipLaunchKernelGGL(k_linear16_bwd_w, dim3(nb), dim3(T), 0, s, x, ld_x, dy, ld_dy, N, Cout, partial);
@@ -389,10 +393,6 @@ int mm_linear_bwd(const float* x, int ld_x, const float* dy, int ld_dy, int64_t 
                          partial);
     // bias partials live behind the weight partials; when db is null they are summed into a scratch tail of ws
     float* dbp = db ? db : (float*)((char*)ws + (size_t)nb * ne * sizeof(double));
-    if (!db && ws_bytes < (size_t)nb * ne * sizeof(double) + Cout * sizeof(float)) {
-      mm_set_error("linear_bwd: workspace too small");
-      return MM_ERR_WORKSPACE;
-    }
     hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)mm_cdiv(ne, 64)), dim3(64), 0, s, partial, nb, ne, dw, Cout * Cin, dbp,
                        accumulate_w);
   }
