@@ -422,15 +422,6 @@ int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N
               size_t ws_bytes, mm_stream_t stream);
 int mm_kl_bwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, const float* grad_out,
               float* dpred, int ld_d, mm_stream_t stream);
-/* 2D->3D lifting (EXP/2d_net/model.py:131-137,166-173): out[p][c] = seg[pix_off[p] + c*chan_stride];
- * backward: dseg[upix_off[u] + c*chan_stride] = sum over the points of unique pixel u (CSR, ascending) */
-int mm_lift_gather(const float* seg, int64_t chan_stride, const int64_t* pix_off, int64_t N, int C, float* out,
-                   mm_stream_t stream);
-int mm_lift_scatter(const float* dout, int C, const int64_t* upix_off, const int32_t* csr_off,
-                    const int32_t* csr_pts, int64_t n_unique, int64_t chan_stride, float* dseg, mm_stream_t stream);
-/* backward of the lifting without compaction: order = stable argsort of the pixel keys, first[e] marks run starts */
-int mm_lift_scatter_runs(const float* dout, int C, const int64_t* order, const unsigned char* first,
-                         const int64_t* sorted_off, int64_t N, int64_t chan_stride, float* dseg, mm_stream_t stream);
 /* The lifting index built on the device in three launches (csrc/lift.hip; round 4).  rc: device int64 [n, 2] (row, col) of every
  * point, scenes concatenated (img_indices of lib/dataset/__init__.py:74,111); counts: device int64 [nb] points per scene.
  * key [n] = pixel id (b*H + row)*W + col (rows / cols clamped into the map; err[0] = 1 if one was outside - the reference asserts

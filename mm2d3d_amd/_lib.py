@@ -108,9 +108,6 @@ _PROTOS = {
     "mm_ce2s_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, i32, vp]),
     "mm_kl_fwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, sz, vp]),
     "mm_kl_bwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, i32, vp]),
-    "mm_lift_gather": (i32, [vp, i64, vp, i64, i32, vp, vp]),
-    "mm_lift_scatter": (i32, [vp, i32, vp, vp, vp, i64, i64, vp, vp]),
-    "mm_lift_scatter_runs": (i32, [vp, i32, vp, vp, vp, i64, i64, vp, vp]),
     "mm_lift_index_ws_bytes": (sz, [i64]),
     "mm_lift_index": (i32, [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "mm_lift_gather_key": (i32, [vp, i64, i64, i64, i64, vp, i64, i32, i32, i32, vp, vp]),

@@ -103,6 +103,8 @@ int mm_lift_index(const int64_t* rc, const int64_t* counts, int nb, int64_t n, i
   MM_CHECK_ARG(nb >= 0 && nb <= MAXB && n >= 0 && H > 0 && W > 0 && (int64_t)nb * H * W < (1ll << 31) && n < (1ll << 31),
                "lift_index: bad shape (nb=%d n=%lld H=%d W=%d)", nb, (long long)n, H, W);
   if (n == 0) return MM_OK;
+  MM_CHECK_ARG(nb >= 1, "lift_index: %lld points in no scene", (long long)n);
+  MM_CHECK_ARG(rc && counts && key && skey && order && err && ws, "lift_index: null rc, counts, key, skey, order, err or workspace");
   size_t tb = sort_bytes(n);
   if (ws_bytes < tb) {
     mm_set_error("lift_index: workspace too small (%zu < %zu)", ws_bytes, tb);
@@ -120,8 +122,10 @@ int mm_lift_index(const int64_t* rc, const int64_t* counts, int nb, int64_t n, i
 // out[p][c] = seg[b*sb + row*sy + col*sx + c*sc] at the pixel of point p
 int mm_lift_gather_key(const float* seg, int64_t sb, int64_t sy, int64_t sx, int64_t sc, const int32_t* key, int64_t N, int C, int H, int W,
                        float* out, hipStream_t s) {
-  MM_CHECK_ARG(N * C < (1ll << 31) && C > 0, "lift_gather: too many elements");
+  MM_CHECK_ARG(C > 0 && N >= 0 && N < (1ll << 31) && N * C < (1ll << 31), "lift_gather: too many elements");
+  MM_CHECK_ARG(H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "lift_gather: bad map shape (H=%d W=%d)", H, W);
   if (N == 0) return MM_OK;
+  MM_CHECK_ARG(seg && key && out, "lift_gather: null seg, key or out");
   hipLaunchKernelGGL(k_lift_gather_key, dim3((unsigned)mm_cdiv(N * C, T)), dim3(T), 0, s, seg, sb, sy, sx, sc, key, N, C, H * W, W, out);
   MM_LAUNCH_CHECK();
   return MM_OK;
@@ -130,8 +134,10 @@ int mm_lift_gather_key(const float* seg, int64_t sb, int64_t sy, int64_t sx, int
 // dseg (zero-filled by the caller) [pixel of run][c] = sum of dout over the run's points, ascending point order
 int mm_lift_scatter_key(const float* dout, int C, const int32_t* order, const int32_t* skey, int64_t N, int H, int W, int64_t sb, int64_t sy,
                         int64_t sx, int64_t sc, float* dseg, hipStream_t s) {
-  MM_CHECK_ARG(N * C < (1ll << 31) && C > 0, "lift_scatter: too many elements");
+  MM_CHECK_ARG(C > 0 && N >= 0 && N < (1ll << 31) && N * C < (1ll << 31), "lift_scatter: too many elements");
+  MM_CHECK_ARG(H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "lift_scatter: bad map shape (H=%d W=%d)", H, W);
   if (N == 0) return MM_OK;
+  MM_CHECK_ARG(dout && order && skey && dseg, "lift_scatter: null dout, order, skey or dseg");
   hipLaunchKernelGGL(k_lift_scatter_key, dim3((unsigned)mm_cdiv(N * C, T)), dim3(T), 0, s, dout, C, order, skey, N, H * W, W, sb, sy, sx,
                      sc, dseg);
   MM_LAUNCH_CHECK();

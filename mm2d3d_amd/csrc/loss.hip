@@ -1,8 +1,8 @@
 // Row-wise losses over per-point logits [N, C]:
 //   weighted cross entropy, ignore_index, weighted-mean reduction   (/root/reference/lib/losses.py:55-68)
 //   cross-modal KL( softmax(target) || softmax(pred) ).sum(1).mean() (/root/reference/.../train.py:157-184)
-// plus the 2D->3D lifting gather and its deterministic backward (2d_net/model.py:131-137,166-173)
-// and the evaluation's confusion matrices.  (The optimiser updates and the loss-scale kernels are in optim.hip.)
+// plus the evaluation's confusion matrices.  (The 2D->3D lifting is in lift.hip, the optimiser updates and the loss-scale kernels
+// are in optim.hip.)
 // Block partial sums are fp64 and combined in a fixed order: bit-stable run to run.
 #include "common.h"
 #include "pointpred.h"
@@ -437,51 +437,6 @@ __global__ __launch_bounds__(T) void k_kl_bwd(const float* __restrict__ pred, in
   for (int c = 0; c < C; c++) dpred[i * ld_d + c] = k * (expf(p[c] - mp) * ip - expf(t[c] - mt) * it);
 }
 
-// ---- lifting: out[p][c] = seg[pix_off[p] + c*sc]
-__global__ __launch_bounds__(T) void k_lift_gather(const float* __restrict__ seg, int64_t sc,
-                                                    const int64_t* __restrict__ pix_off, int64_t N, int C,
-                                                    float* __restrict__ out) {
-  int64_t gid = (int64_t)blockIdx.x * T + threadIdx.x;
-  int64_t p = gid / C;
-  int c = (int)(gid - p * C);
-  if (p >= N) return;
-  out[p * C + c] = seg[pix_off[p] + c * sc];
-}
-
-// dseg[upix_off[u] + c*sc] = sum over the points of unique pixel u (ascending point order)
-__global__ __launch_bounds__(T) void k_lift_scatter(const float* __restrict__ dout, int C,
-                                                     const int64_t* __restrict__ upix_off,
-                                                     const int32_t* __restrict__ csr_off,
-                                                     const int32_t* __restrict__ csr_pts, int64_t n_unique, int64_t sc,
-                                                     float* __restrict__ dseg) {
-  int64_t gid = (int64_t)blockIdx.x * T + threadIdx.x;
-  int64_t u = gid / C;
-  int c = (int)(gid - u * C);
-  if (u >= n_unique) return;
-  float s = 0.f;
-  for (int e = csr_off[u]; e < csr_off[u + 1]; e++) s += dout[(int64_t)csr_pts[e] * C + c];
-  dseg[upix_off[u] + c * sc] = s;
-}
-
-// runs of equal pixel keys in the key-sorted point order: the first element of each run sums the run (ascending point
-// order inside a run because the sort is stable) - no compaction, so the host never needs the number of unique pixels
-__global__ __launch_bounds__(T) void k_lift_scatter_runs(const float* __restrict__ dout, int C, const int64_t* __restrict__ order,
-                                                          const unsigned char* __restrict__ first,
-                                                          const int64_t* __restrict__ sorted_off, int64_t N, int64_t sc,
-                                                          float* __restrict__ dseg) {
-  int64_t gid = (int64_t)blockIdx.x * T + threadIdx.x;
-  int64_t e = gid / C;
-  int c = (int)(gid - e * C);
-  if (e >= N || !first[e]) return;
-  float s = 0.f;
-  int64_t j = e;
-  do {
-    s += dout[order[j] * C + c];
-    j++;
-  } while (j < N && !first[j]);
-  dseg[sorted_off[e] + c * sc] = s;
-}
-
 // ---- evaluation (train.py:297-339): argmax of the 2D logits, of the 3D logits and of the softmax average, three
 // confusion matrices [target][pred] over the rows whose label != ignore.  Integer counts: order independent.
 __global__ __launch_bounds__(T) void k_eval_confusion(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3,
@@ -517,6 +472,8 @@ static inline int loss_blocks(int64_t N) {
 int mm_ce_fwd(const float* logits, int ld, const int64_t* labels, const float* weight, int64_t N, int C, int64_t ignore_index,
               float* stats, void* ws, size_t ws_bytes, hipStream_t s) {
   MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C, "ce: bad C");
+  MM_CHECK_ARG(N >= 0, "ce: negative N");
+  MM_CHECK_ARG(stats && ws && ((logits && labels) || N == 0), "ce: null logits, labels, stats or workspace");
   if (ws_bytes < (size_t)MAX_PART * 2 * sizeof(double)) {
     mm_set_error("ce: workspace too small");
     return MM_ERR_WORKSPACE;
@@ -530,7 +487,10 @@ int mm_ce_fwd(const float* logits, int ld, const int64_t* labels, const float* w
 
 int mm_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* weight, int64_t N, int C, int64_t ignore_index,
               const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C && ld_d >= C, "ce: bad C");
+  MM_CHECK_ARG(N >= 0, "ce: negative N");
   if (N == 0) return MM_OK;
+  MM_CHECK_ARG(logits && labels && stats && grad_out && dlogits, "ce: null logits, labels, stats, grad_out or dlogits");
   hipLaunchKernelGGL(k_ce_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, labels, weight, N, C, ignore_index, stats,
                      grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
@@ -631,7 +591,9 @@ int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const 
 
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws, size_t ws_bytes,
               hipStream_t s) {
-  MM_CHECK_ARG(C > 0 && C <= MAXC, "kl: bad C");
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld_p >= C && ld_t >= C, "kl: bad C");
+  MM_CHECK_ARG(N >= 0, "kl: negative N");
+  MM_CHECK_ARG(loss && ws && ((pred && tgt) || N == 0), "kl: null pred, tgt, loss or workspace");
   if (ws_bytes < (size_t)MAX_PART * sizeof(double)) {
     mm_set_error("kl: workspace too small");
     return MM_ERR_WORKSPACE;
@@ -645,37 +607,11 @@ int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N
 
 int mm_kl_bwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, const float* grad_out, float* dpred,
               int ld_d, hipStream_t s) {
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld_p >= C && ld_t >= C && ld_d >= C, "kl: bad C");
+  MM_CHECK_ARG(N >= 0, "kl: negative N");
   if (N == 0) return MM_OK;
+  MM_CHECK_ARG(pred && tgt && grad_out && dpred, "kl: null pred, tgt, grad_out or dpred");
   hipLaunchKernelGGL(k_kl_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, pred, ld_p, tgt, ld_t, N, C, grad_out, dpred, ld_d);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-// out[p][c] = seg[pix_off[p] + c*chan_stride]   (pix_off = element offset of channel 0 of the point's pixel)
-int mm_lift_gather(const float* seg, int64_t chan_stride, const int64_t* pix_off, int64_t N, int C, float* out, hipStream_t s) {
-  if (N == 0) return MM_OK;
-  hipLaunchKernelGGL(k_lift_gather, dim3((unsigned)mm_cdiv(N * C, T)), dim3(T), 0, s, seg, chan_stride, pix_off, N, C, out);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-// dseg must be zero-filled by the caller; duplicate pixels accumulate in ascending point order
-int mm_lift_scatter(const float* dout, int C, const int64_t* upix_off, const int32_t* csr_off, const int32_t* csr_pts,
-                    int64_t n_unique, int64_t chan_stride, float* dseg, hipStream_t s) {
-  if (n_unique == 0) return MM_OK;
-  hipLaunchKernelGGL(k_lift_scatter, dim3((unsigned)mm_cdiv(n_unique * C, T)), dim3(T), 0, s, dout, C, upix_off, csr_off, csr_pts,
-                     n_unique, chan_stride, dseg);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-// same as mm_lift_scatter without compaction: order = stable argsort of the pixel keys, first[e] = 1 at run starts,
-// sorted_off[e] = element offset of channel 0 of the pixel of sorted element e
-int mm_lift_scatter_runs(const float* dout, int C, const int64_t* order, const unsigned char* first, const int64_t* sorted_off,
-                         int64_t N, int64_t chan_stride, float* dseg, hipStream_t s) {
-  if (N == 0) return MM_OK;
-  hipLaunchKernelGGL(k_lift_scatter_runs, dim3((unsigned)mm_cdiv(N * C, T)), dim3(T), 0, s, dout, C, order, first, sorted_off, N,
-                     chan_stride, dseg);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -683,8 +619,10 @@ int mm_lift_scatter_runs(const float* dout, int C, const int64_t* order, const u
 // cm int64 [3][C][C] (2D, 3D, softmax-average ensemble), accumulated (caller zeroes it at the start of an epoch)
 int mm_eval_confusion(const float* logits2d, int ld2, const float* logits3d, int ld3, const int64_t* labels, int64_t N, int C,
                       int64_t ignore_index, int64_t* cm, hipStream_t s) {
-  MM_CHECK_ARG(C > 0 && C <= MAXC, "eval_confusion: bad C");
+  MM_CHECK_ARG(C > 0 && C <= MAXC && ld2 >= C && ld3 >= C, "eval_confusion: bad C");
+  MM_CHECK_ARG(N >= 0, "eval_confusion: negative N");
   if (N == 0) return MM_OK;
+  MM_CHECK_ARG(logits2d && logits3d && labels && cm, "eval_confusion: null logits, labels or cm");
   int nb = (int)mm_cdiv(N, (int64_t)T * 8);
   if (nb > 1024) nb = 1024;
   hipLaunchKernelGGL(k_eval_confusion, dim3(nb), dim3(T), (size_t)3 * C * C * sizeof(unsigned int), s, logits2d, ld2, logits3d, ld3,

@@ -27,10 +27,10 @@ import pytest
 import torch
 
 import _point_ref as R
+from _gpu_rows import SENTINEL, Rows as _Rows, abi as _abi, dev as _dev, ints as _ints, vec as _vec  # shared with the loss and lift files
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -12345.0
 GATE_BOUNDS = dict(mask=1.4e-06, y=1.5e-06, dx=9.5e-07, dw=1.6e-06, db=8.8e-07)
 
 
@@ -161,53 +161,6 @@ def gate_inputs(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ helpers
-def _dev():
-    import mm2d3d_amd  # noqa: F401
-
-    return torch.device("cuda:0")
-
-
-def _abi():
-    from mm2d3d_amd import _lib
-
-    return _lib.lib(), _lib
-
-
-class _Rows:
-    """An [n, c] operand on the device: a view, rows ``ld`` apart, ``off`` floats into a wider flat buffer that holds ``fill``
-    everywhere else (before the first row, between rows, behind the last one)."""
-
-    def __init__(self, data, n, c, ld, off=0, fill=float("nan")):
-        assert c <= ld
-        flat = torch.full((off + n * ld + 8,), fill, dtype=torch.float32)
-        self._cpu_view = flat[off: off + n * ld].view(n, ld)[:, :c]
-        if data is not None:
-            self._cpu_view.copy_(torch.from_numpy(np.ascontiguousarray(data)).reshape(n, c).float())
-        self.flat = flat.to(_dev())
-        assert self.flat.data_ptr() % 16 == 0
-        self.view = self.flat[off: off + n * ld].view(n, ld)[:, :c]
-        self.ptr = self.flat.data_ptr() + self.flat.element_size() * off
-        self.fill = fill
-
-    def get(self):
-        return self.view.cpu().double().numpy()
-
-    def padding_untouched(self):
-        chk = self.flat.clone()
-        chk.as_strided(self.view.shape, self.view.stride(), self.view.storage_offset()).fill_(self.fill)
-        return bool((chk == self.fill).all())
-
-
-def _vec(data, n=None, fill=SENTINEL):
-    """A dense vector (or matrix, flattened) between two runs of sentinels."""
-    n = int(np.size(data)) if n is None else n
-    return _Rows(None if data is None else np.asarray(data, np.float64).reshape(1, n), 1, n, n, off=4, fill=fill)
-
-
-def _ints(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(_dev())
-
-
 def _workspace(L, cin, cout):
     return torch.empty(int(L.mm_point_ws_bytes(cin, cout)), dtype=torch.uint8, device=_dev())
 
