@@ -319,6 +319,22 @@ int mm_spconv_dw_reduce_batch(const void* descs_dev, int n, int64_t total_blocks
 /* Row sets that fit on chip take single-launch training kernels (one workgroup per CU, rows kept on chip across two grid
  * barriers) when the handle allows it: mm_set_option(h, MM_OPT_BN3D_FUSED, mask), bit 0 = forward, bit 1 = backward. */
 size_t mm_bn_ws_bytes(int C);
+/* Which path a call takes: R, the rows per thread (1..36), when mm_bn_fwd_train (backward = 0) or mm_bn_bwd (backward != 0) over
+ * N fp32 rows of C channels in 16-byte pieces (C, every pitch and every pointer a multiple of 4 floats) would take the
+ * single-launch kernel through this handle now; 0 when it would run reduce / finalize / apply.  The same decision code as the
+ * launch (option bits, device probe, C limits, grid shape); it registers no stream and touches neither the handle nor the
+ * device.  Two things it cannot see: a handle whose 64 stream slots are all taken sends further streams to the three-kernel
+ * path, and the 2 GiB limit on N * pitch * 4 is evaluated for contiguous rows (pitch = C).  MM_ERR_ARG for what is no handle. */
+int mm_bn_fused_rows(mm_handle_t h, int64_t N, int64_t Ns, int C, int backward);
+/* Arguments, all nine entry points: C in [1, 1024] and at most 256 threads wide (C <= 256, or C % 4 == 0 with 16-byte aligned
+ * pointers and pitches), every pitch >= C, N >= 0, ws_bytes >= mm_bn_ws_bytes(C), running_mean and running_var both null or both
+ * given (eval: both given), x / y / dy / dx / save_mean / save_invstd not null; weight, bias, dweight, dbias may each be null
+ * (weight 1, bias 0, gradient not wanted).  A refused call (MM_ERR_ARG, MM_ERR_WORKSPACE) has launched and written nothing.
+ * N == 0: the forward calls return MM_OK and write nothing (the running buffers stay as they are); the backward zeroes a
+ * non-null dweight / dbias when accumulate == 0 and writes nothing otherwise.
+ * A statistics group of ONE row: mean = x, variance 0, save_invstd = 1 / sqrt(eps), and no unbiased correction exists
+ * (Ng / (Ng - 1) with Ng = 1), so the biased value is used: running_var = momentum * running_var + (1 - momentum) * 0.
+ * Results are bit-stable: repeating a call on the same operands through the same handle gives the same bits. */
 /* Ns: rows [0,Ns) and [Ns,N) (the active sites of the source and of the target scenes of a jointly batched step;
  * train.py:186-292 calls the net once per domain) are normalised with their OWN batch statistics and the running
  * buffers are updated group 0 first, then group 1.  Ns = N (or 0): single batch.  save_mean/save_invstd: [G][C]. */

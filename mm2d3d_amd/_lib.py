@@ -87,6 +87,7 @@ _PROTOS = {
     "mm_bn_fwd_eval_f16": (i32, [vp, i32, i64, i32, vp, vp, vp, vp, f32, f32, vp, i32, vp]),
     "mm_bn_bwd_f16": (i32, [vp, vp, i32, vp, i32, i64, i64, i32, vp, vp, vp, vp, f32, vp, i32, vp, vp, i32, vp, sz, vp]),
     "mm_bn_ws_bytes": (sz, [i32]),
+    "mm_bn_fused_rows": (i32, [vp, i64, i64, i32, i32]),
     "mm_bn_fwd_train": (i32, [vp, vp, i32, i64, i64, i32, vp, vp, vp, vp, f32, f32, f32, vp, i32, vp, vp, vp, sz, vp]),
     "mm_bn_fwd_eval": (i32, [vp, i32, i64, i32, vp, vp, vp, vp, f32, f32, vp, i32, vp]),
     "mm_bn_bwd": (i32, [vp, vp, i32, vp, i32, i64, i64, i32, vp, vp, vp, vp, f32, vp, i32, vp, vp, i32, vp, sz, vp]),

@@ -7,6 +7,8 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+extern "C" size_t mm_bn_ws_bytes(int C);
+
 namespace {
 constexpr int T = 256;
 constexpr int MAX_PART = 1024;
@@ -606,10 +608,18 @@ inline int stat_blocks(int64_t N, int C, int VEC) {
 static const void* const k_fused3_fns[] = {(const void*)k_bn_fused_fwd<8>,  (const void*)k_bn_fused_fwd<20>, (const void*)k_bn_fused_fwd<36>,
                                            (const void*)k_bn_fused_bwd<8>,  (const void*)k_bn_fused_bwd<20>, (const void*)k_bn_fused_bwd<36>};
 
+// Rows per thread (1..36) of the single-launch kernel for N fp32 rows of C channels in 16-byte pieces through handle H, or 0: the
+// three-kernel path.  The one decision: bn_fused_try launches by it and mm_bn_fused_rows reports it.  ldmax: the largest pitch.
+static int bn_fused_rows(const MMHandle* H, bool backward, int64_t N, int64_t Ns, int C, int64_t ldmax, int* G0, int* G1) {
+  if (C <= 0 || C % 4 != 0 || N <= 0 || N * ldmax * 4 >= (1ll << 31)) return 0;
+  return fused_decide(H, MM_OPT_BN3D_FUSED, N, (Ns <= 0 || Ns >= N) ? N : Ns, C, 4, 36, backward, 1, G0, G1);
+}
+
 // true: launched.  fp32 rows with 16-byte pieces only; maps too large for the chip fall through to the three-kernel path
 static int bn_fused_try(MMHandle* H, bool backward, Fused3P& p, int64_t ldmax, hipStream_t s, bool* done) {
   *done = false;
-  if (p.C % 4 != 0 || (p.ld_x % 4) || p.N * ldmax * 4 >= (1ll << 31)) return MM_OK;
+  int G0, G1;
+  if ((p.ld_x % 4) || !bn_fused_rows(H, backward, p.N, p.Ns, p.C, ldmax, &G0, &G1)) return MM_OK;
   FusedPlan pl;
   int rc = fused_plan(H, MM_OPT_BN3D_FUSED, 0, p.N, p.Ns, p.C, 4, 36, backward, k_fused3_fns, 6, s, &pl);
   if (rc || !pl.ok) return rc;
@@ -651,16 +661,22 @@ template <typename E>
 static int bn_fwd_train(MMHandle* H, const E* x, int ld_x, int64_t N, int64_t Ns, int C, const float* weight, const float* bias,
                     float* running_mean, float* running_var, float eps, float momentum, float leak, E* y, int ld_y,
                     float* save_mean, float* save_invstd, void* ws, size_t ws_bytes, hipStream_t s) {
-  MM_CHECK_ARG(C > 0 && C <= 4 * T && ld_x >= C && ld_y >= C, "bn_fwd: bad shape C=%d", C);
-  if (ws_bytes < (size_t)MAX_PART * 2 * C * sizeof(double)) {
-    mm_set_error("bn_fwd: workspace too small");
-    return MM_ERR_WORKSPACE;
-  }
-  double* partial = (double*)ws;
+  // every check comes before the first launch: a refused call has written nothing
+  MM_CHECK_ARG(C > 0 && C <= 4 * T && ld_x >= C && ld_y >= C && N >= 0, "bn_fwd: bad shape N=%lld C=%d ld_x=%d ld_y=%d", (long long)N, C,
+               ld_x, ld_y);
   const bool v4 = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) % (4 * sizeof(E)) == 0);
   MM_CHECK_ARG(C / (v4 ? 4 : 1) <= T, "bn_fwd: %d channels need 16-byte aligned rows (C multiple of 4)", C);
+  MM_CHECK_ARG(save_mean && save_invstd, "bn_fwd: save_mean / save_invstd must not be null");
+  MM_CHECK_ARG(!running_mean == !running_var, "bn_fwd: running_mean and running_var are both null or both given");
+  if (!ws || ws_bytes < mm_bn_ws_bytes(C)) {
+    mm_set_error("bn_fwd: workspace too small (mm_bn_ws_bytes)");
+    return MM_ERR_WORKSPACE;
+  }
+  if (N == 0) return MM_OK;  // a level without rows leaves the module's state alone: nothing is launched
+  MM_CHECK_ARG(x && y, "bn_fwd: x / y must not be null");
+  double* partial = (double*)ws;
   if constexpr (sizeof(E) == 4) {
-    if (v4 && N > 0) {
+    if (v4) {
       Fused3P p = {};
       p.x = (const float*)x, p.y = (float*)y, p.ld_x = ld_x, p.ld_y = ld_y, p.N = N, p.Ns = (Ns <= 0 || Ns >= N) ? N : Ns, p.C = C;
       p.weight = weight, p.bias = bias, p.running_mean = running_mean, p.running_var = running_var;
@@ -697,9 +713,14 @@ template <typename E>
 static int bn_fwd_eval(const E* x, int ld_x, int64_t N, int C, const float* weight, const float* bias,
                    const float* running_mean, const float* running_var, float eps, float leak, E* y, int ld_y,
                    hipStream_t s) {
-  MM_CHECK_ARG(C > 0 && ld_x >= C && ld_y >= C, "bn_eval: bad shape");
-  if (N == 0) return MM_OK;
+  MM_CHECK_ARG(C > 0 && C <= 4 * T && ld_x >= C && ld_y >= C && N >= 0, "bn_eval: bad shape N=%lld C=%d ld_x=%d ld_y=%d", (long long)N, C,
+               ld_x, ld_y);
   const bool v4 = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) % (4 * sizeof(E)) == 0);
+  // a block holds T / (C / VEC) row slots: without this, apply_blocks divided by zero on the host
+  MM_CHECK_ARG(C / (v4 ? 4 : 1) <= T, "bn_eval: %d channels need 16-byte aligned rows (C multiple of 4)", C);
+  MM_CHECK_ARG(running_mean && running_var, "bn_eval: running_mean / running_var must not be null");
+  if (N == 0) return MM_OK;
+  MM_CHECK_ARG(x && y, "bn_eval: x / y must not be null");
   const int ab = (int)apply_blocks(N, C, v4 ? 4 : 1);
   if (v4)
     hipLaunchKernelGGL((k_bn_apply<4, E>), dim3(ab), dim3(T), 0, s, x, ld_x, N, C, running_mean, running_var, 1, eps, weight, bias, leak, y,
@@ -716,19 +737,28 @@ template <typename E>
 static int bn_bwd(MMHandle* H, const E* x, int ld_x, const E* dy, int ld_dy, int64_t N, int64_t Ns, int C, const float* weight,
               const float* bias, const float* save_mean, const float* save_invstd, float leak, E* dx, int ld_dx,
               float* dweight, float* dbias, int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
-  MM_CHECK_ARG(C > 0 && C <= 4 * T && ld_x >= C && ld_dy >= C && ld_dx >= C, "bn_bwd: bad shape");
-  size_t need = mm_align((size_t)MAX_PART * 2 * C * sizeof(double));
-  if (ws_bytes < need + 4 * C * sizeof(float)) {
-    mm_set_error("bn_bwd: workspace too small");
-    return MM_ERR_WORKSPACE;
-  }
-  double* partial = (double*)ws;
-  float* sums = (float*)((char*)ws + need);
+  MM_CHECK_ARG(C > 0 && C <= 4 * T && ld_x >= C && ld_dy >= C && ld_dx >= C && N >= 0, "bn_bwd: bad shape N=%lld C=%d ld_x=%d ld_dy=%d ld_dx=%d",
+               (long long)N, C, ld_x, ld_dy, ld_dx);
   const bool v4 = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_dy % 4 == 0) && (ld_dx % 4 == 0) &&
                   (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % (4 * sizeof(E)) == 0);
   MM_CHECK_ARG(C / (v4 ? 4 : 1) <= T, "bn_bwd: %d channels need 16-byte aligned rows (C multiple of 4)", C);
+  size_t need = mm_align((size_t)MAX_PART * 2 * C * sizeof(double));
+  if (!ws || ws_bytes < mm_bn_ws_bytes(C)) {
+    mm_set_error("bn_bwd: workspace too small (mm_bn_ws_bytes)");
+    return MM_ERR_WORKSPACE;
+  }
+  if (N == 0) {  // no rows: the parameter gradients of this call are zero; nothing else is written
+    if (!accumulate) {
+      if (dweight) MM_HIP(hipMemsetAsync(dweight, 0, (size_t)C * sizeof(float), s));
+      if (dbias) MM_HIP(hipMemsetAsync(dbias, 0, (size_t)C * sizeof(float), s));
+    }
+    return MM_OK;
+  }
+  MM_CHECK_ARG(x && dy && dx && save_mean && save_invstd, "bn_bwd: x / dy / dx / save_mean / save_invstd must not be null");
+  double* partial = (double*)ws;
+  float* sums = (float*)((char*)ws + need);
   if constexpr (sizeof(E) == 4) {
-    if (v4 && N > 0) {
+    if (v4) {
       Fused3P p = {};
       p.x = (const float*)x, p.dy = (const float*)dy, p.dx = (float*)dx, p.ld_x = ld_x, p.ld_dy = ld_dy, p.ld_dx = ld_dx;
       p.N = N, p.Ns = (Ns <= 0 || Ns >= N) ? N : Ns, p.C = C, p.weight = weight, p.bias = bias, p.leak = leak;
@@ -766,6 +796,13 @@ extern "C" {
 // Which path runs (single-launch grid-barrier kernels or reduce / finalize / apply) is the HANDLE's choice:
 // mm_set_option(h, MM_OPT_BN3D_FUSED, mask), bit 0 = forward, bit 1 = backward.  Same residency rules as the 2D kernels.
 size_t mm_bn_ws_bytes(int C) { return mm_align((size_t)MAX_PART * 2 * C * sizeof(double)) + mm_align(4 * C * sizeof(float)) + 256; }
+
+// the decision of bn_fused_try (bn_fused_rows above) for contiguous rows; touches neither the handle nor the device
+int mm_bn_fused_rows(void* h, int64_t N, int64_t Ns, int C, int backward) {
+  MM_CHECK_HANDLE(h);
+  int G0, G1;
+  return bn_fused_rows(H, backward != 0, N, Ns, C, C, &G0, &G1);
+}
 
 
 int mm_bn_fwd_train(void* h, const float* x, int ld_x, int64_t N, int64_t Ns, int C, const float* weight, const float* bias,

@@ -262,11 +262,23 @@ static inline int64_t fused_shape(int cus, int64_t N, int64_t Ns, int C, int vec
   return mm_cdiv(rpb0 > rpb1 ? rpb0 : rpb1, rs);
 }
 
+// The decision itself, from the handle's switches and the shape alone (no driver call, no handle state changed): rows per thread
+// R (1..rmax) and the grid split when a call takes the single-launch kernel, 0 when it takes the three-kernel path.  fused_plan
+// below and the query entry points (mm_bn_fused_rows) both come through here.
+static inline int fused_decide(const MMHandle* H, int opt, int64_t N, int64_t Ns, int C, int vec, int rmax, bool backward, int cus_div,
+                               int* G0, int* G1) {
+  if (!H->fused_ok || !(H->opt[opt] & (backward ? 2 : 1)) || N <= 0 || C % vec != 0 || C > FT || C < vec) return 0;
+  const int64_t R = fused_shape(H->cus / cus_div, N, Ns, C, vec, G0, G1);
+  return R > rmax ? 0 : (int)R;
+}
+
 // cus_div = 2: the plan of ONE of two problems that share a launch (half the CUs each; csrc/bn2d.hip pair entry points)
 static inline int fused_plan(MMHandle* H, int opt, int unit, int64_t N, int64_t Ns, int C, int vec, int rmax, bool backward,
                              const void* const* fns, int nfns, hipStream_t s, FusedPlan* pl, int cus_div = 1) {
   pl->ok = false;
-  if (!H->fused_ok || !(H->opt[opt] & (backward ? 2 : 1)) || N <= 0 || C % vec != 0 || C > FT || C < vec) return MM_OK;
+  int G0, G1;
+  const int R = fused_decide(H, opt, N, Ns, C, vec, rmax, backward, cus_div, &G0, &G1);
+  if (R == 0) return MM_OK;
   if (!(H->attr_done & (1u << unit))) {
     bool good = true;
     for (int i = 0; good && i < nfns; i++)
@@ -286,11 +298,8 @@ static inline int fused_plan(MMHandle* H, int opt, int unit, int64_t N, int64_t 
     slot = H->nstream++;
     H->streams[slot] = s;
   }
-  int G0, G1;
-  const int64_t R = fused_shape(H->cus / cus_div, N, Ns, C, vec, &G0, &G1);
-  if (R > rmax) return MM_OK;
   pl->ok = true;
-  pl->G0 = G0, pl->G1 = G1, pl->R = (int)R;
+  pl->G0 = G0, pl->G1 = G1, pl->R = R;
   pl->sync = H->sync + slot * (MM_SYNC_SLOT_BYTES / 4);
   pl->fault = H->fault_dev;
   return MM_OK;

@@ -1,6 +1,6 @@
 """Device operands of the tests that call the C ABI directly (test_gpu_point_rows.py, test_gpu_loss_rows.py,
-test_gpu_lift_index.py): pitched views into wider buffers whose padding is NaN for inputs and a sentinel, which must survive, for
-outputs.  No tests here; importing this needs no GPU."""
+test_gpu_lift_index.py, test_gpu_bn_rows.py): pitched views into wider buffers whose padding is NaN for inputs and a sentinel, which
+must survive, for outputs.  No tests here; importing this needs no GPU."""
 import numpy as np
 import torch
 
@@ -19,37 +19,49 @@ def abi():
     return _lib.lib(), _lib
 
 
-class Rows:
-    """An [n, c] operand on the device: a view, rows ``ld`` apart, ``off`` floats into a wider flat buffer that holds ``fill``
-    everywhere else (before the first row, between rows, behind the last one)."""
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+_BITS = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16}
 
-    def __init__(self, data, n, c, ld, off=0, fill=float("nan")):
+
+class Rows:
+    """An [n, c] operand on the device: a view, rows ``ld`` apart, ``off`` elements into a wider flat buffer that holds ``fill``
+    everywhere else (before the first row, between rows, behind the last one).  ``dtype``: torch.float32 (default), bfloat16 or
+    float16 (or "fp32" / "bf16" / "fp16"); data and fill are rounded to it (nearest even).  ``tight``: the buffer ends with the last
+    element of the last row (a channel slice that reaches the end of its allocation)."""
+
+    def __init__(self, data, n, c, ld, off=0, fill=float("nan"), dtype=torch.float32, tight=False):
         assert c <= ld
-        flat = torch.full((off + n * ld + 8,), fill, dtype=torch.float32)
-        self._cpu_view = flat[off: off + n * ld].view(n, ld)[:, :c]
+        dtype = DTYPES.get(dtype, dtype)
+        flat = torch.full((off + (n - 1) * ld + c if tight and n else off + n * ld + 8,), fill, dtype=dtype)
+        self._cpu_view = flat.as_strided((n, c), (ld, 1), off)
         if data is not None:
             self._cpu_view.copy_(torch.from_numpy(np.ascontiguousarray(data)).reshape(n, c).float())
         self.flat = flat.to(dev())
         assert self.flat.data_ptr() % 16 == 0
-        self.view = self.flat[off: off + n * ld].view(n, ld)[:, :c]
+        self.view = self.flat.as_strided((n, c), (ld, 1), off)
         self.ptr = self.flat.data_ptr() + self.flat.element_size() * off
         self.fill = fill
+        self._fill_bits = torch.full((1,), fill, dtype=dtype).view(_BITS[dtype]).item()  # NaN compares unequal to itself: compare bits
 
     def get(self):
         return self.view.cpu().double().numpy()
 
     def get32(self):
-        """The values as they are: float32, signed zeros and NaN payloads included."""
-        return self.view.cpu().numpy()
+        """The values as they are: float32 (every 16-bit value is one), signed zeros and NaN payloads included."""
+        return self.view.cpu().float().numpy()
+
+    def bits(self):
+        """The rows as the integers that hold them (int32 / int16)."""
+        return self.view.cpu().contiguous().view(_BITS[self.flat.dtype]).numpy()
 
     def padding_untouched(self):
         chk = self.flat.clone()
         chk.as_strided(self.view.shape, self.view.stride(), self.view.storage_offset()).fill_(self.fill)
-        return bool((chk == self.fill).all())
+        return bool((chk.view(_BITS[chk.dtype]) == self._fill_bits).all())
 
     def untouched(self):
         """Nothing was written at all: the whole buffer, rows included, still holds the fill value."""
-        return bool((self.flat == self.fill).all())
+        return bool((self.flat.view(_BITS[self.flat.dtype]) == self._fill_bits).all())
 
 
 def vec(data, n=None, fill=SENTINEL):
