@@ -433,6 +433,28 @@ int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const 
 int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                 int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
                 const float* stats, const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
+/* Lovasz-softmax loss (Berman et al., CVPR 2018) of logits [N, C] (row pitch ld) against int64 labels (csrc/lovasz.hip).
+ * Counted rows: label != ignore_index and 0 <= label < C, as in mm_ce2_*; p = softmax(x) per row.  For every class c:
+ * fg_i = [y_i == c], e_i = |fg_i - p_ic|; the counted rows are ordered by e descending, stable in the row index.  With G = sum fg,
+ * r_i the 1-based rank of row i and f_i the foreground rows among ranks 1 .. r_i: U = G + r_i - f_i, I = G - f_i, and the weight
+ * of row i is the increment of the Jaccard loss 1 - I / U at its rank in closed form: g_i = 1 / U for a foreground row,
+ * I / (U * (U - 1)) for a background row, and 1 for the rank-1 row of a class with G == 0.  loss_c = sum_i e_i * g_i; the loss
+ * is the mean of loss_c over the included classes: those with G > 0, or with classes_all != 0 every class as soon as one row
+ * is counted.  Nothing counted: loss 0, n_included 0, coef 0.
+ *   err, coef   class-major [C][N], indexed by the original row; an uncounted row has err = -1 and coef = 0;
+ *               coef[c][i] = dloss / dp_ic = (fg ? -1 : +1) * g_i / n_included (g is a constant of the gradient);
+ *   stats[3]    the loss, n_included, the number of counted rows.
+ * The backward recomputes the softmax: dlogits_ik = grad_out[0] * p_ik * (coef[k][i] - sum_c coef[c][i] * p_ic), every one of the
+ * N rows written once (zeros where every coefficient of the row is zero); grad_out is read on the device.
+ * 1 <= C <= 32, ld >= C, ld_d >= C, 0 <= N <= 2^24 (U <= N is then exact in float32, and N * C < 2^31); anything else is
+ * refused before a launch.  The sort is a stable three-digit radix sort, every class in one grid; no workgroup waits for another
+ * (no look-back, no spin, no grid barrier) and no float atomics: fp64 partial sums in a fixed order, bit-stable run to run.
+ * mm_lovasz_ws_bytes returns 0 for a C or N outside these limits. */
+size_t mm_lovasz_ws_bytes(int64_t N, int C);
+int mm_lovasz_fwd(const float* logits, int ld, int64_t N, int C, const int64_t* labels, int64_t ignore_index, int classes_all,
+                  float* err, float* coef, float* stats, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_lovasz_bwd(const float* logits, int ld, int64_t N, int C, const float* coef, const float* grad_out, float* dlogits,
+                  int ld_d, mm_stream_t stream);
 /* mean_i sum_c softmax(tgt)_ic (log softmax(tgt)_ic - log softmax(pred)_ic)  (EXP/train.py:157-184) */
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws,
               size_t ws_bytes, mm_stream_t stream);

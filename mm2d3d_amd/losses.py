@@ -2,7 +2,8 @@
 
 ``Loss(cfg)``; ``loss("segmentation", pred=, gt=)``; ``split_by_target()``; ``update_loss_params()`` behave as
 in the reference; ``cross_entropy`` (weighted, ignore_index -100, weighted-mean reduction = torch's
-``F.cross_entropy`` default) and the cross-modal KL of train.py:157-184 run as single fused kernels.
+``F.cross_entropy`` default) and the cross-modal KL of train.py:157-184 run as single fused kernels; ``lovasz_softmax`` sorts its
+errors per class with the segmented radix sort of csrc/lovasz.hip.
 """
 from __future__ import annotations
 
@@ -249,6 +250,64 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
                                          0.0 if threshold is None else float(threshold), int(ignore_index))
 
 
+class _LovaszFn(torch.autograd.Function):
+    """Lovasz-softmax of ``logits`` [N, C] against ``labels`` (csrc/lovasz.hip): the forward sorts every class's errors and leaves
+    the signed, scaled Jaccard increments ``coef`` [C, N]; the backward is one row kernel over ``logits`` and ``coef``."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, classes_all, ignore_index):
+        _lib.require_cuda(logits, "pred")
+        L = _lib.lib()
+        ctx.in_dtype = logits.dtype
+        logits, ld = _row_pitched(logits)
+        N, C = logits.shape
+        err = torch.empty((C, N), dtype=F32, device=logits.device)  # needed by nobody after the call: freed on return
+        coef = torch.empty((C, N), dtype=F32, device=logits.device)
+        stats = torch.empty(3, dtype=F32, device=logits.device)
+        ws = _lib.workspace.get(int(L.mm_lovasz_ws_bytes(N, C)), logits.device)
+        check(L.mm_lovasz_fwd(ptr(logits), ld, N, C, ptr(labels), ignore_index, classes_all, ptr(err), ptr(coef), ptr(stats), ptr(ws),
+                              ws.numel(), stream()), "lovasz_fwd")
+        ctx.save_for_backward(logits, coef)
+        ctx.ld = ld
+        return stats[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _lib.lib()
+        logits, coef = ctx.saved_tensors
+        N, C = logits.shape
+        d = torch.empty((N, C), dtype=F32, device=logits.device)
+        g = g.to(F32).contiguous()
+        check(L.mm_lovasz_bwd(ptr(logits), ctx.ld, N, C, ptr(coef), ptr(g), ptr(d), C, stream()), "lovasz_bwd")
+        if ctx.in_dtype != F32:
+            d = d.to(ctx.in_dtype)
+        return d, None, None, None
+
+
+def lovasz_softmax(pred, gt, classes="present", ignore_index=-100):
+    """Lovasz-softmax loss (Berman et al., CVPR 2018) of ``pred`` [N, C] against the labels ``gt`` [N]: the mean over the included
+    classes of the Lovasz extension of the Jaccard loss of the class's errors ``|[y == c] - softmax(pred)_c|``.  Rows are counted as
+    in :func:`cross_entropy_pair` (``gt != ignore_index`` and ``0 <= gt < C``).  ``classes="present"``: the classes that label a
+    counted row; ``"all"``: every class.  Nothing counted: loss ``0.0`` and a zero gradient.  The Jaccard increments are constants
+    of the gradient, as in the paper's implementation; there is no ``per_image``.  ``pred`` may be fp16, bf16 or a row-pitched
+    view (``stride(1) == 1``), which is read in place.  One autograd node; bit-stable run to run."""
+    who = "lovasz_softmax"
+    if not isinstance(classes, str) or classes not in ("present", "all"):
+        raise ValueError(f'{who}: classes must be "present" or "all", not {classes!r}')
+    if not torch.is_tensor(pred) or pred.dim() != 2:
+        raise ValueError(f"{who}: pred must be [N, C]")
+    N, C = int(pred.shape[0]), int(pred.shape[1])
+    if not 1 <= C <= 32:
+        raise ValueError(f"{who}: {C} classes, the row kernels take 1 to 32")
+    if N > 1 << 24:
+        raise ValueError(f"{who}: {N} rows, the sort takes at most 2^24")
+    if not torch.is_tensor(gt) or gt.dim() != 1 or gt.shape[0] != N:
+        got = tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__
+        raise ValueError(f"{who}: gt is {got}, pred has {N} rows")
+    gt = gt.to(device=pred.device, dtype=torch.int64).contiguous()
+    return _LovaszFn.apply(pred, gt, 1 if classes == "all" else 0, int(ignore_index))
+
+
 class _KLFn(torch.autograd.Function):
     """mean_i sum_c softmax(t)_ic * (log_softmax(t)_ic - log_softmax(p)_ic); gradient flows to p only (t is detached)."""
 
@@ -320,7 +379,14 @@ class CrossEntropy(_GenericLoss):
         return cross_entropy(pred, gt, weight)
 
 
-_LOSSES = {"l1": L1, "l2": L2, "cross_entropy": CrossEntropy}
+class LovaszSoftmax(_GenericLoss):
+    name, default_target = "lovasz_softmax", "segmentation"
+
+    def __call__(self, pred, gt, classes="present", **kw):
+        return lovasz_softmax(pred, gt, classes)
+
+
+_LOSSES = {"l1": L1, "l2": L2, "cross_entropy": CrossEntropy, "lovasz_softmax": LovaszSoftmax}
 
 
 class Loss:
