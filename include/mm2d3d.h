@@ -392,7 +392,8 @@ int mm_linear_bwd(const float* x, int ld_x, const float* dy, int ld_dy, int64_t 
 /* ---------------------------------------------------------------- losses, lifting, evaluation (csrc/loss.hip) */
 size_t mm_loss_ws_bytes(void);
 /* weighted cross entropy, ignore_index, weighted-mean reduction (lib/losses.py:55-68 -> F.cross_entropy).
- * stats[0] = loss, stats[1] = sum of the class weights of the counted rows */
+ * stats[0] = loss, stats[1] = sum of the class weights of the counted rows.  This is mm_ce2_* below with P = N (the tail
+ * unlabelled, zero_if_empty = 0), bit for bit: loss, weight sum and gradient. */
 int mm_ce_fwd(const float* logits, int ld, const int64_t* labels, const float* weight, int64_t N, int C,
               int64_t ignore_index, float* stats, void* ws, size_t ws_bytes, mm_stream_t stream);
 int mm_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* weight, int64_t N, int C,

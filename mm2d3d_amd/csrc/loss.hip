@@ -6,202 +6,106 @@
 // Block partial sums are fp64 and combined in a fixed order: bit-stable run to run.
 #include "common.h"
 #include "pointpred.h"
+#include "rows.h"
 
 namespace {
 constexpr int T = 256;
 constexpr int MAX_PART = 1024;
 constexpr int MAXC = MM_PRED_MAXC;
 
-__device__ inline double block_sum(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// partial[b] = (sum w*nll, sum w)
-__global__ __launch_bounds__(T) void k_ce_fwd(const float* __restrict__ logits, int ld, const int64_t* __restrict__ labels,
-                                               const float* __restrict__ weight, int64_t N, int C, int64_t ignore,
+// ---- hard-label cross entropy over NSEG segments of the rows: rows [0, P) against (labels0, weight0) and, with NSEG = 2, rows
+// [P, N) against (labels1, weight1), each segment its own weighted mean.  The joined [source | target] pass keeps a head's logits
+// in ONE tensor; NSEG = 2 reads it once per direction and writes its gradient once (no slice gradients to zero-fill, copy and
+// add).  NSEG = 1 (mm_ce_*: P = N, labels required) is the same code with `tail` a compile-time false: over one labelled segment
+// the two agree bit for bit.  NSEG = 2: a NULL labels pointer = an unlabelled segment.
+// partial[b] = (sum w*nll, sum w) per segment
+template <int NSEG>
+__global__ __launch_bounds__(T) void k_ce_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
+                                               const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
+                                               const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
                                                double* __restrict__ partial) {
   __shared__ double red[T];
-  double sl = 0.0, sw = 0.0;
+  double sl[NSEG] = {}, sw[NSEG] = {};
   for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
-    int64_t y = labels[i];
-    if (y == ignore || y < 0 || y >= C) continue;
-    const float* x = logits + i * ld;
-    float m = x[0];
-    for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; c++) s += expf(x[c] - m);
-    float nll = (m + logf(s)) - x[y];
-    float w = weight ? weight[y] : 1.f;
-    sl += (double)(w * nll);
-    sw += (double)w;
-  }
-  double a = block_sum(sl, red);
-  double b = block_sum(sw, red);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = a;
-    partial[2 * blockIdx.x + 1] = b;
-  }
-}
-
-// one wave: lanes stride the partials (independent loads), then a fixed shuffle tree - a fixed order, bit-stable.  (Rounds 1-3: one
-// thread walked all <= 1024 partials through dependent loads: 18-26 us per call, six calls per step.)
-__device__ inline double wave_sum64(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(64) void k_ce_finalize(const double* __restrict__ partial, int nb, float* __restrict__ out /*[2]: loss, sum_w*/) {
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 64) {
-    a += partial[2 * i];
-    b += partial[2 * i + 1];
-  }
-  a = wave_sum64(a), b = wave_sum64(b);
-  if (threadIdx.x == 0) {
-    out[0] = (float)(a / b);  // 0/0 = nan, as torch does when every label is ignored
-    out[1] = (float)b;
-  }
-}
-
-// dlogits = gscale * w[y] * (softmax - onehot) / sum_w
-__global__ __launch_bounds__(T) void k_ce_bwd(const float* __restrict__ logits, int ld, const int64_t* __restrict__ labels,
-                                               const float* __restrict__ weight, int64_t N, int C, int64_t ignore,
-                                               const float* __restrict__ stats, const float* __restrict__ gout,
-                                               float* __restrict__ dlogits, int ld_d) {
-  int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
-  if (i >= N) return;
-  int64_t y = labels[i];
-  float* d = dlogits + i * ld_d;
-  if (y == ignore || y < 0 || y >= C) {
-    for (int c = 0; c < C; c++) d[c] = 0.f;
-    return;
-  }
-  const float* x = logits + i * ld;
-  float m = x[0];
-  for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-  float s = 0.f;
-  for (int c = 0; c < C; c++) s += expf(x[c] - m);
-  float k = gout[0] * (weight ? weight[y] : 1.f) / stats[1];
-  float inv = 1.f / s;
-  for (int c = 0; c < C; c++) d[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
-}
-
-// ---- two-segment cross entropy: rows [0, P) against (labels0, weight0), rows [P, N) against (labels1, weight1), each segment its
-// own weighted mean.  The joined [source | target] pass keeps a head's logits in ONE tensor; this reads it once per direction and
-// writes its gradient once (no slice gradients to zero-fill, copy and add).  Row arithmetic and reduction order are k_ce_fwd's.
-// A NULL labels pointer = an unlabelled segment.  partial[b] = (sum w*nll, sum w) of segment 0, then of segment 1.
-__global__ __launch_bounds__(T) void k_ce2_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
-                                                const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
-                                                const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
-                                                double* __restrict__ partial) {
-  __shared__ double red[T];
-  double sl0 = 0.0, sw0 = 0.0, sl1 = 0.0, sw1 = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
-    const bool tail = i >= P;
+    const bool tail = NSEG == 2 && i >= P;
     const int64_t* labels = tail ? labels1 : labels0;
-    if (!labels) continue;
+    if (NSEG == 2 && !labels) continue;
     int64_t y = labels[tail ? i - P : i];
-    if (y == ignore || y < 0 || y >= C) continue;
+    if (!label_counted(y, ignore, C)) continue;
     const float* weight = tail ? weight1 : weight0;
     const float* x = logits + i * ld;
-    float m = x[0];
-    for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; c++) s += expf(x[c] - m);
-    float nll = (m + logf(s)) - x[y];
+    const RowLse r = row_lse(x, C);
+    float nll = (r.m + logf(r.s)) - x[y];
     float w = weight ? weight[y] : 1.f;
     if (tail) {
-      sl1 += (double)(w * nll);
-      sw1 += (double)w;
+      sl[NSEG - 1] += (double)(w * nll);
+      sw[NSEG - 1] += (double)w;
     } else {
-      sl0 += (double)(w * nll);
-      sw0 += (double)w;
+      sl[0] += (double)(w * nll);
+      sw[0] += (double)w;
     }
   }
-  double a0 = block_sum(sl0, red);
-  double b0 = block_sum(sw0, red);
-  double a1 = block_sum(sl1, red);
-  double b1 = block_sum(sw1, red);
-  if (threadIdx.x == 0) {
-    double* o = partial + 4 * (int64_t)blockIdx.x;
-    o[0] = a0, o[1] = b0, o[2] = a1, o[3] = b1;
+  double* o = partial + 2 * NSEG * (int64_t)blockIdx.x;
+#pragma unroll
+  for (int s = 0; s < NSEG; s++) {
+    double a = block_sum<T>(sl[s], red);
+    double b = block_sum<T>(sw[s], red);
+    if (threadIdx.x == 0) o[2 * s] = a, o[2 * s + 1] = b;
   }
 }
 
+// out[2 * s] = loss (0/0 = nan, as torch does when every label is ignored), out[2 * s + 1] = sum_w of segment s.  NSEG = 2 only:
 // labelled: bit s = segment s has labels; zero_if_empty: bit s = a segment whose weights sum to 0 reports loss 0 instead of 0/0
-__global__ __launch_bounds__(64) void k_ce2_finalize(const double* __restrict__ partial, int nb, int labelled, int zero_if_empty,
-                                                      float* __restrict__ out /*[4]: loss0, sum_w0, loss1, sum_w1*/) {
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nb; i += 64) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] += partial[4 * i + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) v[k] = wave_sum64(v[k]);
+template <int NSEG>
+__global__ __launch_bounds__(64) void k_ce_finalize(const double* __restrict__ partial, int nb, int labelled, int zero_if_empty,
+                                                     float* __restrict__ out /*[2 * NSEG]*/) {
+  double v[2 * NSEG];
+  sum_partials<2 * NSEG>(partial, nb, threadIdx.x, v);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int s = 0; s < 2; s++) {
+    for (int s = 0; s < NSEG; s++) {
       double a = v[2 * s], b = v[2 * s + 1];
-      bool zero = !((labelled >> s) & 1) || (((zero_if_empty >> s) & 1) && b == 0.0);
-      out[2 * s] = zero ? 0.f : (float)(a / b);  // 0/0 = nan, as k_ce_finalize
+      bool zero = NSEG == 2 && (!((labelled >> s) & 1) || (((zero_if_empty >> s) & 1) && b == 0.0));
+      out[2 * s] = zero ? 0.f : (float)(a / b);
       out[2 * s + 1] = (float)b;
     }
   }
 }
 
 // every row written once: segment s: gout[s] * w[y] / sum_w_s * (softmax - onehot); ignored and unlabelled rows: zeros
-__global__ __launch_bounds__(T) void k_ce2_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
-                                                const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
-                                                const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
-                                                const float* __restrict__ stats, const float* __restrict__ gout,
-                                                float* __restrict__ dlogits, int ld_d) {
+template <int NSEG>
+__global__ __launch_bounds__(T) void k_ce_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
+                                               const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
+                                               const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
+                                               const float* __restrict__ stats, const float* __restrict__ gout,
+                                               float* __restrict__ dlogits, int ld_d) {
   int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
   if (i >= N) return;
-  const bool tail = i >= P;
+  const bool tail = NSEG == 2 && i >= P;
   const int64_t* labels = tail ? labels1 : labels0;
-  int64_t y = labels ? labels[tail ? i - P : i] : ignore;
+  const bool labelled = NSEG == 1 || labels;
+  int64_t y = labelled ? labels[tail ? i - P : i] : ignore;
   float* d = dlogits + i * ld_d;
-  if (!labels || y == ignore || y < 0 || y >= C) {
+  if (!labelled || !label_counted(y, ignore, C)) {
     for (int c = 0; c < C; c++) d[c] = 0.f;
     return;
   }
   const float* weight = tail ? weight1 : weight0;
   const float* x = logits + i * ld;
-  float m = x[0];
-  for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-  float s = 0.f;
-  for (int c = 0; c < C; c++) s += expf(x[c] - m);
+  const RowLse r = row_lse(x, C);
   float k = gout[tail] * (weight ? weight[y] : 1.f) / stats[2 * tail + 1];
-  float inv = 1.f / s;
-  for (int c = 0; c < C; c++) d[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
+  ce_grad_row(d, x, C, r.m, 1.f / r.s, k, (int)y);
 }
 
-// ---- two-segment cross entropy with a SOFT tail (mean-teacher targets): rows [0, P) as k_ce2_* against (labels0, weight0), rows
+// ---- two-segment cross entropy with a SOFT tail (mean-teacher targets): rows [0, P) as k_ce_*<2> against (labels0, weight0), rows
 // [P, N) against the distribution q of the teacher logits ta (and tb: the ensemble), softened by the temperature, kept or not by
 // the row's confidence at temperature 1 - pa / pe of mm_point_predict, the value mm_teacher_labels judges the row by.
-// Staging: a workgroup is ONE wave and owns tiles of ST rows; the [rows, C] blocks of the (up to three) matrices are copied into
-// LDS with consecutive lanes on consecutive addresses, then each lane reads its own row from LDS, rows pitched to C | 1 words so
-// that the 64 lanes fall on distinct banks (the pattern of k_teacher_labels in pselab.hip).  3 x 64 x 33 words = 25,344 bytes at
-// C = 32: six workgroups per CU by LDS.  Sums: per lane fp64 over its rows in ascending order, a fixed shuffle tree per workgroup,
-// then k_ce2s_finalize over the workgroups' partials in a fixed order; the kept count is an integer carried in fp64 (exact below
-// 2^53).  No atomics of any kind.
+// Staging: a workgroup is ONE wave and owns tiles of ST rows; the [rows, C] blocks of the (up to three) matrices go through LDS
+// (stage_rows of rows.h, rows pitched to C | 1 words).  3 x 64 x 33 words = 25,344 bytes at C = 32: six workgroups per CU by
+// LDS.  Sums: per lane fp64 over its rows in ascending order, a fixed shuffle tree per workgroup, then k_ce2s_finalize over the
+// workgroups' partials in a fixed order; the kept count is an integer carried in fp64 (exact below 2^53).  No atomics of any kind.
 constexpr int ST = 64;          // rows per tile = lanes of the one wave
 constexpr int S_MAX_PART = 2048;
-
-__device__ inline void stage_rows(float* __restrict__ dst, const float* __restrict__ src, int64_t ld, int rows, int C, int pitch) {
-  for (int e = threadIdx.x; e < rows * C; e += ST) {
-    const int r = e / C, c = e - r * C;
-    dst[r * pitch + c] = src[(int64_t)r * ld + c];
-  }
-}
 
 // sum_c softmax(t * inv_t)_c * v_c over one teacher row (tm = its maximum), v_c = lse - x_c
 __device__ inline float soft_dot(const float* t, float tm, float inv_t, const float* x, float lse, int C) {
@@ -234,23 +138,20 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
     // the tile's tail rows are [h, rows): teacher row (row0 + r - P)
     const int h = (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
     __syncthreads();  // the previous tile's rows have been read
-    stage_rows(sx, logits + row0 * ld, ld, rows, C, pitch);
+    stage_rows<ST>(sx, logits + row0 * ld, ld, rows, C, pitch);
     if (h < rows) {
       const int64_t t0 = row0 + h - P;
-      stage_rows(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
-      if (HAS_B) stage_rows(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
+      stage_rows<ST>(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
+      if (HAS_B) stage_rows<ST>(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
     }
     __syncthreads();
     const int r = threadIdx.x;
     const float* x = sx + r * pitch;
     if (r < h) {
       const int64_t y = labels0 ? labels0[row0 + r] : ignore;
-      if (labels0 && y != ignore && y >= 0 && y < C) {
-        float m = x[0];
-        for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-        float s = 0.f;
-        for (int c = 0; c < C; c++) s += expf(x[c] - m);
-        const float nll = (m + logf(s)) - x[y];
+      if (labels0 && label_counted(y, ignore, C)) {
+        const RowLse l = row_lse(x, C);
+        const float nll = (l.m + logf(l.s)) - x[y];
         const float w = weight0 ? weight0[y] : 1.f;
         sl0 += (double)(w * nll);
         sw0 += (double)w;
@@ -260,11 +161,8 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
       const float* b = sb + r * pitch;
       const MMPointPred pr = mm_point_predict<HAS_B>(a, b, C);
       if ((HAS_B ? pr.pe : pr.pa) >= thr) {  // a NaN confidence (or the ensemble's -1 of a non-finite row) is never kept
-        float m = x[0];
-        for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-        float s = 0.f;
-        for (int c = 0; c < C; c++) s += expf(x[c] - m);
-        const float lse = m + logf(s);
+        const RowLse l = row_lse(x, C);
+        const float lse = l.m + logf(l.s);
         float v = soft_dot(a, a[pr.ia], inv_t, x, lse, C);
         if (HAS_B) v = 0.5f * (v + soft_dot(b, b[pr.ib], inv_t, x, lse, C));
         sl1 += (double)v;
@@ -283,13 +181,8 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
 __global__ __launch_bounds__(64) void k_ce2s_finalize(const double* __restrict__ partial, int nb, int head_labelled,
                                                        float* __restrict__ out /*[4]: loss0, sum_w0, loss1, K*/,
                                                        int64_t* __restrict__ kept) {
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nb; i += 64) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] += partial[4 * i + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) v[k] = wave_sum64(v[k]);
+  double v[4];
+  sum_partials<4>(partial, nb, threadIdx.x, v);
   if (threadIdx.x == 0) {
     out[0] = head_labelled ? (float)(v[0] / v[1]) : 0.f;
     out[1] = (float)v[1];
@@ -300,7 +193,7 @@ __global__ __launch_bounds__(64) void k_ce2s_finalize(const double* __restrict__
 }
 
 // One tile per workgroup, every row written once: the gradient rows are formed in place in the staged logits tile and leave it
-// with consecutive lanes on consecutive addresses.  Head: gout[0] * w[y] / sum_w * (softmax - onehot), as k_ce2_bwd; kept tail
+// with consecutive lanes on consecutive addresses.  Head: gout[0] * w[y] / sum_w * (softmax - onehot), as k_ce_bwd; kept tail
 // rows: gout[1] / K * (softmax - q), q recomputed from the teacher rows; every other row: zeros.
 template <bool HAS_B>
 __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
@@ -316,11 +209,11 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
   const int64_t row0 = (int64_t)blockIdx.x * ST;
   const int rows = (int)((N - row0) < (int64_t)ST ? (N - row0) : (int64_t)ST);
   const int h = (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
-  stage_rows(sx, logits + row0 * ld, ld, rows, C, pitch);
+  stage_rows<ST>(sx, logits + row0 * ld, ld, rows, C, pitch);
   if (h < rows) {
     const int64_t t0 = row0 + h - P;
-    stage_rows(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
-    if (HAS_B) stage_rows(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
+    stage_rows<ST>(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
+    if (HAS_B) stage_rows<ST>(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
   }
   __syncthreads();
   const int r = threadIdx.x;
@@ -334,7 +227,7 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
     const float* b = sb + r * pitch;
     if (r < h) {
       const int64_t yl = labels0 ? labels0[row0 + r] : ignore;
-      live = labels0 && yl != ignore && yl >= 0 && yl < C;
+      live = labels0 && label_counted(yl, ignore, C);
       if (live) {
         y = (int)yl;
         k = gout[0] * (weight0 ? weight0[y] : 1.f) / stats[1];
@@ -347,13 +240,10 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
     if (!live) {
       for (int c = 0; c < C; c++) x[c] = 0.f;
     } else {
-      float m = x[0];
-      for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-      float s = 0.f;
-      for (int c = 0; c < C; c++) s += expf(x[c] - m);
-      const float inv = 1.f / s;
+      const RowLse l = row_lse(x, C);
+      const float m = l.m, inv = 1.f / l.s;
       if (r < h) {
-        for (int c = 0; c < C; c++) x[c] = k * (expf(x[c] - m) * inv - (c == y ? 1.f : 0.f));
+        ce_grad_row(x, x, C, m, inv, k, y);
       } else {
         const float ma = a[pr.ia];
         float za = 0.f, zb = 1.f, mb = 0.f;
@@ -386,17 +276,8 @@ __global__ __launch_bounds__(T) void k_kl_fwd(const float* __restrict__ pred, in
   for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
     const float* p = pred + i * ld_p;
     const float* t = tgt + i * ld_t;
-    float mp = p[0], mt = t[0];
-    for (int c = 1; c < C; c++) {
-      mp = fmaxf(mp, p[c]);
-      mt = fmaxf(mt, t[c]);
-    }
-    float sp = 0.f, st = 0.f;
-    for (int c = 0; c < C; c++) {
-      sp += expf(p[c] - mp);
-      st += expf(t[c] - mt);
-    }
-    float lp = mp + logf(sp), lt = mt + logf(st);
+    const RowLse rp = row_lse(p, C), rt = row_lse(t, C);
+    float lp = rp.m + logf(rp.s), lt = rt.m + logf(rt.s);
     float r = 0.f;
     for (int c = 0; c < C; c++) {
       float lq = t[c] - lt;
@@ -404,15 +285,14 @@ __global__ __launch_bounds__(T) void k_kl_fwd(const float* __restrict__ pred, in
     }
     acc += (double)r;
   }
-  double a = block_sum(acc, red);
+  double a = block_sum<T>(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
 
 __global__ __launch_bounds__(64) void k_kl_finalize(const double* __restrict__ partial, int nb, int64_t N, float* __restrict__ out) {
-  double a = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 64) a += partial[i];
-  a = wave_sum64(a);
-  if (threadIdx.x == 0) out[0] = (float)(a / (double)N);
+  double a[1];
+  sum_partials<1>(partial, nb, threadIdx.x, a);
+  if (threadIdx.x == 0) out[0] = (float)(a[0] / (double)N);
 }
 
 // dpred = gscale/N * (softmax(pred) - softmax(tgt))
@@ -423,18 +303,9 @@ __global__ __launch_bounds__(T) void k_kl_bwd(const float* __restrict__ pred, in
   if (i >= N) return;
   const float* p = pred + i * ld_p;
   const float* t = tgt + i * ld_t;
-  float mp = p[0], mt = t[0];
-  for (int c = 1; c < C; c++) {
-    mp = fmaxf(mp, p[c]);
-    mt = fmaxf(mt, t[c]);
-  }
-  float sp = 0.f, st = 0.f;
-  for (int c = 0; c < C; c++) {
-    sp += expf(p[c] - mp);
-    st += expf(t[c] - mt);
-  }
-  float k = gout[0] / (float)N, ip = 1.f / sp, it = 1.f / st;
-  for (int c = 0; c < C; c++) dpred[i * ld_d + c] = k * (expf(p[c] - mp) * ip - expf(t[c] - mt) * it);
+  const RowLse rp = row_lse(p, C), rt = row_lse(t, C);
+  float k = gout[0] / (float)N, ip = 1.f / rp.s, it = 1.f / rt.s;
+  for (int c = 0; c < C; c++) dpred[i * ld_d + c] = k * (expf(p[c] - rp.m) * ip - expf(t[c] - rt.m) * it);
 }
 
 // ---- evaluation (train.py:297-339): argmax of the 2D logits, of the 3D logits and of the softmax average, three
@@ -447,7 +318,7 @@ __global__ __launch_bounds__(T) void k_eval_confusion(const float* __restrict__ 
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
     int64_t y = labels[i];
-    if (y == ignore || y < 0 || y >= C) continue;
+    if (!label_counted(y, ignore, C)) continue;
     const MMPointPred r = mm_point_predict<true>(l2 + i * ld2, l3 + i * ld3, C);  // pointpred.h: shared with the pseudo-label export
     atomicAdd(&hist[(0 * C + (int)y) * C + r.ia], 1u);
     atomicAdd(&hist[(1 * C + (int)y) * C + r.ib], 1u);
@@ -479,8 +350,9 @@ int mm_ce_fwd(const float* logits, int ld, const int64_t* labels, const float* w
     return MM_ERR_WORKSPACE;
   }
   int nb = loss_blocks(N);
-  hipLaunchKernelGGL(k_ce_fwd, dim3(nb), dim3(T), 0, s, logits, ld, labels, weight, N, C, ignore_index, (double*)ws);
-  hipLaunchKernelGGL(k_ce_finalize, dim3(1), dim3(64), 0, s, (const double*)ws, nb, stats);
+  hipLaunchKernelGGL(k_ce_fwd<1>, dim3(nb), dim3(T), 0, s, logits, ld, N, N, C, labels, weight, nullptr, nullptr, ignore_index,
+                     (double*)ws);
+  hipLaunchKernelGGL(k_ce_finalize<1>, dim3(1), dim3(64), 0, s, (const double*)ws, nb, 1, 0, stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -491,8 +363,8 @@ int mm_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* w
   MM_CHECK_ARG(N >= 0, "ce: negative N");
   if (N == 0) return MM_OK;
   MM_CHECK_ARG(logits && labels && stats && grad_out && dlogits, "ce: null logits, labels, stats, grad_out or dlogits");
-  hipLaunchKernelGGL(k_ce_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, labels, weight, N, C, ignore_index, stats,
-                     grad_out, dlogits, ld_d);
+  hipLaunchKernelGGL(k_ce_bwd<1>, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, N, C, labels, weight, nullptr, nullptr,
+                     ignore_index, stats, grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -510,9 +382,9 @@ int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
     return MM_ERR_WORKSPACE;
   }
   int nb = loss_blocks(N);
-  hipLaunchKernelGGL(k_ce2_fwd, dim3(nb), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index,
+  hipLaunchKernelGGL(k_ce_fwd<2>, dim3(nb), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index,
                      (double*)ws);
-  hipLaunchKernelGGL(k_ce2_finalize, dim3(1), dim3(64), 0, s, (const double*)ws, nb, (labels0 ? 1 : 0) | (labels1 ? 2 : 0),
+  hipLaunchKernelGGL(k_ce_finalize<2>, dim3(1), dim3(64), 0, s, (const double*)ws, nb, (labels0 ? 1 : 0) | (labels1 ? 2 : 0),
                      zero_if_empty, stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
@@ -524,7 +396,7 @@ int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
   MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C && ld_d >= C, "ce2: bad C");
   MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N, "ce2: the split must lie in [0, N]");
   if (N == 0) return MM_OK;
-  hipLaunchKernelGGL(k_ce2_bwd, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1,
+  hipLaunchKernelGGL(k_ce_bwd<2>, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1,
                      ignore_index, stats, grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
   return MM_OK;

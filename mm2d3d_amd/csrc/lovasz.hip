@@ -16,6 +16,7 @@
 // uncounted row gets 0x3F800001 and sorts behind e == 0.  30 significant bits = three 10-bit digits.
 #include "common.h"
 #include "pointpred.h"
+#include "rows.h"
 
 namespace {
 constexpr int T = 256;
@@ -64,23 +65,6 @@ __device__ inline int block_excl_scan(int v, int* tot, int* wsum /*[WAVES] LDS*/
   return base + inc - v;
 }
 
-__device__ inline double block_sum(double v, double* red /*[T] LDS*/) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-__device__ inline double wave_sum64(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
-
 // counts[0 .. C) = foreground rows per class, counts[C] = counted rows (zeroed by the caller)
 __global__ __launch_bounds__(T) void k_lv_keys(const float* __restrict__ logits, int ld, int64_t N, int C,
                                                 const int64_t* __restrict__ labels, int64_t ignore, float* __restrict__ err,
@@ -91,7 +75,7 @@ __global__ __launch_bounds__(T) void k_lv_keys(const float* __restrict__ logits,
   const int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
   if (i < N) {
     const int64_t y = labels[i];
-    if (y == ignore || y < 0 || y >= C) {
+    if (!label_counted(y, ignore, C)) {
       for (int c = 0; c < C; c++) {
         err[c * N + i] = -1.f;
         keys[c * N + i] = KEY_UNCOUNTED;
@@ -99,11 +83,8 @@ __global__ __launch_bounds__(T) void k_lv_keys(const float* __restrict__ logits,
       }
     } else {
       const float* x = logits + i * ld;
-      float m = x[0];
-      for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-      float s = 0.f;
-      for (int c = 0; c < C; c++) s += expf(x[c] - m);
-      const float inv = 1.f / s;
+      const RowLse l = row_lse(x, C);
+      const float m = l.m, inv = 1.f / l.s;
       for (int c = 0; c < C; c++) {
         const float p = expf(x[c] - m) * inv;
         const bool fg = c == (int)y;
@@ -317,7 +298,7 @@ __global__ __launch_bounds__(T) void k_lv_eval(const unsigned* __restrict__ keys
     const int64_t row = v & 0x00FFFFFFu;
     if (row < N) coef[cbase + row] = g == 0.f ? 0.f : (fg ? -q : q);
   }
-  const double s = block_sum(sum, red);
+  const double s = block_sum<T>(sum, red);
   if (threadIdx.x == 0) partial[(int64_t)c * ntiles + t] = s;
 }
 
@@ -328,10 +309,9 @@ __global__ __launch_bounds__(T) void k_lv_finalize(const double* __restrict__ pa
   __shared__ double lc[MAXC];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int c = w; c < C; c += WAVES) {
-    double a = 0.0;
-    for (int i = lane; i < ntiles; i += 64) a += partial[(int64_t)c * ntiles + i];
-    a = wave_sum64(a);
-    if (lane == 0) lc[c] = a;
+    double a[1];
+    sum_partials<1>(partial + (int64_t)c * ntiles, ntiles, lane, a);
+    if (lane == 0) lc[c] = a[0];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -358,11 +338,8 @@ __global__ __launch_bounds__(T) void k_lv_bwd(const float* __restrict__ logits, 
     for (int c = 0; c < C; c++) d[c] = 0.f;
     return;
   }
-  float m = x[0];
-  for (int c = 1; c < C; c++) m = fmaxf(m, x[c]);
-  float s = 0.f;
-  for (int c = 0; c < C; c++) s += expf(x[c] - m);
-  const float inv = 1.f / s;
+  const RowLse l = row_lse(x, C);
+  const float m = l.m, inv = 1.f / l.s;
   float dot = 0.f;
   for (int c = 0; c < C; c++) dot += coef[c * N + i] * (expf(x[c] - m) * inv);
   const float g = gout[0];

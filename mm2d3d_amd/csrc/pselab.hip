@@ -8,6 +8,7 @@
 // Counts are integers and are summed with integer atomics: the result does not depend on the order of the additions.
 #include "common.h"
 #include "pointpred.h"
+#include "rows.h"
 
 namespace {
 constexpr int PT = 128;      // points per workgroup of the prediction kernel
@@ -15,9 +16,8 @@ constexpr int T = 256;
 constexpr int RADIX = 256;   // 8 bits per pass
 constexpr int MAX_BLOCKS = 2048;
 
-// ---- prediction.  The [rows, C] blocks of both logit matrices are copied into LDS with consecutive lanes on consecutive
-// addresses of a row (a lane per point reading its own row strides by ld floats); each lane then reads its row from LDS,
-// rows pitched to an odd number of words so that the 64 lanes fall on distinct banks.
+// ---- prediction.  The [rows, C] blocks of both logit matrices go through LDS (stage_rows of rows.h: coalesced copies, then each
+// lane reads its own row, pitched to an odd number of words).
 template <bool HAS3>
 __global__ __launch_bounds__(PT) void k_pselab_predict(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3,
                                                         int64_t N, int C, float* __restrict__ p2, uint8_t* __restrict__ y2,
@@ -29,11 +29,8 @@ __global__ __launch_bounds__(PT) void k_pselab_predict(const float* __restrict__
   const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
   float* ta = tile;
   float* tb = tile + PT * pitch;
-  for (int e = threadIdx.x; e < rows * C; e += PT) {
-    const int r = e / C, c = e - r * C;
-    ta[r * pitch + c] = l2[(row0 + r) * ld2 + c];
-    if (HAS3) tb[r * pitch + c] = l3[(row0 + r) * ld3 + c];
-  }
+  stage_rows<PT>(ta, l2 + row0 * ld2, ld2, rows, C, pitch);
+  if (HAS3) stage_rows<PT>(tb, l3 + row0 * ld3, ld3, rows, C, pitch);
   __syncthreads();
   if ((int)threadIdx.x >= rows) return;
   const MMPointPred r = mm_point_predict<HAS3>(ta + threadIdx.x * pitch, tb + threadIdx.x * pitch, C);
@@ -64,11 +61,8 @@ __global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__
   const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
   float* ta = tile;
   float* tb = tile + PT * pitch;
-  for (int e = threadIdx.x; e < rows * C; e += PT) {
-    const int r = e / C, c = e - r * C;
-    ta[r * pitch + c] = l2[(row0 + r) * ld2 + c];
-    tb[r * pitch + c] = l3[(row0 + r) * ld3 + c];
-  }
+  stage_rows<PT>(ta, l2 + row0 * ld2, ld2, rows, C, pitch);
+  stage_rows<PT>(tb, l3 + row0 * ld3, ld3, rows, C, pitch);
   __syncthreads();
   bool k2 = false, k3 = false;
   if ((int)threadIdx.x < rows) {

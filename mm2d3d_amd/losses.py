@@ -69,20 +69,54 @@ def cross_entropy(pred, gt, weight=None, ignore_index=-100):
     return _CrossEntropyFn.apply(pred, gt, _device_weight(weight, pred.device), ignore_index)
 
 
+def _row_pitched(t):
+    """fp32 [N, C] that the row kernels read in place: a row-pitched view (stride(1) == 1) stays, as pselab._logits does, anything
+    else is copied."""
+    t = t.to(F32)
+    N, C = t.shape
+    if t.stride(1) != 1 or (N > 1 and t.stride(0) < C):
+        t = t.contiguous()
+    return t, (t.stride(0) if N > 1 else C)
+
+
+def _grad_rows(logits, in_dtype, launch):
+    """The gradient of a row loss: ``launch(d)`` has a backward kernel write the fp32 [N, C] buffer ``d`` (row pitch C), which goes
+    back in the dtype the logits came in."""
+    d = torch.empty(tuple(logits.shape), dtype=F32, device=logits.device)
+    launch(d)
+    return d if in_dtype == F32 else d.to(in_dtype)
+
+
+def _labels(gt, n, device, ignore_index, who, which):
+    """int64 labels of a segment of ``n`` rows on ``device``; ``None`` = unlabelled."""
+    if gt is None:
+        return None
+    gt = gt.to(device=device, dtype=torch.int64).contiguous()
+    if gt.dim() != 1 or gt.shape[0] != n:
+        raise ValueError(f"{who}: {which} has shape {tuple(gt.shape)}, its segment has {n} rows")
+    # an empty tensor has no address, and no address means "unlabelled" to the library: a labelled segment without rows
+    # (0/0 unless zero_if_empty) passes one label that no row reads
+    return gt if n else gt.new_full((1,), ignore_index)
+
+
+def _class_weights(w, C, device, who, which):
+    w = _device_weight(w, device)
+    if w is not None and w.numel() != C:
+        raise ValueError(f"{who}: {which} has {w.numel()} entries for {C} classes")
+    return w
+
+
 class _CrossEntropyPairFn(torch.autograd.Function):
     """Rows [0, split) of ``logits`` against (labels0, weight0), rows [split, N) against (labels1, weight1): one forward call,
-    and ONE backward launch that writes the whole gradient from both upstream gradients (csrc/loss.hip k_ce2_*)."""
+    and ONE backward launch that writes the whole gradient from both upstream gradients (csrc/loss.hip k_ce_*<2>)."""
 
     @staticmethod
     def forward(ctx, logits, split, labels0, weight0, labels1, weight1, ignore_index, zero_bits):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
-        logits = logits.to(F32)
+        logits, ld = _row_pitched(logits)
         N, C = logits.shape
-        if logits.stride(1) != 1 or (N > 1 and logits.stride(0) < C):
-            logits = logits.contiguous()  # a row-pitched view (stride(1) == 1) is read in place, as pselab._logits does
-        ld = logits.stride(0) if N > 1 else C
         stats = torch.empty(4, dtype=F32, device=logits.device)
         ws = _lib.workspace.get(int(L.mm_ce2_ws_bytes()), logits.device)
         check(L.mm_ce2_fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
@@ -97,12 +131,10 @@ class _CrossEntropyPairFn(torch.autograd.Function):
         logits, labels0, weight0, labels1, weight1, stats = ctx.saved_tensors
         ld, split, ignore_index = ctx.args
         N, C = logits.shape
-        d = torch.empty((N, C), dtype=F32, device=logits.device)
         g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
-        check(L.mm_ce2_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
-                           ptr(stats), ptr(g), ptr(d), C, stream()), "ce2_bwd")
-        if ctx.in_dtype != F32:
-            d = d.to(ctx.in_dtype)
+        d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
+            L.mm_ce2_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                         ptr(stats), ptr(g), ptr(d), C, stream()), "ce2_bwd"))
         return d, None, None, None, None, None, None, None
 
 
@@ -124,38 +156,13 @@ def cross_entropy_pair(pred, split, gt_head=None, gt_tail=None, weight_head=None
     N, split = int(pred.shape[0]), int(split)
     if not 0 <= split <= N:
         raise ValueError(f"cross_entropy_pair: split {split} outside [0, {N}]")
-
-    def labels(gt, n, which):
-        if gt is None:
-            return None
-        gt = gt.to(device=pred.device, dtype=torch.int64).contiguous()
-        if gt.dim() != 1 or gt.shape[0] != n:
-            raise ValueError(f"cross_entropy_pair: {which} has shape {tuple(gt.shape)}, its segment has {n} rows")
-        # an empty tensor has no address, and no address means "unlabelled" to the library: a labelled segment without rows
-        # (0/0 unless zero_if_empty) passes one label that no row reads
-        return gt if n else gt.new_full((1,), ignore_index)
-
-    gt_head, gt_tail = labels(gt_head, split, "gt_head"), labels(gt_tail, N - split, "gt_tail")
-    C = int(pred.shape[1])
-
-    def weights(w, which):
-        w = _device_weight(w, pred.device)
-        if w is not None and w.numel() != C:
-            raise ValueError(f"cross_entropy_pair: {which} has {w.numel()} entries for {C} classes")
-        return w
-
+    who, dev, C = "cross_entropy_pair", pred.device, int(pred.shape[1])
+    gt_head = _labels(gt_head, split, dev, ignore_index, who, "gt_head")
+    gt_tail = _labels(gt_tail, N - split, dev, ignore_index, who, "gt_tail")
+    weight_head = _class_weights(weight_head, C, dev, who, "weight_head")
+    weight_tail = _class_weights(weight_tail, C, dev, who, "weight_tail")
     bits = (1 if zero_if_empty[0] else 0) | (2 if zero_if_empty[1] else 0)
-    return _CrossEntropyPairFn.apply(pred, split, gt_head, weights(weight_head, "weight_head"), gt_tail,
-                                     weights(weight_tail, "weight_tail"), int(ignore_index), bits)
-
-
-def _row_pitched(t):
-    """fp32 [N, C] that the row kernels read in place: a row-pitched view (stride(1) == 1) stays, anything else is copied."""
-    t = t.to(F32)
-    N, C = t.shape
-    if t.stride(1) != 1 or (N > 1 and t.stride(0) < C):
-        t = t.contiguous()
-    return t, (t.stride(0) if N > 1 else C)
+    return _CrossEntropyPairFn.apply(pred, split, gt_head, weight_head, gt_tail, weight_tail, int(ignore_index), bits)
 
 
 class _CrossEntropySoftPairFn(torch.autograd.Function):
@@ -188,12 +195,10 @@ class _CrossEntropySoftPairFn(torch.autograd.Function):
         logits, labels0, weight0, ta, tb, stats = ctx.saved_tensors
         ld, ld_a, ld_b, split, temperature, thr, ignore_index = ctx.args
         N, C = logits.shape
-        d = torch.empty((N, C), dtype=F32, device=logits.device)
         g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
-        check(L.mm_ce2s_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
-                            temperature, thr, ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd")
-        if ctx.in_dtype != F32:
-            d = d.to(ctx.in_dtype)
+        d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
+            L.mm_ce2s_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                          temperature, thr, ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd"))
         return d, None, None, None, None, None, None, None, None
 
 
@@ -237,15 +242,8 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
     teacher = logits(teacher, "teacher")
     if teacher_other is not None:
         teacher_other = logits(teacher_other, "teacher_other")
-    if gt_head is not None:
-        gt_head = gt_head.to(device=pred.device, dtype=torch.int64).contiguous()
-        if gt_head.dim() != 1 or gt_head.shape[0] != split:
-            raise ValueError(f"{who}: gt_head has shape {tuple(gt_head.shape)}, its segment has {split} rows")
-        if not split:
-            gt_head = gt_head.new_full((1,), ignore_index)  # a labelled head without rows: 0/0, as cross_entropy_pair
-    weight_head = _device_weight(weight_head, pred.device)
-    if weight_head is not None and weight_head.numel() != C:
-        raise ValueError(f"{who}: weight_head has {weight_head.numel()} entries for {C} classes")
+    gt_head = _labels(gt_head, split, pred.device, ignore_index, who, "gt_head")  # a labelled head without rows: 0/0
+    weight_head = _class_weights(weight_head, C, pred.device, who, "weight_head")
     return _CrossEntropySoftPairFn.apply(pred, split, gt_head, weight_head, teacher, teacher_other, float(temperature),
                                          0.0 if threshold is None else float(threshold), int(ignore_index))
 
@@ -276,11 +274,9 @@ class _LovaszFn(torch.autograd.Function):
         L = _lib.lib()
         logits, coef = ctx.saved_tensors
         N, C = logits.shape
-        d = torch.empty((N, C), dtype=F32, device=logits.device)
         g = g.to(F32).contiguous()
-        check(L.mm_lovasz_bwd(ptr(logits), ctx.ld, N, C, ptr(coef), ptr(g), ptr(d), C, stream()), "lovasz_bwd")
-        if ctx.in_dtype != F32:
-            d = d.to(ctx.in_dtype)
+        d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
+            L.mm_lovasz_bwd(ptr(logits), ctx.ld, N, C, ptr(coef), ptr(g), ptr(d), C, stream()), "lovasz_bwd"))
         return d, None, None, None
 
 

@@ -1,5 +1,6 @@
 """The row-wise loss and evaluation kernels of csrc/loss.hip, called straight through the C ABI (mm_ce_fwd, mm_ce_bwd, mm_kl_fwd,
-mm_kl_bwd, mm_eval_confusion) against the float64 numpy references of tests/_loss_ref.py.
+mm_kl_bwd, mm_eval_confusion) against the float64 numpy references of tests/_loss_ref.py, and mm_ce_* against mm_ce2_* over one
+segment, bit for bit.
 
 Exact, whatever the order of the kernels' sums: the weight sum stats[1] when the class weights are multiples of 1/8 (the makers
 assert that the sum is a float32 number), zero gradient rows of rows that are not counted, everything at C = 1, and every count of
@@ -215,6 +216,35 @@ def test_cross_entropy_forward_and_backward_against_float64(name):
         stats2, dl2 = _run_ce(L, lib, c, x, labels, w, g, ws)
         assert torch.equal(stats2.flat.view(torch.int32), stats.flat.view(torch.int32)), "two runs differ in the loss bits"
         assert torch.equal(dl2.flat.view(torch.int32), dl.flat.view(torch.int32)), "two runs differ in the gradient bits"
+
+
+@pytest.mark.parametrize("name", list(CE_CASES))
+def test_cross_entropy_is_the_two_segment_entry_with_one_segment_bit_for_bit(name):
+    """mm_ce_* against mm_ce2_* with P = N, the tail unlabelled and zero_if_empty = 0: k_ce_*<1> and k_ce_*<2> of csrc/loss.hip are
+    one template, so loss, weight sum and every gradient word are the same bits (NaN of the all-ignored cases included: int32
+    views), and the tail reports loss 0 over weight 0."""
+    c, d = CE_CASES[name], ce_inputs(name)
+    L, lib = _abi()
+    n, C = c["n"], c["c"]
+    x = Rows(d["x"], n, C, c["ld"], 4)
+    # N = 0: an address all the same (no address = "unlabelled" to mm_ce2_*), one label that no row reads, as losses._labels
+    labels = Ints(d["labels"] if n else np.array([c["ignore"]]), dtype=torch.int64)
+    w = vec(d["weight"], fill=float("nan")) if d["weight"] is not None else None
+    g, ws = vec([c["g"]], fill=float("nan")), _workspace(L)
+    stats, dl = _run_ce(L, lib, c, x, labels, w, g, ws)
+    ws2 = torch.empty(int(L.mm_ce2_ws_bytes()), dtype=torch.uint8, device=_dev())
+    stats2, dl2 = vec(None, 4), Rows(None, n, C, c["ld_d"], 4, fill=SENTINEL)
+    lib.check(L.mm_ce2_fwd(x.ptr, c["ld"], n, n, C, labels.ptr, w.ptr if w else None, None, None, c["ignore"], 0, stats2.ptr,
+                           ws2.data_ptr(), ws2.numel(), lib.stream()), "ce2_fwd")
+    lib.check(L.mm_ce2_bwd(x.ptr, c["ld"], n, n, C, labels.ptr, w.ptr if w else None, None, None, c["ignore"], stats2.ptr, g.ptr, dl2.ptr,
+                           c["ld_d"], lib.stream()), "ce2_bwd")
+    torch.cuda.synchronize()
+    assert stats2.padding_untouched() and dl2.padding_untouched()
+    s1, s2 = stats.bits()[0], stats2.bits()[0]
+    assert np.array_equal(s2[:2], s1), f"{name}: (loss, sum_w) bits {s2[:2]} of mm_ce2_fwd, {s1} of mm_ce_fwd"
+    tail = stats2.get32()[0, 2:]
+    assert (tail == 0.0).all(), f"{name}: the unlabelled tail reports (loss, sum_w) = {tail}, not (0.0, 0.0)"
+    assert torch.equal(dl2.flat.view(torch.int32), dl.flat.view(torch.int32)), f"{name}: the gradients of mm_ce2_bwd and mm_ce_bwd differ"
 
 
 # ----------------------------------------------------------------------------------------------------------------------- KL

@@ -16,7 +16,8 @@ CATS = [
                               r"k_batch_lower|k_csr_|k_init_level|k_meta|k_hash|k_dedupe|k_scan|k_tile|k_bucket"),
     ("rocPRIM", r"rocprim"),
     ("2d misc (pool/heads/concat/pack/dropout)", r"k_maxpool|k_head|k_box5|k_concat|k_pack_weights|k_copy_rows|k_dropout|k_bnpool"),
-    ("points / lifting / losses", r"k_gate|k_seg_mean|k_row_gather|k_linear|k_lift|k_ce_|k_kl_|k_segment|k_key"),
+    ("points / lifting / losses", r"k_gate|k_seg_mean|k_row_gather|k_linear|k_lift|k_ce_|k_kl_|k_segment|k_key|"
+                                  r"k_ce2s|k_lv_|k_teacher|k_pselab|k_refine"),
     ("optimiser / amp / packs", r"k_adamw|k_optim|k_amp|k_grad_nonfinite|k_os_pack|k_pack_frag"),
     ("torch (at::)", r"at::|at_cuda|elementwise_kernel|reduce_kernel|CatArray|index"),
     ("runtime fill/copy", r"__amd_rocclr"),
