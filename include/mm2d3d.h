@@ -434,6 +434,16 @@ int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const 
 int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                 int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
                 const float* stats, const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
+/* The same pair with one threshold per class, thr_cls[C] fp32 on the device, in place of the scalar: a tail row is kept iff its
+ * confidence >= thr_cls[y] in float32, y the arg-max the confidence belongs to (of softmax(ta), or with tb of the ensemble; the
+ * first maximum wins).  A NaN threshold keeps nothing of its class.  Everything else, the return codes included, is as above; the
+ * scalar entry points run the same kernels and keep their results bit for bit. */
+int mm_ce2s_fwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                    int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature,
+                    const float* thr_cls, float* stats, int64_t* kept, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_ce2s_bwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                    int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature,
+                    const float* thr_cls, const float* stats, const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
 /* Lovasz-softmax loss (Berman et al., CVPR 2018) of logits [N, C] (row pitch ld) against int64 labels (csrc/lovasz.hip).
  * Counted rows: label != ignore_index and 0 <= label < C, as in mm_ce2_*; p = softmax(x) per row.  For every class c:
  * fg_i = [y_i == c], e_i = |fg_i - p_ic|; the counted rows are ordered by e descending, stable in the row index.  With G = sum fg,
@@ -498,6 +508,29 @@ int mm_pselab_predict(const float* logits2d, int ld2, const float* logits3d, int
 int mm_teacher_labels(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, float thr,
                       int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d, float* prob_3d,
                       unsigned long long* kept, mm_stream_t stream);
+/* mm_teacher_labels with one threshold per output and class: thr_cls[2][C] fp32 on the device (row 0 the 2D output's, row 1 the
+ * 3D output's) in place of thr.  Output o keeps a row iff p >= thr_cls[o][y] in float32, y the row's label of that output; there
+ * is no "keep all" value.  The same kernel: labels, confidences and counts are otherwise those of mm_teacher_labels. */
+int mm_teacher_labels_cls(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble,
+                          const float* thr_cls, int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d,
+                          float* prob_3d, unsigned long long* kept, mm_stream_t stream);
+/* Self-adaptive per-class pseudo-label thresholds (FreeMatch, Wang et al., ICLR 2023), state on the device, no host read.
+ * Per output o (0: 2D, 1: 3D): state[o][0] = tau_o, state[o][1 + c] = pt_o[c] (fp64, the caller initialises all to 1 / C),
+ * count[o] = updates taken.  With p, y the confidence and label mm_teacher_labels gives the row for that output and q[c] the
+ * float32 per-class values behind them (softmax of the output's logits, or with ensemble != 0 the softmax average for both):
+ *   counted    a row enters output o's statistics iff p >= 0 in float32 (a NaN confidence, or the ensemble's -1 of a non-finite
+ *              row, fails: the rows threshold 0 refuses); n_o = the counted rows;
+ *   update     if n_o > 0: m_t = momentum, or with warmup != 0 min(momentum, (1 + count[o]) / (10 + count[o]));
+ *              tau_o <- m_t * tau_o + (1 - m_t) * mean p;  pt_o[c] <- m_t * pt_o[c] + (1 - m_t) * mean q[c];  count[o] += 1.
+ *              n_o == 0 leaves state and count as they are;
+ *   thr        thr[o][c] = (float)((pt_o[c] / max_c pt_o[c]) * tau_o), in fp64 in this order, always written from the (possibly
+ *              unchanged) state: what mm_teacher_labels_cls and mm_ce2s_*_cls take.
+ * Two launches: fp64 partial sums and integer row counts per workgroup of a capped grid, then one workgroup that sums them in a
+ * fixed order, updates the state in place and writes thr.  No atomics: bit-stable run to run.  N == 0 runs the second launch
+ * alone.  momentum in [0, 1); C <= 32; every argument check is made before the first launch. */
+size_t mm_pl_adapt_ws_bytes(void);
+int mm_pl_adapt(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, double momentum,
+                int warmup, double* state, int64_t* count, float* thr, void* ws, size_t ws_bytes, mm_stream_t stream);
 /* lib/utils/refine_pseudo_labels.py, exact: for every class c of [0, C) that occurs n_c > 0 times, med_c = the element of rank
  * (n_c - 1) / 2 (ascending, 0-based: torch.median's lower median) among the probs of that class, thr_c = min(med_c, 0.9f);
  * labels_out[i] = ignore_label where labels[i] == c and probs[i] < thr_c, else labels[i].  Labels outside [0, C) pass through.

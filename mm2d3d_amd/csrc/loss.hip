@@ -119,11 +119,11 @@ __device__ inline float soft_dot(const float* t, float tm, float inv_t, const fl
 }
 
 // partial[b] = (sum w*nll, sum w) of the head, (sum of the kept rows' soft cross entropies, kept rows) of the tail
-template <bool HAS_B>
+template <bool HAS_B, bool CLS>
 __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                   const int64_t* __restrict__ labels0, const float* __restrict__ weight0, int64_t ignore,
                                                   const float* __restrict__ ta, int ld_a, const float* __restrict__ tb, int ld_b,
-                                                  float inv_t, float thr, double* __restrict__ partial) {
+                                                  float inv_t, float thr, const float* __restrict__ thr_cls, double* __restrict__ partial) {
   extern __shared__ float tile[];  // [HAS_B ? 3 : 2][ST][pitch]
   const int pitch = C | 1;
   float* sx = tile;
@@ -160,7 +160,9 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
       const float* a = sa + r * pitch;
       const float* b = sb + r * pitch;
       const MMPointPred pr = mm_point_predict<HAS_B>(a, b, C);
-      if ((HAS_B ? pr.pe : pr.pa) >= thr) {  // a NaN confidence (or the ensemble's -1 of a non-finite row) is never kept
+      // CLS (mm_ce2s_*_cls): the threshold of the row's own class.  A NaN confidence (or the ensemble's -1 of a non-finite row)
+      // is never kept
+      if ((HAS_B ? pr.pe : pr.pa) >= (CLS ? thr_cls[HAS_B ? pr.ie : pr.ia] : thr)) {
         const RowLse l = row_lse(x, C);
         const float lse = l.m + logf(l.s);
         float v = soft_dot(a, a[pr.ia], inv_t, x, lse, C);
@@ -195,11 +197,12 @@ __global__ __launch_bounds__(64) void k_ce2s_finalize(const double* __restrict__
 // One tile per workgroup, every row written once: the gradient rows are formed in place in the staged logits tile and leave it
 // with consecutive lanes on consecutive addresses.  Head: gout[0] * w[y] / sum_w * (softmax - onehot), as k_ce_bwd; kept tail
 // rows: gout[1] / K * (softmax - q), q recomputed from the teacher rows; every other row: zeros.
-template <bool HAS_B>
+template <bool HAS_B, bool CLS>
 __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                   const int64_t* __restrict__ labels0, const float* __restrict__ weight0, int64_t ignore,
                                                   const float* __restrict__ ta, int ld_a, const float* __restrict__ tb, int ld_b,
-                                                  float inv_t, float thr, const float* __restrict__ stats,
+                                                  float inv_t, float thr, const float* __restrict__ thr_cls,
+                                                  const float* __restrict__ stats,
                                                   const float* __restrict__ gout, float* __restrict__ dlogits, int ld_d) {
   extern __shared__ float tile[];  // [HAS_B ? 3 : 2][ST][pitch]
   const int pitch = C | 1;
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
       }
     } else {
       pr = mm_point_predict<HAS_B>(a, b, C);
-      live = (HAS_B ? pr.pe : pr.pa) >= thr;
+      live = (HAS_B ? pr.pe : pr.pa) >= (CLS ? thr_cls[HAS_B ? pr.ie : pr.ia] : thr);
       if (live) k = gout[1] / stats[3];
     }
     if (!live) {
@@ -404,23 +407,26 @@ int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
 
 size_t mm_ce2s_ws_bytes() { return mm_align((size_t)S_MAX_PART * 4 * sizeof(double)) + 256; }
 
+// thr_cls != NULL (mm_ce2s_*_cls): thr_cls[C] on the device replaces the scalar thr
 static int ce2s_check(const float* logits, int ld, int64_t N, int64_t P, int C, const float* ta, int ld_a, const float* tb, int ld_b,
-                      float temperature, float thr) {
+                      float temperature, float thr, const float* thr_cls, bool cls) {
   MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C, "ce2s: bad C");
   MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N && N <= (int64_t)ST * 0x7fffffff, "ce2s: the split must lie in [0, N]");
   MM_CHECK_ARG(logits || N == 0, "ce2s: null logits");
   MM_CHECK_ARG(ta || (P == N && !tb), "ce2s: tail rows without teacher logits");
   MM_CHECK_ARG((!ta || ld_a >= C) && (!tb || ld_b >= C), "ce2s: teacher row pitch below C");
   MM_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "ce2s: the temperature must be a finite number > 0");
-  MM_CHECK_ARG(thr >= 0.f && thr <= 1.f, "ce2s: the threshold must lie in [0, 1]");
+  if (cls)
+    MM_CHECK_ARG(thr_cls, "ce2s: null class thresholds");
+  else
+    MM_CHECK_ARG(thr >= 0.f && thr <= 1.f, "ce2s: the threshold must lie in [0, 1]");
   return MM_OK;
 }
 
-// stats[4] = head loss, head weight sum, tail loss, kept rows K (as a float); kept[0] = K exactly; see include/mm2d3d.h
-int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
-                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr, float* stats,
-                int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr)) return rc;
+static int ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                    int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                    const float* thr_cls, bool cls, float* stats, int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr, thr_cls, cls)) return rc;
   MM_CHECK_ARG(stats, "ce2s: null stats");
   if (ws_bytes < (size_t)S_MAX_PART * 4 * sizeof(double)) {
     mm_set_error("ce2s: workspace too small");
@@ -430,35 +436,76 @@ int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const 
   const int nb = (int)(nt > S_MAX_PART ? S_MAX_PART : nt);
   const size_t lds = (size_t)(tb ? 3 : 2) * ST * (C | 1) * sizeof(float);
   const float inv_t = 1.f / temperature;
-  if (tb)
-    hipLaunchKernelGGL(k_ce2s_fwd<true>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
-                       ld_b, inv_t, thr, (double*)ws);
-  else
-    hipLaunchKernelGGL(k_ce2s_fwd<false>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
-                       ld_b, inv_t, thr, (double*)ws);
+#define MM_CE2S_FWD(HAS_B, CLS)                                                                                                  \
+  hipLaunchKernelGGL((k_ce2s_fwd<HAS_B, CLS>), dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, \
+                     ta, ld_a, tb, ld_b, inv_t, thr, thr_cls, (double*)ws)
+  if (cls) {
+    if (tb) MM_CE2S_FWD(true, true);
+    else MM_CE2S_FWD(false, true);
+  } else {
+    if (tb) MM_CE2S_FWD(true, false);
+    else MM_CE2S_FWD(false, false);
+  }
+#undef MM_CE2S_FWD
   hipLaunchKernelGGL(k_ce2s_finalize, dim3(1), dim3(64), 0, s, (const double*)ws, nb, labels0 ? 1 : 0, stats, kept);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
 
-int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
-                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
-                const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
-  if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr)) return rc;
+static int ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                    int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                    const float* thr_cls, bool cls, const float* stats, const float* grad_out, float* dlogits, int ld_d,
+                    hipStream_t s) {
+  if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr, thr_cls, cls)) return rc;
   MM_CHECK_ARG(ld_d >= C, "ce2s: gradient row pitch below C");
   if (N == 0) return MM_OK;
   MM_CHECK_ARG(stats && grad_out && dlogits, "ce2s: null stats, grad_out or dlogits");
   const unsigned nb = (unsigned)mm_cdiv(N, (int64_t)ST);
   const size_t lds = (size_t)(tb ? 3 : 2) * ST * (C | 1) * sizeof(float);
   const float inv_t = 1.f / temperature;
-  if (tb)
-    hipLaunchKernelGGL(k_ce2s_bwd<true>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
-                       ld_b, inv_t, thr, stats, grad_out, dlogits, ld_d);
-  else
-    hipLaunchKernelGGL(k_ce2s_bwd<false>, dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb,
-                       ld_b, inv_t, thr, stats, grad_out, dlogits, ld_d);
+#define MM_CE2S_BWD(HAS_B, CLS)                                                                                                  \
+  hipLaunchKernelGGL((k_ce2s_bwd<HAS_B, CLS>), dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, \
+                     ta, ld_a, tb, ld_b, inv_t, thr, thr_cls, stats, grad_out, dlogits, ld_d)
+  if (cls) {
+    if (tb) MM_CE2S_BWD(true, true);
+    else MM_CE2S_BWD(false, true);
+  } else {
+    if (tb) MM_CE2S_BWD(true, false);
+    else MM_CE2S_BWD(false, false);
+  }
+#undef MM_CE2S_BWD
   MM_LAUNCH_CHECK();
   return MM_OK;
+}
+
+// stats[4] = head loss, head weight sum, tail loss, kept rows K (as a float); kept[0] = K exactly; see include/mm2d3d.h
+int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr, float* stats,
+                int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
+  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr, nullptr, false, stats, kept,
+                  ws, ws_bytes, s);
+}
+
+int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
+  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr, nullptr, false, stats,
+                  grad_out, dlogits, ld_d, s);
+}
+
+// the same pair with a threshold per class: a tail row is kept iff its confidence >= thr_cls[its arg-max class]
+int mm_ce2s_fwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                    int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, const float* thr_cls,
+                    float* stats, int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
+  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, 0.f, thr_cls, true, stats, kept,
+                  ws, ws_bytes, s);
+}
+
+int mm_ce2s_bwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                    int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, const float* thr_cls,
+                    const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
+  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, 0.f, thr_cls, true, stats,
+                  grad_out, dlogits, ld_d, s);
 }
 
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws, size_t ws_bytes,

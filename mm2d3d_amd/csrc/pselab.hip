@@ -2,6 +2,9 @@
 //   mm_pselab_predict   per point: max and argmax of softmax(2D logits), of softmax(3D logits) and of their average
 //   mm_teacher_labels   the same per-point expression, written as the int64 training labels of both heads (a mean teacher that
 //                       labels the target batch inside the step), with an optional confidence threshold and kept counts
+//   mm_teacher_labels_cls  the same launch with one threshold per output and class, read from the device
+//   mm_pl_adapt         the self-adaptive per-class thresholds (FreeMatch): running confidence and class mass of both outputs,
+//                       kept on the device and updated from every target batch; two launches, no atomics, no host read
 //   mm_pselab_refine    lib/utils/refine_pseudo_labels.py, exact: per class the lower median of the confidences by a
 //                       most-significant-digit radix select (four 8-bit passes over the order-preserving uint32 image of the
 //                       floats), threshold min(median, 0.9f), labels below it become ignore_label
@@ -50,12 +53,15 @@ __global__ __launch_bounds__(PT) void k_pselab_predict(const float* __restrict__
 // thr >= 0: a label whose confidence is not >= thr (a NaN confidence included) becomes `ignore`.  kept[2]: labels that were
 // kept, per output - a ballot per wave, the two waves' counts through two words of the tile (its rows are dead by then), one
 // 64-bit integer atomic per workgroup and counter.
-template <bool ENS>
+// CLS (mm_teacher_labels_cls): thr_cls[2][C] on the device replaces thr - output o keeps a row iff p >= thr_cls[o][y].
+template <bool ENS, bool CLS>
 __global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3,
-                                                        int64_t N, int C, float thr, int64_t ignore, int64_t* __restrict__ y2,
-                                                        int64_t* __restrict__ y3, float* __restrict__ p2, float* __restrict__ p3,
-                                                        unsigned long long* __restrict__ kept) {
+                                                        int64_t N, int C, float thr, const float* __restrict__ thr_cls, int64_t ignore,
+                                                        int64_t* __restrict__ y2, int64_t* __restrict__ y3, float* __restrict__ p2,
+                                                        float* __restrict__ p3, unsigned long long* __restrict__ kept) {
   extern __shared__ float tile[];  // [2][PT][pitch]
+  __shared__ float th[CLS ? 2 * MM_PRED_MAXC : 1];
+  if (CLS && (int)threadIdx.x < 2 * C) th[threadIdx.x] = thr_cls[threadIdx.x];
   const int pitch = C | 1;
   const int64_t row0 = (int64_t)blockIdx.x * PT;
   const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
@@ -69,8 +75,8 @@ __global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__
     const MMPointPred r = mm_point_predict<true>(ta + threadIdx.x * pitch, tb + threadIdx.x * pitch, C);
     const float pa = ENS ? r.pe : r.pa, pb = ENS ? r.pe : r.pb;
     const int ia = ENS ? r.ie : r.ia, ib = ENS ? r.ie : r.ib;
-    k2 = thr < 0.f || pa >= thr;
-    k3 = thr < 0.f || pb >= thr;
+    k2 = CLS ? pa >= th[ia] : (thr < 0.f || pa >= thr);
+    k3 = CLS ? pb >= th[C + ib] : (thr < 0.f || pb >= thr);
     const int64_t i = row0 + threadIdx.x;
     y2[i] = k2 ? (int64_t)ia : ignore;
     y3[i] = k3 ? (int64_t)ib : ignore;
@@ -88,6 +94,141 @@ __global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__
     unsigned n = 0;
     for (int w = 0; w < PT / 64; w++) n += cnt[2 * w + threadIdx.x];
     if (n) atomicAdd(&kept[threadIdx.x], (unsigned long long)n);
+  }
+}
+
+// ---- self-adaptive per-class thresholds (mm_pl_adapt; include/mm2d3d.h has the definition).  Per output o the state is tau_o
+// and pt_o[c]; a batch contributes mean p and mean q[c] over its counted rows (p >= 0 in float32: the rows threshold 0 keeps).
+// k_pl_stats: a capped grid walks the 128-row tiles, staged as in k_teacher_labels.  A lane that kept 2 * (1 + C) accumulators
+// indexed by a runtime c would spill them, so each lane writes its row's q values back INTO the staged tile (zeros for a row that
+// is not counted) and its confidences into conf[]; then thread (o, j) sums column j of output o over the tile's rows in ascending
+// order into ONE fp64 accumulator that it carries across the workgroup's tiles.  Row counts are ballots, integers throughout.
+// k_pl_update: one workgroup sums the <= PL_MAX_WG partials per quantity (a wave per quantity, lanes striding the workgroups,
+// then the shuffle tree: a fixed order), applies the update in place and writes the thresholds.  No atomics of any kind.
+constexpr int PL_MAX_WG = 1024;  // workgroups of the statistics pass = partials per quantity
+constexpr int PL_UT = 1024;      // threads of the update kernel: sixteen waves share the 2 * (1 + C) + 2 quantities
+
+template <bool ENS>
+__global__ __launch_bounds__(PT) void k_pl_stats(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3, int64_t N,
+                                                  int C, double* __restrict__ psum /*[grid][2][1 + C]*/,
+                                                  long long* __restrict__ pcnt /*[grid][2]*/) {
+  extern __shared__ float tile[];  // [2][PT][pitch], then conf [2][PT]
+  __shared__ unsigned wcnt[PT / 64][2];
+  const int pitch = C | 1;
+  float* ta = tile;
+  float* tb = tile + PT * pitch;
+  float* conf = tile + 2 * PT * pitch;
+  const int K = 1 + C;
+  const int o = (int)threadIdx.x / K, j = (int)threadIdx.x - o * K;  // the column this thread sums (threads < 2 * K)
+  double acc = 0.0;
+  unsigned n2 = 0, n3 = 0;  // per wave: every lane holds the wave's counts (a workgroup sees at most 2^28 rows: mm_pl_adapt)
+  const unsigned ntiles = (unsigned)((N + PT - 1) / PT);  // <= 2^31 - 1 (mm_pl_adapt), so t + gridDim.x does not wrap
+  for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t row0 = (int64_t)t * PT;
+    const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
+    __syncthreads();  // the previous tile's columns have been summed
+    stage_rows<PT>(ta, l2 + row0 * ld2, ld2, rows, C, pitch);
+    stage_rows<PT>(tb, l3 + row0 * ld3, ld3, rows, C, pitch);
+    __syncthreads();
+    bool k2 = false, k3 = false;
+    if ((int)threadIdx.x < rows) {
+      float* a = ta + threadIdx.x * pitch;
+      float* b = tb + threadIdx.x * pitch;
+      const MMPointPred r = mm_point_predict<true>(a, b, C);
+      const float pa = ENS ? r.pe : r.pa, pb = ENS ? r.pe : r.pb;
+      k2 = pa >= 0.f;  // a NaN confidence, or the ensemble's -1 of a non-finite row, is not counted
+      k3 = pb >= 0.f;
+      // the per-class values mm_point_predict forms: its maxima are a[ia] / b[ib], its sums run ascending in c
+      const float ma = a[r.ia], mb = b[r.ib];
+      float sa = 0.f, sb = 0.f;
+#pragma unroll 1
+      for (int c = 0; c < C; c++) {
+        sa += expf(a[c] - ma);
+        sb += expf(b[c] - mb);
+      }
+#pragma unroll 1
+      for (int c = 0; c < C; c++) {
+        const float qa = expf(a[c] - ma) / sa, qb = expf(b[c] - mb) / sb;
+        const float q2 = ENS ? 0.5f * (qa + qb) : qa, q3 = ENS ? q2 : qb;
+        a[c] = k2 ? q2 : 0.f;
+        b[c] = k3 ? q3 : 0.f;
+      }
+      conf[threadIdx.x] = k2 ? pa : 0.f;
+      conf[PT + threadIdx.x] = k3 ? pb : 0.f;
+    }
+    n2 += (unsigned)__popcll(__ballot(k2));
+    n3 += (unsigned)__popcll(__ballot(k3));
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * K) {
+      if (j == 0) {
+        const float* p = conf + o * PT;
+        for (int r = 0; r < rows; r++) acc += (double)p[r];
+      } else {
+        const float* q = (o ? tb : ta) + (j - 1);
+        for (int r = 0; r < rows; r++) acc += (double)q[r * pitch];
+      }
+    }
+  }
+  if ((int)threadIdx.x < 2 * K) psum[(int64_t)blockIdx.x * 2 * K + threadIdx.x] = acc;
+  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][0] = n2, wcnt[threadIdx.x >> 6][1] = n3;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    long long n = 0;
+    for (int w = 0; w < PT / 64; w++) n += (long long)wcnt[w][threadIdx.x];
+    pcnt[(int64_t)blockIdx.x * 2 + threadIdx.x] = n;
+  }
+}
+
+// state[2][1 + C] = (tau_o, pt_o[c]), count[2] = updates taken, thr[2][C] = float((pt_o[c] / max_c pt_o[c]) * tau_o) in fp64.
+// An output without counted rows keeps its state and its count; its thresholds are written all the same.
+__global__ __launch_bounds__(PL_UT) void k_pl_update(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nb, int C,
+                                                      double momentum, int warmup, double* __restrict__ state,
+                                                      int64_t* __restrict__ count, float* __restrict__ thr) {
+  __shared__ double tot[2 * (1 + MM_PRED_MAXC)];
+  __shared__ long long cnt[2];
+  __shared__ double cur[2 * (1 + MM_PRED_MAXC)];
+  const int K = 1 + C, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int q = wave; q < 2 * K + 2; q += PL_UT / 64) {  // uniform per wave
+    if (q < 2 * K) {
+      double v = 0.0;
+      for (int i = lane; i < nb; i += 64) v += psum[(int64_t)i * 2 * K + q];
+      v = wave_sum64(v);
+      if (lane == 0) tot[q] = v;
+    } else {
+      long long n = 0;
+      for (int i = lane; i < nb; i += 64) n += pcnt[2 * i + (q - 2 * K)];
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d, 64);
+      if (lane == 0) cnt[q - 2 * K] = n;
+    }
+  }
+  __syncthreads();
+  const int o = (int)threadIdx.x / K, j = (int)threadIdx.x - o * K;
+  if ((int)threadIdx.x < 2 * K) {
+    const long long n = cnt[o];
+    double v = state[threadIdx.x];
+    if (n > 0) {
+      const int64_t t = count[o];
+      double m = momentum;
+      if (warmup) {
+        const double w = (1.0 + (double)t) / (10.0 + (double)t);
+        m = w < m ? w : m;
+      }
+      v = m * v + (1.0 - m) * (tot[threadIdx.x] / (double)n);
+      state[threadIdx.x] = v;
+    }
+    cur[threadIdx.x] = v;
+  }
+  __syncthreads();  // every thread has read count[o]
+  if ((int)threadIdx.x < 2 * K) {
+    if (j == 0) {
+      if (cnt[o] > 0) count[o] += 1;
+    } else {
+      const double* pt = cur + o * K + 1;
+      double mx = pt[0];
+      for (int c = 1; c < C; c++) mx = pt[c] > mx ? pt[c] : mx;
+      thr[o * C + (j - 1)] = (float)((pt[j - 1] / mx) * cur[o * K]);
+    }
   }
 }
 
@@ -229,25 +370,78 @@ int mm_pselab_predict(const float* logits2d, int ld2, const float* logits3d, int
   return MM_OK;
 }
 
-int mm_teacher_labels(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, float thr,
-                      int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d, float* prob_3d,
-                      unsigned long long* kept, hipStream_t s) {
+// thr_cls == NULL: the scalar thr; else one threshold per output and class (who: the entry point's name in error texts)
+static int teacher_labels(const char* who, const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C,
+                          int ensemble, float thr, const float* thr_cls, bool cls, int64_t ignore_label, int64_t* label_2d,
+                          int64_t* label_3d, float* prob_2d, float* prob_3d, unsigned long long* kept, hipStream_t s) {
   static_assert(PT % 64 == 0, "k_teacher_labels counts per 64-lane wave");
-  MM_CHECK_ARG(C > 0 && C <= MM_PRED_MAXC, "teacher_labels: bad C");
-  MM_CHECK_ARG(N >= 0 && N <= (int64_t)PT * 0x7fffffff, "teacher_labels: bad N");
+  MM_CHECK_ARG(C > 0 && C <= MM_PRED_MAXC, "%s: bad C", who);
+  MM_CHECK_ARG(N >= 0 && N <= (int64_t)PT * 0x7fffffff, "%s: bad N", who);
   if (N == 0) return MM_OK;
-  MM_CHECK_ARG(logits2d && logits3d, "teacher_labels: null logits");
-  MM_CHECK_ARG(label_2d && label_3d, "teacher_labels: null labels");
-  MM_CHECK_ARG(ld2 >= C && ld3 >= C, "teacher_labels: row pitch below C");
+  MM_CHECK_ARG(logits2d && logits3d, "%s: null logits", who);
+  MM_CHECK_ARG(label_2d && label_3d, "%s: null labels", who);
+  MM_CHECK_ARG(!cls || thr_cls, "%s: null class thresholds", who);
+  MM_CHECK_ARG(ld2 >= C && ld3 >= C, "%s: row pitch below C", who);
   if (kept) MM_HIP(hipMemsetAsync(kept, 0, 2 * sizeof(unsigned long long), s));
   const dim3 grid((unsigned)mm_cdiv(N, PT));
   const size_t lds = (size_t)2 * PT * (C | 1) * sizeof(float);  // <= 33 KB
-  if (ensemble)
-    hipLaunchKernelGGL(k_teacher_labels<true>, grid, dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, thr, ignore_label, label_2d,
-                       label_3d, prob_2d, prob_3d, kept);
-  else
-    hipLaunchKernelGGL(k_teacher_labels<false>, grid, dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, thr, ignore_label, label_2d,
-                       label_3d, prob_2d, prob_3d, kept);
+#define MM_TL_LAUNCH(ENS, CLS)                                                                                                   \
+  hipLaunchKernelGGL((k_teacher_labels<ENS, CLS>), grid, dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, thr, thr_cls,     \
+                     ignore_label, label_2d, label_3d, prob_2d, prob_3d, kept)
+  if (cls) {
+    if (ensemble) MM_TL_LAUNCH(true, true);
+    else MM_TL_LAUNCH(false, true);
+  } else {
+    if (ensemble) MM_TL_LAUNCH(true, false);
+    else MM_TL_LAUNCH(false, false);
+  }
+#undef MM_TL_LAUNCH
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_teacher_labels(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, float thr,
+                      int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d, float* prob_3d,
+                      unsigned long long* kept, hipStream_t s) {
+  return teacher_labels("teacher_labels", logits2d, ld2, logits3d, ld3, N, C, ensemble, thr, nullptr, false, ignore_label, label_2d,
+                        label_3d, prob_2d, prob_3d, kept, s);
+}
+
+int mm_teacher_labels_cls(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble,
+                          const float* thr_cls, int64_t ignore_label, int64_t* label_2d, int64_t* label_3d, float* prob_2d,
+                          float* prob_3d, unsigned long long* kept, hipStream_t s) {
+  return teacher_labels("teacher_labels_cls", logits2d, ld2, logits3d, ld3, N, C, ensemble, 0.f, thr_cls, true, ignore_label, label_2d,
+                        label_3d, prob_2d, prob_3d, kept, s);
+}
+
+size_t mm_pl_adapt_ws_bytes() {
+  return mm_align((size_t)PL_MAX_WG * 2 * (1 + MM_PRED_MAXC) * sizeof(double)) + mm_align((size_t)PL_MAX_WG * 2 * sizeof(long long));
+}
+
+int mm_pl_adapt(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, double momentum,
+                int warmup, double* state, int64_t* count, float* thr, void* ws, size_t ws_bytes, hipStream_t s) {
+  static_assert(2 * (1 + MM_PRED_MAXC) <= PT && 2 * (1 + MM_PRED_MAXC) <= PL_UT, "one thread per (output, quantity)");
+  MM_CHECK_ARG(C > 0 && C <= MM_PRED_MAXC, "pl_adapt: bad C");
+  MM_CHECK_ARG(N >= 0 && N <= (int64_t)PT * 0x7fffffff, "pl_adapt: bad N");
+  MM_CHECK_ARG(momentum >= 0.0 && momentum < 1.0, "pl_adapt: the momentum must lie in [0, 1)");
+  MM_CHECK_ARG(state && count && thr, "pl_adapt: null state, count or thr");
+  MM_CHECK_ARG(N == 0 || (logits2d && logits3d), "pl_adapt: null logits");
+  MM_CHECK_ARG(N == 0 || (ld2 >= C && ld3 >= C), "pl_adapt: row pitch below C");
+  MM_CHECK_ARG(ws && ws_bytes >= mm_pl_adapt_ws_bytes(), "pl_adapt: workspace missing or too small");
+  double* psum = (double*)ws;
+  long long* pcnt = (long long*)((char*)ws + mm_align((size_t)PL_MAX_WG * 2 * (1 + MM_PRED_MAXC) * sizeof(double)));
+  const int64_t nt = mm_cdiv(N, PT);
+  const int nb = (int)(nt > PL_MAX_WG ? PL_MAX_WG : nt);
+  if (nb > 0) {
+    const size_t lds = ((size_t)2 * PT * (C | 1) + 2 * PT) * sizeof(float);  // <= 34 KB
+    if (ensemble)
+      hipLaunchKernelGGL(k_pl_stats<true>, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, psum, pcnt);
+    else
+      hipLaunchKernelGGL(k_pl_stats<false>, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, psum, pcnt);
+    MM_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_pl_update, dim3(1), dim3(PL_UT), 0, s, (const double*)psum, (const long long*)pcnt, nb, C, momentum, warmup ? 1 : 0,
+                     state, count, thr);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -182,23 +182,26 @@ class _CrossEntropySoftPairFn(torch.autograd.Function):
         stats = torch.empty(4, dtype=F32, device=logits.device)
         kept = torch.empty((), dtype=torch.int64, device=logits.device)
         ws = _lib.workspace.get(int(L.mm_ce2s_ws_bytes()), logits.device)
-        check(L.mm_ce2s_fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
-                            temperature, thr, ptr(stats), ptr(kept), ptr(ws), ws.numel(), stream()), "ce2s_fwd")
-        ctx.save_for_backward(logits, labels0, weight0, ta, tb, stats)
-        ctx.args = (ld, ld_a, ld_b, split, temperature, thr, ignore_index)
+        cls = torch.is_tensor(thr)  # float32 [C] on the device: one threshold per class (mm_ce2s_*_cls)
+        fwd = L.mm_ce2s_fwd_cls if cls else L.mm_ce2s_fwd
+        check(fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                  temperature, ptr(thr) if cls else thr, ptr(stats), ptr(kept), ptr(ws), ws.numel(), stream()), "ce2s_fwd")
+        ctx.save_for_backward(logits, labels0, weight0, ta, tb, stats, thr if cls else None)
+        ctx.args = (ld, ld_a, ld_b, split, temperature, None if cls else thr, ignore_index)
         ctx.mark_non_differentiable(kept)
         return stats[0], stats[2], kept
 
     @staticmethod
     def backward(ctx, g0, g1, _):
         L = _lib.lib()
-        logits, labels0, weight0, ta, tb, stats = ctx.saved_tensors
+        logits, labels0, weight0, ta, tb, stats, thr_cls = ctx.saved_tensors
         ld, ld_a, ld_b, split, temperature, thr, ignore_index = ctx.args
         N, C = logits.shape
         g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
+        bwd = L.mm_ce2s_bwd if thr_cls is None else L.mm_ce2s_bwd_cls
         d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
-            L.mm_ce2s_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
-                          temperature, thr, ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd"))
+            bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                temperature, thr if thr_cls is None else ptr(thr_cls), ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd"))
         return d, None, None, None, None, None, None, None, None
 
 
@@ -212,7 +215,8 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
     ``teacher_other`` (same shape) the ensemble ``0.5 * (softmax(teacher / T) + softmax(teacher_other / T))``.  A row's confidence
     is the largest probability of that target at temperature 1 - the float32 value ``pselab.teacher_labels`` judges the row by,
     bit for bit - and with ``threshold`` in (0, 1] only rows whose confidence is ``>= threshold`` are kept; ``None`` keeps every
-    row whose teacher logits are finite.  ``loss_tail`` = mean over the kept rows of ``sum_c q_c * (logsumexp(x) - x_c)``, i.e.
+    row whose teacher logits are finite; a float32 device tensor ``[C]`` gives every class its own threshold, a row being judged
+    by that of its arg-max class (``pselab.AdaptiveThreshold``; the values are read on the device).  ``loss_tail`` = mean over the kept rows of ``sum_c q_c * (logsumexp(x) - x_c)``, i.e.
     KL(q || softmax(x)) plus the entropy of q; there is no ``T^2`` factor.  Nothing kept: loss 0 and a zero gradient.  ``kept``:
     the number of kept rows, an int64 device scalar.
 
@@ -228,8 +232,13 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
         raise ValueError(f"{who}: {C} classes, the row kernels take at most 32")
     if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0.0 < float(temperature) < float("inf"):
         raise ValueError(f"{who}: temperature must be a finite number > 0, not {temperature!r}")
-    if threshold is not None and (isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold <= 1.0):
-        raise ValueError(f"{who}: threshold must be None or a number in (0, 1], not {threshold!r}")
+    if torch.is_tensor(threshold):  # one threshold per class (pselab.AdaptiveThreshold's rows); the values stay on the device
+        if threshold.dtype != F32 or tuple(threshold.shape) != (C,) or threshold.device != pred.device:
+            raise ValueError(f"{who}: a threshold tensor must be float32 [{C}] on {pred.device}, not {threshold.dtype} "
+                             f"{tuple(threshold.shape)} on {threshold.device}")
+        threshold = threshold.detach().contiguous()
+    elif threshold is not None and (isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold <= 1.0):
+        raise ValueError(f"{who}: threshold must be None, a number in (0, 1] or a float32 device tensor [C], not {threshold!r}")
 
     def logits(t, which):
         if not torch.is_tensor(t) or tuple(t.shape) != (N - split, C):
@@ -245,7 +254,8 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
     gt_head = _labels(gt_head, split, pred.device, ignore_index, who, "gt_head")  # a labelled head without rows: 0/0
     weight_head = _class_weights(weight_head, C, pred.device, who, "weight_head")
     return _CrossEntropySoftPairFn.apply(pred, split, gt_head, weight_head, teacher, teacher_other, float(temperature),
-                                         0.0 if threshold is None else float(threshold), int(ignore_index))
+                                         threshold if torch.is_tensor(threshold) else 0.0 if threshold is None else float(threshold),
+                                         int(ignore_index))
 
 
 class _LovaszFn(torch.autograd.Function):

@@ -9,6 +9,9 @@ its class (uint8) of the 2D network, of the 3D network and of their average (tra
     teacher_labels(logits_2d, logits_3d)     the same per-point expression as int64 training labels of both heads, with an
                                              optional confidence threshold (mm_teacher_labels): what a mean teacher gives the
                                              target batch inside the training step (train.py pseudo_label_source="teacher")
+    AdaptiveThreshold(num_classes)           self-adaptive per-class thresholds for those labels (mm_pl_adapt): running state
+                                             on the device, ``update`` / ``labels`` per target batch
+                                             (train.py pl_threshold="adaptive")
     PseudoLabelWriter(path)                  collects scenes, ``close()`` writes the file
     export_pseudo_labels(trainer, dataset, path)   walks a dataset through ``TrainModel.predict_step`` into a writer
     refine_pseudo_labels(probs, labels)      lib/utils/refine_pseudo_labels.py on the GPU (mm_pselab_refine), exact: what the
@@ -95,6 +98,103 @@ def teacher_labels(logits_2d, logits_3d, ensemble=False, threshold=None, ignore_
     if with_probs:
         out["prob_2d"], out["prob_3d"] = probs[0], probs[1]
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- adaptive thresholds
+class AdaptiveThreshold:
+    """Self-adaptive per-class thresholds for a mean teacher's pseudo labels (FreeMatch, Wang et al., ICLR 2023; the definition
+    the kernels follow is in include/mm2d3d.h at mm_pl_adapt).  Per output (0: 2D, 1: 3D) a running confidence level ``tau`` and a
+    running class mass ``pt[c]``, both an exponential moving average over the target batches, give
+    ``thr[c] = (pt[c] / max(pt)) * tau``: classes the teacher rarely predicts get a lower bar, and the bar moves with the
+    teacher's confidence.  A row is kept iff its confidence is ``>= thr[its class]`` (float32, the project's ``>=``).
+
+    ``state``: fp64 ``[2, 1 + C]`` = (tau, pt) per output, all ``1 / C`` at the start; ``count``: int64 ``[2]``, the updates
+    taken.  Both live on the device and are updated there (two launches, no atomics, no host read: bit-stable run to run).  Rows
+    whose confidence is not ``>= 0`` (non-finite logits) are not counted; a batch without counted rows leaves an output's state
+    and count alone.  ``warmup``: momentum_t = min(momentum, (1 + t) / (10 + t)) over the updates t taken so far, the form of
+    ``ema_warmup``.  With momentum 0.999 and no warm-up the thresholds start near ``1 / C``, which no confidence is below: every
+    row is kept until the state has moved.
+
+    Every ``update`` / ``labels`` call counts: the trainer's update is not gated by the loss-scale skip or by the data-parallel
+    reducer's flag (the teacher's predictions are valid whether or not the student's step is taken).  Under data parallelism every
+    rank keeps its own state from its own target batches; it is not reduced (a known gap)."""
+
+    def __init__(self, num_classes, momentum=0.999, warmup=False, device="cuda"):
+        C = int(num_classes)
+        if not 1 <= C <= MAX_CLASSES:
+            raise ValueError(f"pselab.AdaptiveThreshold: {num_classes!r} classes, the row kernels take 1 to {MAX_CLASSES}")
+        if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum < 1.0:
+            raise ValueError(f"pselab.AdaptiveThreshold: momentum must be a number in [0, 1), not {momentum!r}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("pselab.AdaptiveThreshold keeps its state on a GPU")
+        self.num_classes, self.momentum, self.warmup = C, float(momentum), bool(warmup)
+        self.state = torch.empty((2, 1 + C), dtype=torch.float64, device=dev)
+        self.count = torch.empty(2, dtype=torch.int64, device=dev)
+        self.reset()
+
+    def reset(self):
+        """Back to the initial state: tau = pt[c] = 1 / C, no update taken."""
+        self.state.fill_(1.0 / self.num_classes)
+        self.count.zero_()
+
+    def state_dict(self):
+        return {"num_classes": self.num_classes, "state": self.state.clone(), "count": self.count.clone()}
+
+    def load_state_dict(self, sd):
+        if int(sd["num_classes"]) != self.num_classes or tuple(sd["state"].shape) != tuple(self.state.shape):
+            raise ValueError(f"pselab.AdaptiveThreshold: the state is of {int(sd['num_classes'])} classes, this object has {self.num_classes}")
+        self.state.copy_(sd["state"].to(torch.float64))
+        self.count.copy_(sd["count"].to(torch.int64))
+
+    def _pair(self, logits_2d, logits_3d, who):
+        a, b = _logits(logits_2d, "logits_2d", who), _logits(logits_3d, "logits_3d", who)
+        if b.shape != a.shape or b.device != a.device:
+            raise ValueError(f"pselab.{who}: logits_2d and logits_3d must have the same shape and device")
+        if a.shape[1] != self.num_classes or a.device != self.state.device:
+            raise ValueError(f"pselab.{who}: logits [N, {a.shape[1]}] on {a.device}, the state is of {self.num_classes} classes on "
+                             f"{self.state.device}")
+        return a, b
+
+    def _update(self, a, b, ensemble):
+        N, C = a.shape
+        thr = torch.empty((2, C), dtype=torch.float32, device=a.device)
+        pitch = lambda t: t.stride(0) if N > 1 else C
+        L = _lib.lib()
+        with torch.cuda.device(a.device):
+            ws = _lib.workspace.get(int(L.mm_pl_adapt_ws_bytes()), a.device, "pselab")
+            check(L.mm_pl_adapt(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)), self.momentum, int(self.warmup),
+                                ptr(self.state), ptr(self.count), ptr(thr), ptr(ws), ws.numel(), stream()), "pl_adapt")
+        return thr
+
+    @torch.no_grad()
+    def update(self, logits_2d, logits_3d, ensemble=False):
+        """Takes the batch into the state and returns this step's thresholds, a fresh float32 ``[2, C]`` device tensor (row 0 the
+        2D output's, row 1 the 3D output's): updated first, then to be applied to the same batch.  ``ensemble``: both outputs
+        follow the softmax average.  Row-pitched views are read in place."""
+        a, b = self._pair(logits_2d, logits_3d, "AdaptiveThreshold.update")
+        return self._update(a, b, ensemble)
+
+    @torch.no_grad()
+    def labels(self, logits_2d, logits_3d, ensemble=False, ignore_label=-100, with_probs=False):
+        """:meth:`update`, then the labels of :func:`teacher_labels` under the new thresholds (mm_teacher_labels_cls): its dict
+        plus ``"threshold"``, the ``[2, C]`` tensor the rows were judged by."""
+        a, b = self._pair(logits_2d, logits_3d, "AdaptiveThreshold.labels")
+        thr = self._update(a, b, ensemble)
+        N, C = a.shape
+        labels = torch.empty((2, N), dtype=torch.int64, device=a.device)
+        probs = torch.empty((2, N), dtype=torch.float32, device=a.device) if with_probs else None
+        kept = torch.zeros(2, dtype=torch.int64, device=a.device) if N == 0 else torch.empty(2, dtype=torch.int64, device=a.device)
+        pitch = lambda t: t.stride(0) if N > 1 else C
+        with torch.cuda.device(a.device):
+            check(_lib.lib().mm_teacher_labels_cls(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)), ptr(thr),
+                                                   int(ignore_label), ptr(labels[0]), ptr(labels[1]),
+                                                   ptr(probs[0]) if with_probs else None, ptr(probs[1]) if with_probs else None,
+                                                   ptr(kept), stream()), "teacher_labels_cls")
+        out = {"label_2d": labels[0], "label_3d": labels[1], "kept": kept, "threshold": thr}
+        if with_probs:
+            out["prob_2d"], out["prob_3d"] = probs[0], probs[1]
+        return out
 
 
 # ---------------------------------------------------------------------------------------------------- refinement

@@ -70,8 +70,28 @@ class TrainModel(nn.Module):
             raise ValueError(f"train_kwargs['pseudo_label_source'] must be 'batch' or 'teacher', not {self.pseudo_label_source!r}")
         self.pl_threshold = train_kwargs.get("pl_threshold")
         thr = self.pl_threshold
-        if not (thr is None or thr == "median" or (isinstance(thr, (int, float)) and not isinstance(thr, bool) and 0.0 < thr <= 1.0)):
-            raise ValueError(f"train_kwargs['pl_threshold'] must be None, 'median' or a number in (0, 1], not {thr!r}")
+        if not (thr is None or (isinstance(thr, str) and thr in ("median", "adaptive"))
+                or (isinstance(thr, (int, float)) and not isinstance(thr, bool) and 0.0 < thr <= 1.0)):
+            raise ValueError(f"train_kwargs['pl_threshold'] must be None, 'median', 'adaptive' or a number in (0, 1], not {thr!r}")
+        # "adaptive" (teacher source only; hard and soft targets, "own" and "ensemble"): FreeMatch's self-adaptive per-class
+        # thresholds (pselab.AdaptiveThreshold, mm_pl_adapt).  Per output a running confidence level tau and a running class mass
+        # pt[c] - EMAs with ``pl_threshold_momentum`` (default 0.999; ``pl_threshold_warmup``: min(momentum, (1 + t) / (10 + t)),
+        # as ``ema_warmup``) over the target batches - give thr[c] = pt[c] / max(pt) * tau; every target batch updates them
+        # first and is then judged by them, a row by the threshold of its own class.  The state lives on the device and no host
+        # read is added.  The update is NOT gated by the loss-scale skip or by the data-parallel reducer's flag: the teacher's
+        # predictions are valid whether or not the student's step is taken.  KNOWN GAP: under data parallelism the state is per
+        # rank (each rank sees its own target batches) and is not reduced.  ``pl_adaptive``: the object, built with the first
+        # teacher pass (the class count is known then), None without the option or with ``lambda_pl`` 0; ``last_teacher`` gains
+        # "threshold" (float32 [2, C], this step's), the logs ``train/pl_tau_2d`` / ``_3d``, the checkpoint "pl_adaptive".
+        if isinstance(thr, str) and thr == "adaptive" and self.pseudo_label_source != "teacher":
+            raise ValueError("train_kwargs['pl_threshold'] = 'adaptive' needs pseudo_label_source='teacher': the thresholds follow "
+                             "the teacher's predictions of every target batch")
+        m = train_kwargs.get("pl_threshold_momentum", 0.999)
+        if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0.0 <= m < 1.0:
+            raise ValueError(f"train_kwargs['pl_threshold_momentum'] must be a number in [0, 1), not {m!r}")
+        self.pl_threshold_momentum = float(m)
+        self.pl_threshold_warmup = bool(train_kwargs.get("pl_threshold_warmup", False))
+        self.pl_adaptive = None
         self.last_teacher = None
         # What the target rows learn from (consulted only with ``lambda_pl`` > 0).  "hard" (default): int64 pseudo labels, as above,
         # launch for launch the step without the option.  "soft": the teacher's DISTRIBUTION - each head's target rows take
@@ -307,8 +327,9 @@ class TrainModel(nn.Module):
     def _pl_pair(self, logits, split, gt_head, target, weight_head=None):
         """(loss of the head rows, pseudo-label loss of the target rows, kept rows or None) of one head's logits."""
         if self.pl_targets == "soft":
+            # pl_threshold="adaptive": the head's row of this step's thresholds travels with its targets (_teacher_labels)
             return cross_entropy_soft_pair(logits, split, gt_head, target[0], target[1], weight_head=weight_head,
-                                           temperature=self.pl_temperature, threshold=self.pl_threshold)
+                                           temperature=self.pl_temperature, threshold=target[2] if len(target) > 2 else self.pl_threshold)
         return (*cross_entropy_pair(logits, split, gt_head, target, weight_head=weight_head), None)
 
     @torch.no_grad()
@@ -319,7 +340,13 @@ class TrainModel(nn.Module):
         target's - in the joined step the [source | target] tensors, whose coordinate tensor carries the step's sparse metadata:
         nothing is built a second time and no host read is added.  Eval mode draws no dropout mask and updates no running
         statistic; every module's mode is put back as it was.  ``applied()`` marks the packed 16-bit weights stale twice
-        (conv2d.PARAM_EPOCH): the eager eval trunk repacks on first use, the student's graphs repack as their first node anyway."""
+        (conv2d.PARAM_EPOCH): the eager eval trunk repacks on first use, the student's graphs repack as their first node anyway.
+
+        ``pl_threshold="adaptive"``: the pass first takes the batch into ``pl_adaptive`` (pselab.AdaptiveThreshold, built here once
+        the class count is known), then labels under the new per-class thresholds (hard targets) or hands each head's loss call its
+        row of them (soft targets).  That update is NOT gated by the loss-scale skip or by the data-parallel reducer's flag - the
+        teacher's predictions are valid whether or not the student's step is taken - and under data parallelism the state is per
+        rank and is not reduced (a known gap)."""
         from . import gradsink, pselab
 
         if self.ema is None:
@@ -332,6 +359,19 @@ class TrainModel(nn.Module):
                 self.model.eval()
                 l2 = self(batch_2d, model_name=n2d)[0]["seg_logit"]
                 l3 = self(batch_3d, model_name=n3d)[0]["seg_logit"][first_row:]
+                ens, adaptive = self.pseudo_labels == "ensemble", self.pl_threshold == "adaptive"
+                if adaptive and self.pl_adaptive is None:  # the class count is known now
+                    self.pl_adaptive = pselab.AdaptiveThreshold(int(l2.shape[1]), self.pl_threshold_momentum, self.pl_threshold_warmup,
+                                                                device=l2.device)
+                if adaptive and self.pl_targets == "soft":
+                    # the state takes this batch in, then each head's loss call judges its rows by its row of the thresholds
+                    thr = self.pl_adaptive.update(l2, l3, ensemble=ens)
+                    self.last_teacher = {"logit_2d": l2, "logit_3d": l3, "kept": None, "threshold": thr}
+                    return [(*t, thr[o]) for o, t in enumerate(self._soft_targets(l2, l3))], None
+                if adaptive:  # hard targets: update, then the label launch under the per-class thresholds
+                    out = self.pl_adaptive.labels(l2, l3, ensemble=ens)
+                    self.last_teacher = {k: out[k] for k in ("label_2d", "label_3d", "kept", "threshold")}
+                    return [out["label_2d"], out["label_3d"]], out["kept"].to(torch.float32) / max(int(l2.shape[0]), 1)
                 if self.pl_targets == "soft":
                     # no label launch: the loss calls read the logits themselves.  They now outlive the student's forward and
                     # backward; both are tensors of their own (lifting's and the linear head's torch.empty outputs, l3 a row
@@ -496,6 +536,9 @@ class TrainModel(nn.Module):
                 self.last_teacher["kept"] = counts
         if kept is not None:
             self.last_logs[f"{stage}/pl_kept_2d"], self.last_logs[f"{stage}/pl_kept_3d"] = kept[0], kept[1]
+        if teacher and self.pl_adaptive is not None:  # this step's confidence levels, a copy: the state moves on with the next batch
+            tau = self.pl_adaptive.state[:, 0].to(torch.float32)
+            self.last_logs[f"{stage}/pl_tau_2d"], self.last_logs[f"{stage}/pl_tau_3d"] = tau[0], tau[1]
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
@@ -673,6 +716,8 @@ class TrainModel(nn.Module):
                 **({"ema": self.ema.state_dict(),
                     "ema_state_dict": {self._ckpt_key(k): v for k, v in self.ema.teacher_state_dict().items()}}
                    if self.ema is not None else {}),
+                # the self-adaptive pseudo-label thresholds (pl_threshold="adaptive"): the running state of both outputs
+                **({"pl_adaptive": self.pl_adaptive.state_dict()} if self.pl_adaptive is not None else {}),
                 # Lightning's key for the GradScaler of a ``precision: 16`` run
                 **({"native_amp_scaling_state": self.scaler.state_dict()} if self.scaler is not None else {})}
 
@@ -714,6 +759,18 @@ class TrainModel(nn.Module):
                 self.ema.load_state_dict(ckpt["ema"])
             else:
                 self.ema.reset()  # a checkpoint without a teacher: it starts from the loaded weights
+        if self.pl_threshold == "adaptive" and self.lambda_pl > 0:
+            sd = ckpt.get("pl_adaptive")
+            if sd is not None:
+                if self.pl_adaptive is None:  # a resume before the first teacher pass: the checkpoint knows the class count
+                    from . import pselab
+
+                    dev = next((p.device for p in self.model.parameters() if p.is_cuda), sd["state"].device)
+                    self.pl_adaptive = pselab.AdaptiveThreshold(sd["num_classes"], self.pl_threshold_momentum, self.pl_threshold_warmup,
+                                                                device=dev)
+                self.pl_adaptive.load_state_dict(sd)
+            elif self.pl_adaptive is not None:
+                self.pl_adaptive.reset()  # a checkpoint without the thresholds: they start over
         # the loss scale resumes where it was; the scaler itself is rebuilt by the next fit_step (its device step counters start
         # from the optimisers' restored step counts)
         self._scaler_state = ckpt.get("native_amp_scaling_state")

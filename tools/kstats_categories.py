@@ -17,7 +17,7 @@ CATS = [
     ("rocPRIM", r"rocprim"),
     ("2d misc (pool/heads/concat/pack/dropout)", r"k_maxpool|k_head|k_box5|k_concat|k_pack_weights|k_copy_rows|k_dropout|k_bnpool"),
     ("points / lifting / losses", r"k_gate|k_seg_mean|k_row_gather|k_linear|k_lift|k_ce_|k_kl_|k_segment|k_key|"
-                                  r"k_ce2s|k_lv_|k_teacher|k_pselab|k_refine"),
+                                  r"k_ce2s|k_lv_|k_teacher|k_pselab|k_refine|k_pl_"),
     ("optimiser / amp / packs", r"k_adamw|k_optim|k_amp|k_grad_nonfinite|k_os_pack|k_pack_frag"),
     ("torch (at::)", r"at::|at_cuda|elementwise_kernel|reduce_kernel|CatArray|index"),
     ("runtime fill/copy", r"__amd_rocclr"),
