@@ -8,10 +8,10 @@ its class (uint8) of the 2D network, of the 3D network and of their average (tra
     predict(logits_2d, logits_3d)            the six per-point tensors of one batch, one kernel (mm_pselab_predict)
     teacher_labels(logits_2d, logits_3d)     the same per-point expression as int64 training labels of both heads, with an
                                              optional confidence threshold (mm_teacher_labels): what a mean teacher gives the
-                                             target batch inside the training step (train.py pseudo_label_source="teacher")
+                                             target batch inside the training step (selftrain.py pseudo_label_source="teacher")
     AdaptiveThreshold(num_classes)           self-adaptive per-class thresholds for those labels (mm_pl_adapt): running state
                                              on the device, ``update`` / ``labels`` per target batch
-                                             (train.py pl_threshold="adaptive")
+                                             (selftrain.py pl_threshold="adaptive")
     PseudoLabelWriter(path)                  collects scenes, ``close()`` writes the file
     export_pseudo_labels(trainer, dataset, path)   walks a dataset through ``TrainModel.predict_step`` into a writer
     refine_pseudo_labels(probs, labels)      lib/utils/refine_pseudo_labels.py on the GPU (mm_pselab_refine), exact: what the
@@ -78,9 +78,16 @@ def teacher_labels(logits_2d, logits_3d, ensemble=False, threshold=None, ignore_
     """The int64 training labels a teacher's logits give both heads, in one launch (mm_teacher_labels): per row the expression
     of :func:`predict`, so ``label_2d`` / ``label_3d`` are ``pseudo_label_2d`` / ``pseudo_label_3d`` of an export, or with
     ``ensemble`` both ``pseudo_label_ensemble``.  ``threshold``: a label whose confidence is not ``>= threshold`` (float32)
-    becomes ``ignore_label``; ``None`` keeps all.  Returns ``dict(label_2d, label_3d, kept)``, ``kept`` an int64 ``[2]`` device
-    tensor with the labels kept per output; ``with_probs`` adds ``prob_2d`` / ``prob_3d``, the confidences the labels were
-    judged by.  Row-pitched views are read in place."""
+    becomes ``ignore_label``; ``None`` keeps all; a float32 ``[2, C]`` device tensor (row 0: 2D, row 1: 3D; read on the device) judges
+    a row by the threshold of its own class (mm_teacher_labels_cls, :class:`AdaptiveThreshold`).  Returns ``dict(label_2d, label_3d,
+    kept)``, ``kept`` an int64 ``[2]`` device tensor with the labels kept per output; ``with_probs`` adds ``prob_2d`` / ``prob_3d``,
+    the confidences the labels were judged by.  Row-pitched views are read in place."""
+    cls = torch.is_tensor(threshold)
+    if cls:  # checked from the arguments as they come, before anything else looks at them
+        if (threshold.dtype, tuple(threshold.shape), threshold.device) != (torch.float32, (2, logits_2d.shape[-1]), logits_2d.device):
+            raise ValueError(f"pselab.teacher_labels: a threshold tensor must be float32 [2, {logits_2d.shape[-1]}] on "
+                             f"{logits_2d.device}, not {threshold.dtype} {tuple(threshold.shape)} on {threshold.device}")
+        threshold = threshold.detach().contiguous()
     a, b = _logits(logits_2d, "logits_2d", "teacher_labels"), _logits(logits_3d, "logits_3d", "teacher_labels")
     if b.shape != a.shape or b.device != a.device:
         raise ValueError("pselab.teacher_labels: logits_2d and logits_3d must have the same shape and device")
@@ -90,14 +97,13 @@ def teacher_labels(logits_2d, logits_3d, ensemble=False, threshold=None, ignore_
     kept = torch.zeros(2, dtype=torch.int64, device=a.device) if N == 0 else torch.empty(2, dtype=torch.int64, device=a.device)
     pitch = lambda t: t.stride(0) if N > 1 else C
     with torch.cuda.device(a.device):
-        check(_lib.lib().mm_teacher_labels(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)),
-                                           -1.0 if threshold is None else float(threshold), int(ignore_label), ptr(labels[0]),
-                                           ptr(labels[1]), ptr(probs[0]) if with_probs else None, ptr(probs[1]) if with_probs else None,
-                                           ptr(kept), stream()), "teacher_labels")
+        fn = _lib.lib().mm_teacher_labels_cls if cls else _lib.lib().mm_teacher_labels
+        check(fn(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)),
+                 ptr(threshold) if cls else -1.0 if threshold is None else float(threshold), int(ignore_label), ptr(labels[0]),
+                 ptr(labels[1]), ptr(probs[0]) if with_probs else None, ptr(probs[1]) if with_probs else None, ptr(kept), stream()),
+              "teacher_labels_cls" if cls else "teacher_labels")
     out = {"label_2d": labels[0], "label_3d": labels[1], "kept": kept}
-    if with_probs:
-        out["prob_2d"], out["prob_3d"] = probs[0], probs[1]
-    return out
+    return dict(out, prob_2d=probs[0], prob_3d=probs[1]) if with_probs else out
 
 
 # ---------------------------------------------------------------------------------------------------- adaptive thresholds
@@ -147,16 +153,13 @@ class AdaptiveThreshold:
         self.state.copy_(sd["state"].to(torch.float64))
         self.count.copy_(sd["count"].to(torch.int64))
 
-    def _pair(self, logits_2d, logits_3d, who):
+    def _update(self, logits_2d, logits_3d, ensemble, who):
         a, b = _logits(logits_2d, "logits_2d", who), _logits(logits_3d, "logits_3d", who)
         if b.shape != a.shape or b.device != a.device:
             raise ValueError(f"pselab.{who}: logits_2d and logits_3d must have the same shape and device")
         if a.shape[1] != self.num_classes or a.device != self.state.device:
             raise ValueError(f"pselab.{who}: logits [N, {a.shape[1]}] on {a.device}, the state is of {self.num_classes} classes on "
                              f"{self.state.device}")
-        return a, b
-
-    def _update(self, a, b, ensemble):
         N, C = a.shape
         thr = torch.empty((2, C), dtype=torch.float32, device=a.device)
         pitch = lambda t: t.stride(0) if N > 1 else C
@@ -165,36 +168,21 @@ class AdaptiveThreshold:
             ws = _lib.workspace.get(int(L.mm_pl_adapt_ws_bytes()), a.device, "pselab")
             check(L.mm_pl_adapt(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)), self.momentum, int(self.warmup),
                                 ptr(self.state), ptr(self.count), ptr(thr), ptr(ws), ws.numel(), stream()), "pl_adapt")
-        return thr
+        return a, b, thr
 
     @torch.no_grad()
     def update(self, logits_2d, logits_3d, ensemble=False):
         """Takes the batch into the state and returns this step's thresholds, a fresh float32 ``[2, C]`` device tensor (row 0 the
         2D output's, row 1 the 3D output's): updated first, then to be applied to the same batch.  ``ensemble``: both outputs
         follow the softmax average.  Row-pitched views are read in place."""
-        a, b = self._pair(logits_2d, logits_3d, "AdaptiveThreshold.update")
-        return self._update(a, b, ensemble)
+        return self._update(logits_2d, logits_3d, ensemble, "AdaptiveThreshold.update")[2]
 
     @torch.no_grad()
     def labels(self, logits_2d, logits_3d, ensemble=False, ignore_label=-100, with_probs=False):
         """:meth:`update`, then the labels of :func:`teacher_labels` under the new thresholds (mm_teacher_labels_cls): its dict
         plus ``"threshold"``, the ``[2, C]`` tensor the rows were judged by."""
-        a, b = self._pair(logits_2d, logits_3d, "AdaptiveThreshold.labels")
-        thr = self._update(a, b, ensemble)
-        N, C = a.shape
-        labels = torch.empty((2, N), dtype=torch.int64, device=a.device)
-        probs = torch.empty((2, N), dtype=torch.float32, device=a.device) if with_probs else None
-        kept = torch.zeros(2, dtype=torch.int64, device=a.device) if N == 0 else torch.empty(2, dtype=torch.int64, device=a.device)
-        pitch = lambda t: t.stride(0) if N > 1 else C
-        with torch.cuda.device(a.device):
-            check(_lib.lib().mm_teacher_labels_cls(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)), ptr(thr),
-                                                   int(ignore_label), ptr(labels[0]), ptr(labels[1]),
-                                                   ptr(probs[0]) if with_probs else None, ptr(probs[1]) if with_probs else None,
-                                                   ptr(kept), stream()), "teacher_labels_cls")
-        out = {"label_2d": labels[0], "label_3d": labels[1], "kept": kept, "threshold": thr}
-        if with_probs:
-            out["prob_2d"], out["prob_3d"] = probs[0], probs[1]
-        return out
+        a, b, thr = self._update(logits_2d, logits_3d, ensemble, "AdaptiveThreshold.labels")
+        return dict(teacher_labels(a, b, ensemble, thr, ignore_label, with_probs), threshold=thr)
 
 
 # ---------------------------------------------------------------------------------------------------- refinement

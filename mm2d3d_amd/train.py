@@ -14,8 +14,9 @@ import torch.nn as nn
 
 from . import _lib, domains
 from .ddp import GradAllReducer, ranks_share_a_gpu
-from .losses import CrossEntropy, Loss, cross_entropy_pair, cross_entropy_soft_pair, cross_modal_loss
+from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
+from .selftrain import FORWARDED, SelfTraining
 
 
 class TrainModel(nn.Module):
@@ -29,20 +30,6 @@ class TrainModel(nn.Module):
         self.loss = loss
         self.lambda_xm_src = train_kwargs.get("lambda_xm_src", 1.0)
         self.lambda_xm_trg = train_kwargs.get("lambda_xm_trg", 0.1)
-        # Self-training (the second round: pselab.export_pseudo_labels -> the loaders' ``pselab_paths=`` -> here): with
-        # ``lambda_pl`` > 0 each main head also learns from the pseudo labels of the TARGET batch, loss_2d += lambda_pl * pl2d and
-        # loss_3d += lambda_pl * pl3d, logged as ``{stage}/pl_loss_tgt_2d`` / ``_3d``.  pl* = unweighted cross entropy of the head's
-        # target rows, ignore_index -100 (a refined-away point), mean over the counted rows.  The class weights are left out on
-        # purpose: they describe the SOURCE label distribution.  A target batch whose pseudo labels are all -100 contributes loss 0
-        # and a zero gradient (losses.cross_entropy_pair), not torch's 0/0.  ``pseudo_labels``: "own" = the 2D head learns from
-        # ``pseudo_label_2d`` and the 3D head from ``pseudo_label_3d``; "ensemble" = both from ``pseudo_label_ensemble``.
-        # 0.0 (default): the step is exactly the step without the option - pseudo-label keys of the batch are ignored.
-        self.lambda_pl = float(train_kwargs.get("lambda_pl", 0.0))
-        if not self.lambda_pl >= 0.0:
-            raise ValueError(f"train_kwargs['lambda_pl'] must be >= 0, not {train_kwargs['lambda_pl']!r}")
-        self.pseudo_labels = train_kwargs.get("pseudo_labels", "own")
-        if self.pseudo_labels not in ("own", "ensemble"):
-            raise ValueError(f"train_kwargs['pseudo_labels'] must be 'own' or 'ensemble', not {self.pseudo_labels!r}")
         # Mean-teacher weights (mm2d3d_amd/ema.py): with ``ema_decay`` set, an exponential moving average of every arena of the
         # optimisers and every floating-point buffer follows the step in one launch, gated on the device by the decision the
         # optimiser update was gated by (a skipped step is neither averaged in nor counted).  ``ema_warmup``: decay_t =
@@ -56,64 +43,6 @@ class TrainModel(nn.Module):
         self.ema_warmup = bool(train_kwargs.get("ema_warmup", False))
         self.ema_eval = bool(train_kwargs.get("ema_eval", False))
         self.ema = None
-        # Where the pseudo labels come from (consulted only with ``lambda_pl`` > 0).  "batch" (default): the batch's
-        # ``pseudo_label_*`` keys, as above.  "teacher": the mean teacher labels the target batch inside the step - before the
-        # student's forward the model computes the target rows in eval mode with the teacher's weights (``ema.applied()``, no_grad)
-        # and ONE launch turns the two logit matrices into the int64 labels of both heads (pselab.teacher_labels; "own" / "ensemble"
-        # as above); after the step the teacher follows the student as always.  ``pseudo_label_*`` keys of the batch are ignored.
-        # ``pl_threshold`` (teacher source only): None keeps every label, a float in (0, 1] refuses labels whose confidence is
-        # below it, "median" applies the loaders' refinement rule over this batch's target rows (per class min(lower median, 0.9),
-        # mm_pselab_refine per output).  What was used: ``last_teacher`` = dict(label_2d, label_3d, kept) and the logged
-        # ``train/pl_kept_2d`` / ``_3d`` (kept share of the target rows), all device tensors.
-        self.pseudo_label_source = train_kwargs.get("pseudo_label_source", "batch")
-        if self.pseudo_label_source not in ("batch", "teacher"):
-            raise ValueError(f"train_kwargs['pseudo_label_source'] must be 'batch' or 'teacher', not {self.pseudo_label_source!r}")
-        self.pl_threshold = train_kwargs.get("pl_threshold")
-        thr = self.pl_threshold
-        if not (thr is None or (isinstance(thr, str) and thr in ("median", "adaptive"))
-                or (isinstance(thr, (int, float)) and not isinstance(thr, bool) and 0.0 < thr <= 1.0)):
-            raise ValueError(f"train_kwargs['pl_threshold'] must be None, 'median', 'adaptive' or a number in (0, 1], not {thr!r}")
-        # "adaptive" (teacher source only; hard and soft targets, "own" and "ensemble"): FreeMatch's self-adaptive per-class
-        # thresholds (pselab.AdaptiveThreshold, mm_pl_adapt).  Per output a running confidence level tau and a running class mass
-        # pt[c] - EMAs with ``pl_threshold_momentum`` (default 0.999; ``pl_threshold_warmup``: min(momentum, (1 + t) / (10 + t)),
-        # as ``ema_warmup``) over the target batches - give thr[c] = pt[c] / max(pt) * tau; every target batch updates them
-        # first and is then judged by them, a row by the threshold of its own class.  The state lives on the device and no host
-        # read is added.  The update is NOT gated by the loss-scale skip or by the data-parallel reducer's flag: the teacher's
-        # predictions are valid whether or not the student's step is taken.  KNOWN GAP: under data parallelism the state is per
-        # rank (each rank sees its own target batches) and is not reduced.  ``pl_adaptive``: the object, built with the first
-        # teacher pass (the class count is known then), None without the option or with ``lambda_pl`` 0; ``last_teacher`` gains
-        # "threshold" (float32 [2, C], this step's), the logs ``train/pl_tau_2d`` / ``_3d``, the checkpoint "pl_adaptive".
-        if isinstance(thr, str) and thr == "adaptive" and self.pseudo_label_source != "teacher":
-            raise ValueError("train_kwargs['pl_threshold'] = 'adaptive' needs pseudo_label_source='teacher': the thresholds follow "
-                             "the teacher's predictions of every target batch")
-        m = train_kwargs.get("pl_threshold_momentum", 0.999)
-        if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0.0 <= m < 1.0:
-            raise ValueError(f"train_kwargs['pl_threshold_momentum'] must be a number in [0, 1), not {m!r}")
-        self.pl_threshold_momentum = float(m)
-        self.pl_threshold_warmup = bool(train_kwargs.get("pl_threshold_warmup", False))
-        self.pl_adaptive = None
-        self.last_teacher = None
-        # What the target rows learn from (consulted only with ``lambda_pl`` > 0).  "hard" (default): int64 pseudo labels, as above,
-        # launch for launch the step without the option.  "soft": the teacher's DISTRIBUTION - each head's target rows take
-        # losses.cross_entropy_soft_pair against softmax(teacher logits / ``pl_temperature``) ("own": the 2D head the teacher's 2D
-        # logits, the 3D head its 3D logits; "ensemble": both heads the average of the two softmaxes), rows kept by their
-        # confidence at temperature 1 against ``pl_threshold`` (None or a float; "median" works on labels and is refused), mean
-        # over the kept rows, no T^2 factor.  Source "teacher": the teacher pass runs as above without the label launch, and
-        # ``last_teacher`` = dict(logit_2d, logit_3d, kept); source "batch": the target batch carries ``teacher_logit_2d`` /
-        # ``teacher_logit_3d`` [n, C] (a frozen teacher of the caller's own).  Both log ``train/pl_kept_2d`` / ``_3d``.
-        self.pl_targets = train_kwargs.get("pl_targets", "hard")
-        if self.pl_targets not in ("hard", "soft"):
-            raise ValueError(f"train_kwargs['pl_targets'] must be 'hard' or 'soft', not {self.pl_targets!r}")
-        T = train_kwargs.get("pl_temperature", 1.0)
-        if isinstance(T, bool) or not isinstance(T, (int, float)) or not 0.0 < T < float("inf"):
-            raise ValueError(f"train_kwargs['pl_temperature'] must be a finite number > 0, not {T!r}")
-        self.pl_temperature = float(T)
-        if self.pl_targets == "hard" and self.pl_temperature != 1.0:
-            raise ValueError(f"train_kwargs['pl_temperature'] = {T!r} with pl_targets='hard': an arg-max has no temperature "
-                             "(it would be silently meaningless); use pl_targets='soft'")
-        if self.pl_targets == "soft" and thr == "median":
-            raise ValueError("train_kwargs['pl_threshold'] = 'median' is refused with pl_targets='soft': the refinement works on "
-                             "labels; give a number in (0, 1] or None")
         self.broadcast_buffers = bool(int(train_kwargs.get("broadcast_buffers", os.environ.get("MM_DDP_BROADCAST_BUFFERS", "1"))))  # torch DDP default (run.py:264-268)
         # One pass per network over [source scenes | target scenes] instead of one per domain: half the launches, twice
         # the rows per launch.  The batch-norm layers keep per-domain statistics (mm2d3d_amd/domains.py), so the
@@ -187,14 +116,8 @@ class TrainModel(nn.Module):
         # keeps refilling them; what exactly keeps them from ever draining at that size was not found.
         # Never under data parallelism.
         self.overlap_branches = int(train_kwargs.get("overlap_branches", os.environ.get("MM_OVERLAP_BRANCHES", "0")))
-        if self.pseudo_label_source == "teacher":
-            # checked whatever lambda_pl is: a schedule that starts at 0 must not hide a configuration that cannot run later
-            why = ("ema_decay is None (the teacher is the EMA of the weights)" if self.ema_decay is None else
-                   "overlap_metadata is on" if self.overlap_metadata else
-                   f"overlap_branches is {self.overlap_branches}" if self.overlap_branches != 0 else None)
-            if why is not None:
-                raise ValueError(f"train_kwargs['pseudo_label_source'] = 'teacher' is refused: {why}; the teacher pass runs on the "
-                                 "step's one stream (the side-stream modes are experimental and not extended to it)")
+        # self-training (``lambda_pl``, ``pseudo_label*``, ``pl_*``): selftrain.SelfTraining owns options and state; forwarded below the class
+        self.selftrain = SelfTraining(train_kwargs, self.ema_decay, self.overlap_metadata, self.overlap_branches)
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -284,116 +207,6 @@ class TrainModel(nn.Module):
         return (self.joint_domains and self.training and src["img"].is_cuda and src["img"].shape[1:] == trg["img"].shape[1:]
                 and src["depth"].shape[1:] == trg["depth"].shape[1:])
 
-    def _pseudo_labels(self, trg):
-        """(labels for the 2D head, labels for the 3D head) of a target batch, checked on the host before anything is queued."""
-        keys = ("pseudo_label_ensemble",) * 2 if self.pseudo_labels == "ensemble" else ("pseudo_label_2d", "pseudo_label_3d")
-        n = int(trg["x"][0].shape[0])
-        out = []
-        for k in keys:
-            if k not in trg:
-                raise KeyError(f"lambda_pl > 0 but the target batch has no '{k}': build the target dataset with pselab_paths= "
-                               "(the file pselab.export_pseudo_labels writes)")
-            v = trg[k]
-            if k == "pseudo_label_3d" and isinstance(v, (list, tuple)) and len(v) == 0:
-                raise ValueError(f"the pseudo-label file has no 3D entries ('{k}' is empty): train with pseudo_labels=\"ensemble\"")
-            if not torch.is_tensor(v) or v.dim() != 1 or int(v.shape[0]) != n:
-                raise ValueError(f"'{k}' holds {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__} labels, the target batch "
-                                 f"has {n} point rows")
-            out.append(v)
-        return out
-
-    def _teacher_logits(self, trg):
-        """``pl_targets="soft"`` with the batch source: (teacher logits for the 2D head, for the 3D head) of a target batch, checked
-        on the host before anything is queued."""
-        n = int(trg["x"][0].shape[0])
-        out = []
-        for k in ("teacher_logit_2d", "teacher_logit_3d"):
-            if k not in trg:
-                raise KeyError(f"lambda_pl > 0 with pl_targets='soft' but the target batch has no '{k}': give the teacher's logits "
-                               "[n, C] of the target rows, or train with pseudo_label_source='teacher'")
-            v = trg[k]
-            if not torch.is_tensor(v) or v.dim() != 2 or int(v.shape[0]) != n or not v.is_floating_point():
-                raise ValueError(f"'{k}' holds {(tuple(v.shape), v.dtype) if torch.is_tensor(v) else type(v).__name__}, the target "
-                                 f"batch has {n} point rows: float logits [{n}, C] are expected")
-            out.append(v)
-        if out[0].shape != out[1].shape:
-            raise ValueError(f"'teacher_logit_2d' is {tuple(out[0].shape)} and 'teacher_logit_3d' is {tuple(out[1].shape)}")
-        return out
-
-    def _soft_targets(self, l2, l3):
-        """Per head (teacher, teacher_other) of losses.cross_entropy_soft_pair: "own" = the head's own modality, "ensemble" = both."""
-        return [(l2, l3), (l2, l3)] if self.pseudo_labels == "ensemble" else [(l2, None), (l3, None)]
-
-    def _pl_pair(self, logits, split, gt_head, target, weight_head=None):
-        """(loss of the head rows, pseudo-label loss of the target rows, kept rows or None) of one head's logits."""
-        if self.pl_targets == "soft":
-            # pl_threshold="adaptive": the head's row of this step's thresholds travels with its targets (_teacher_labels)
-            return cross_entropy_soft_pair(logits, split, gt_head, target[0], target[1], weight_head=weight_head,
-                                           temperature=self.pl_temperature, threshold=target[2] if len(target) > 2 else self.pl_threshold)
-        return (*cross_entropy_pair(logits, split, gt_head, target, weight_head=weight_head), None)
-
-    @torch.no_grad()
-    def _teacher_labels(self, batch_2d, batch_3d, first_row=0):
-        """``pseudo_label_source="teacher"``: ([labels for the 2D head, labels for the 3D head], kept share [2]) of the target rows,
-        computed by the teacher before the student's forward is queued.  ``batch_2d``: the target images; ``batch_3d``: a dict the
-        3D net may write to (Net3DSeg.forward replaces ``x[1]`` by the gated features) whose point rows ``[first_row:]`` are the
-        target's - in the joined step the [source | target] tensors, whose coordinate tensor carries the step's sparse metadata:
-        nothing is built a second time and no host read is added.  Eval mode draws no dropout mask and updates no running
-        statistic; every module's mode is put back as it was.  ``applied()`` marks the packed 16-bit weights stale twice
-        (conv2d.PARAM_EPOCH): the eager eval trunk repacks on first use, the student's graphs repack as their first node anyway.
-
-        ``pl_threshold="adaptive"``: the pass first takes the batch into ``pl_adaptive`` (pselab.AdaptiveThreshold, built here once
-        the class count is known), then labels under the new per-class thresholds (hard targets) or hands each head's loss call its
-        row of them (soft targets).  That update is NOT gated by the loss-scale skip or by the data-parallel reducer's flag - the
-        teacher's predictions are valid whether or not the student's step is taken - and under data parallelism the state is per
-        rank and is not reduced (a known gap)."""
-        from . import gradsink, pselab
-
-        if self.ema is None:
-            raise RuntimeError("pseudo_label_source='teacher': the teacher is built with the optimisers (fit_step does it; before a "
-                               "bare training_step call configure_optimizers() first)")
-        n2d, n3d = self.modules_name[0], self.modules_name[1]
-        modes = [(m, m.training) for m in self.model.modules()]
-        try:
-            with self.ema.applied(), gradsink.suspended():  # no backward follows this forward: it claims no gradient sink
-                self.model.eval()
-                l2 = self(batch_2d, model_name=n2d)[0]["seg_logit"]
-                l3 = self(batch_3d, model_name=n3d)[0]["seg_logit"][first_row:]
-                ens, adaptive = self.pseudo_labels == "ensemble", self.pl_threshold == "adaptive"
-                if adaptive and self.pl_adaptive is None:  # the class count is known now
-                    self.pl_adaptive = pselab.AdaptiveThreshold(int(l2.shape[1]), self.pl_threshold_momentum, self.pl_threshold_warmup,
-                                                                device=l2.device)
-                if adaptive and self.pl_targets == "soft":
-                    # the state takes this batch in, then each head's loss call judges its rows by its row of the thresholds
-                    thr = self.pl_adaptive.update(l2, l3, ensemble=ens)
-                    self.last_teacher = {"logit_2d": l2, "logit_3d": l3, "kept": None, "threshold": thr}
-                    return [(*t, thr[o]) for o, t in enumerate(self._soft_targets(l2, l3))], None
-                if adaptive:  # hard targets: update, then the label launch under the per-class thresholds
-                    out = self.pl_adaptive.labels(l2, l3, ensemble=ens)
-                    self.last_teacher = {k: out[k] for k in ("label_2d", "label_3d", "kept", "threshold")}
-                    return [out["label_2d"], out["label_3d"]], out["kept"].to(torch.float32) / max(int(l2.shape[0]), 1)
-                if self.pl_targets == "soft":
-                    # no label launch: the loss calls read the logits themselves.  They now outlive the student's forward and
-                    # backward; both are tensors of their own (lifting's and the linear head's torch.empty outputs, l3 a row
-                    # slice of one) - neither a workspace nor a static graph buffer (eval forwards are eager): no copy is needed
-                    self.last_teacher = {"logit_2d": l2, "logit_3d": l3, "kept": None}  # "kept": filled by the loss calls
-                    return self._soft_targets(l2, l3), None
-                ens, median = self.pseudo_labels == "ensemble", self.pl_threshold == "median"
-                # "median": threshold 0 refuses exactly the rows without a confidence (non-finite logits give NaN, or the
-                # ensemble's -1): mm_pselab_refine wants finite probabilities, and passes -100 through without reading them
-                out = pselab.teacher_labels(l2, l3, ensemble=ens, threshold=0.0 if median else self.pl_threshold, with_probs=median)
-                y2, y3, kept = out["label_2d"], out["label_3d"], out["kept"]
-                if median:  # the loaders' refinement over this batch: an exact radix select per output (mm_pselab_refine)
-                    C = int(l2.shape[1])
-                    y2 = pselab.refine_pseudo_labels(out["prob_2d"], y2, num_classes=C, device=l2.device)
-                    y3 = y2 if ens else pselab.refine_pseudo_labels(out["prob_3d"], y3, num_classes=C, device=l2.device)
-                    kept = torch.stack([(y2 != -100).sum(), (y3 != -100).sum()])
-        finally:
-            for m, was in modes:
-                m.training = was
-        self.last_teacher = {"label_2d": y2, "label_3d": y3, "kept": kept}
-        return [y2, y3], kept.to(torch.float32) / max(int(l2.shape[0]), 1)
-
     def _single_cross_entropy(self):
         """(registry weight, class weights) if the "segmentation" target of the loss registry is one ``cross_entropy`` entry."""
         sel = [(w, l) for w, t, l in self.loss._losses if t == "segmentation"]
@@ -404,12 +217,9 @@ class TrainModel(nn.Module):
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
-        teacher = self.lambda_pl > 0 and self.pseudo_label_source == "teacher"
-        soft = self.pl_targets == "soft"
-        pseudo = None
-        if self.lambda_pl > 0 and not teacher:
-            pseudo = self._soft_targets(*self._teacher_logits(trg)) if soft else self._pseudo_labels(trg)
-        kept = None
+        st = self.selftrain
+        teacher = st.lambda_pl > 0 and st.pseudo_label_source == "teacher"
+        pseudo = st.batch_targets(trg) if st.lambda_pl > 0 and not teacher else None
         if self._can_join(src, trg):
             pre = self._pipelined if self._pipelined is not None and self._matches(self._pipelined, batch) else None
             self._pipelined = None
@@ -425,7 +235,7 @@ class TrainModel(nn.Module):
                 if prep is not None and getattr(both["x"][0], "_mm_metadata", None) is None:
                     with domains.split(B):
                         prep(both)
-                pseudo, kept = self._teacher_labels({k: trg[k] for k in ("img", "depth", "img_indices")}, {"x": list(both["x"])}, P)
+                pseudo = st.teacher_targets(self, {k: trg[k] for k in ("img", "depth", "img_indices")}, {"x": list(both["x"])}, P)
             with domains.split(B):
                 dev = both["img"].device
                 step_start = torch.cuda.current_stream(dev).record_event()
@@ -490,21 +300,19 @@ class TrainModel(nn.Module):
                 # one pass over each head's [source | target] logits: source labels with the entry's class weights, pseudo labels
                 # without; one backward launch writes the head's whole gradient
                 (rw, cw), gt = single, src["seg_label"]
-                seg2d, pl2d, k2 = self._pl_pair(l2d, P, gt, pseudo[0], cw)
-                seg3d, pl3d, k3 = self._pl_pair(l3d, P, gt, pseudo[1], cw)
+                seg2d, seg3d, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo, gt, cw)
                 seg2d, seg3d = rw * seg2d, rw * seg3d
             else:
                 seg2d = self.loss("segmentation", pred=l2d[:P], gt=src["seg_label"])
                 seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
                 if pseudo is not None:
-                    _, pl2d, k2 = self._pl_pair(l2d, P, None, pseudo[0])
-                    _, pl3d, k3 = self._pl_pair(l3d, P, None, pseudo[1])
+                    _, _, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo)
             xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
         else:
             if teacher:
                 own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
-                pseudo, kept = self._teacher_labels(own, own)
+                pseudo = st.teacher_targets(self, own, own)
             p2d, _, _, aux2d = self(src, model_name=n2d)
             p3d, _, aux3d = self(src, model_name=n3d)
             seg2d = self.loss("segmentation", pred=p2d["seg_logit"], gt=src["seg_label"])
@@ -516,8 +324,7 @@ class TrainModel(nn.Module):
             xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
                                                aux3d["seg_logit_point"])
             if pseudo is not None:
-                _, pl2d, k2 = self._pl_pair(p2d["seg_logit"], 0, None, pseudo[0])
-                _, pl3d, k3 = self._pl_pair(p3d["seg_logit"], 0, None, pseudo[1])
+                _, _, pl2d, pl3d = st.losses(p2d["seg_logit"], p3d["seg_logit"], 0, pseudo)
         self.last_logs = {
             f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
@@ -526,19 +333,9 @@ class TrainModel(nn.Module):
         loss_2d = seg2d + self.lambda_xm_src * xs2d + self.lambda_xm_trg * xt2d
         loss_3d = seg3d + self.lambda_xm_src * xs3d + self.lambda_xm_trg * xt3d
         if pseudo is not None:
-            self.last_logs[f"{stage}/pl_loss_tgt_2d"], self.last_logs[f"{stage}/pl_loss_tgt_3d"] = pl2d, pl3d
-            loss_2d = loss_2d + self.lambda_pl * pl2d
-            loss_3d = loss_3d + self.lambda_pl * pl3d
-        if pseudo is not None and soft:  # the rows the two loss calls kept: counted in their forward launches
-            counts = torch.stack((k2, k3))
-            kept = counts.to(torch.float32) / max(int(trg["x"][0].shape[0]), 1)
-            if teacher:
-                self.last_teacher["kept"] = counts
-        if kept is not None:
-            self.last_logs[f"{stage}/pl_kept_2d"], self.last_logs[f"{stage}/pl_kept_3d"] = kept[0], kept[1]
-        if teacher and self.pl_adaptive is not None:  # this step's confidence levels, a copy: the state moves on with the next batch
-            tau = self.pl_adaptive.state[:, 0].to(torch.float32)
-            self.last_logs[f"{stage}/pl_tau_2d"], self.last_logs[f"{stage}/pl_tau_3d"] = tau[0], tau[1]
+            loss_2d = loss_2d + st.lambda_pl * pl2d
+            loss_3d = loss_3d + st.lambda_pl * pl3d
+            st.log(self.last_logs, stage, pl2d, pl3d, trg["x"][0].shape[0])
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
@@ -716,8 +513,7 @@ class TrainModel(nn.Module):
                 **({"ema": self.ema.state_dict(),
                     "ema_state_dict": {self._ckpt_key(k): v for k, v in self.ema.teacher_state_dict().items()}}
                    if self.ema is not None else {}),
-                # the self-adaptive pseudo-label thresholds (pl_threshold="adaptive"): the running state of both outputs
-                **({"pl_adaptive": self.pl_adaptive.state_dict()} if self.pl_adaptive is not None else {}),
+                **self.selftrain.state_dict(),  # "pl_adaptive": the self-adaptive pseudo-label thresholds, once built
                 # Lightning's key for the GradScaler of a ``precision: 16`` run
                 **({"native_amp_scaling_state": self.scaler.state_dict()} if self.scaler is not None else {})}
 
@@ -759,18 +555,7 @@ class TrainModel(nn.Module):
                 self.ema.load_state_dict(ckpt["ema"])
             else:
                 self.ema.reset()  # a checkpoint without a teacher: it starts from the loaded weights
-        if self.pl_threshold == "adaptive" and self.lambda_pl > 0:
-            sd = ckpt.get("pl_adaptive")
-            if sd is not None:
-                if self.pl_adaptive is None:  # a resume before the first teacher pass: the checkpoint knows the class count
-                    from . import pselab
-
-                    dev = next((p.device for p in self.model.parameters() if p.is_cuda), sd["state"].device)
-                    self.pl_adaptive = pselab.AdaptiveThreshold(sd["num_classes"], self.pl_threshold_momentum, self.pl_threshold_warmup,
-                                                                device=dev)
-                self.pl_adaptive.load_state_dict(sd)
-            elif self.pl_adaptive is not None:
-                self.pl_adaptive.reset()  # a checkpoint without the thresholds: they start over
+        self.selftrain.load_state_dict(ckpt, next((p.device for p in self.model.parameters() if p.is_cuda), None))
         # the loss scale resumes where it was; the scaler itself is rebuilt by the next fit_step (its device step counters start
         # from the optimisers' restored step counts)
         self._scaler_state = ckpt.get("native_amp_scaling_state")
@@ -868,3 +653,8 @@ class TrainModel(nn.Module):
                 s.step()
         self.global_step += 1
         return loss
+
+
+for _name in FORWARDED:  # trainer.lambda_pl, ..., trainer.last_teacher: read and assigned on the policy object
+    setattr(TrainModel, _name, property(lambda self, n=_name: getattr(self.selftrain, n),
+                                        lambda self, value, n=_name: setattr(self.selftrain, n, value)))

@@ -1,6 +1,6 @@
 """Self-adaptive per-class pseudo-label thresholds in the training step: train_kwargs["pl_threshold"] = "adaptive" with
 ["pl_threshold_momentum"] / ["pl_threshold_warmup"] (mm2d3d_amd/train.py, pselab.AdaptiveThreshold).  Shapes and helpers of
-tests/test_gpu_teacher_step.py: 1 + 1 synthetic nuScenes scenes with 48x64 images, 6 classes, fp16, dropout p = 0, ema_decay 0.9;
+tests/_step_util.py: 1 + 1 synthetic nuScenes scenes with 48x64 images, 6 classes, fp16, dropout p = 0, ema_decay 0.9;
 heads scaled by 4 as in tests/test_gpu_soft_step.py (confidences spread out), and a small momentum so that the thresholds bite
 from the first step.
 
@@ -12,54 +12,15 @@ import copy
 import pytest
 import torch
 
-import test_gpu_teacher_step as T
+import _step_util as T
+from _step_util import _BUILT, _release_memory, _restore_precision  # noqa: F401  (the autouse fixtures, for this module too)
 
 pytestmark = pytest.mark.gpu
 
 STEPS = 3
+PL_KEYS = ("train/pl_loss_tgt_2d", "train/pl_loss_tgt_3d")
+KEPT_KEYS = ("train/pl_kept_2d", "train/pl_kept_3d")
 TAU_KEYS = ("train/pl_tau_2d", "train/pl_tau_3d")
-_restore_precision = T._restore_precision  # the autouse fixture of the helpers' module, for this one too
-
-
-_BUILT = []  # the trainers of the running test
-
-
-def _dispose(tm):
-    """Lets a finished trainer's device memory go.  A flat optimiser's post-accumulate hooks close over its arena, whose ``params``
-    list holds the parameters the hooks hang on: a cycle through the tensors that the collector does not take apart, so a trainer
-    that is merely dropped keeps about 1 GiB of arenas for the life of the process (measured: 1.02 GiB per trainer dropped, 0.08
-    after this).  Emptying the arenas and the hook tables breaks it."""
-    for opt in tm.optimizers:
-        for a in opt._arenas:
-            if a is not None:
-                a.clear()
-    for q in tm.model.parameters():
-        hooks = getattr(q, "_post_accumulate_grad_hooks", None)
-        if hooks is not None:
-            hooks.clear()
-        q.__dict__.pop("_mm_hooks", None)
-
-
-@pytest.fixture(autouse=True)
-def _release_memory():
-    """The suite runs in one process, which the step tests of the other files fill close to the device's capacity, so this file
-    hands back what it takes.  Its 2D trunks run eagerly (graph2d.ENABLED off for the test: the same kernels, launched one by
-    one) - a captured graph keeps a private memory pool - and every trainer a test built is taken apart once the test is over."""
-    import gc
-
-    from mm2d3d_amd import graph2d
-
-    was = graph2d.ENABLED[0]
-    graph2d.ENABLED[0] = False
-    try:
-        yield
-    finally:
-        graph2d.ENABLED[0] = was
-        for tm in _BUILT:
-            _dispose(tm)
-        del _BUILT[:]
-        gc.collect()
-        torch.cuda.empty_cache()
 
 
 def _trainer(n2, n3, **kw):
@@ -126,12 +87,12 @@ def test_hard_targets_twin_fed_the_labels_stays_bit_identical(case):
         lb = B.fit_step(batches_b[s])
         assert T._same(la, lb), (case, s, T._f(la), T._f(lb))
         common = [k for k in A.last_logs if k in B.last_logs]
-        assert len(common) == 8 and set(T.PL_KEYS) <= set(common)
-        assert set(A.last_logs) - set(common) == set(T.KEPT_KEYS) | set(TAU_KEYS)
+        assert len(common) == 8 and set(PL_KEYS) <= set(common)
+        assert set(A.last_logs) - set(common) == set(KEPT_KEYS) | set(TAU_KEYS)
         for k in common:
             assert T._same(A.last_logs[k], B.last_logs[k]), (case, s, k, T._f(A.last_logs[k]), T._f(B.last_logs[k]))
         # the logged share is the labels' kept share, the logged tau this step's state
-        for o, k in enumerate(T.KEPT_KEYS):
+        for o, k in enumerate(KEPT_KEYS):
             assert A.last_logs[k].is_cuda and T._f(A.last_logs[k]) == T._f(torch.tensor(kept[o], dtype=torch.float32, device=dev) / n_trg)
         for o, k in enumerate(TAU_KEYS):
             assert A.last_logs[k].is_cuda and A.last_logs[k].dim() == 0
@@ -164,11 +125,11 @@ def test_soft_targets_thresholds_are_a_stand_alone_objects(case):
         assert got["kept"].tolist() == want
         if kw["pl_threshold_momentum"] == 0.0:
             assert all(0 < k < n_trg for k in want), want
-        for o, k in enumerate(T.KEPT_KEYS):
+        for o, k in enumerate(KEPT_KEYS):
             assert T._f(A.last_logs[k]) == T._f(torch.tensor(want[o], dtype=torch.float32, device=dev) / n_trg)
         for o, k in enumerate(TAU_KEYS):
             assert T._f(A.last_logs[k]) == float(alone.state[o, 0].to(torch.float32))
-        assert all(torch.isfinite(A.last_logs[k]) for k in T.PL_KEYS)
+        assert all(torch.isfinite(A.last_logs[k]) for k in PL_KEYS)
 
 
 @pytest.mark.parametrize("targets", ["hard", "soft"])

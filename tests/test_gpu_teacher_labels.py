@@ -227,3 +227,28 @@ def test_an_empty_batch_launches_nothing():
         pselab.teacher_labels(torch.zeros(3, device=dev), e)
     with pytest.raises(ValueError, match=r"pselab\.teacher_labels: .*same shape"):
         pselab.teacher_labels(torch.zeros(2, 6, device=dev), e)
+
+
+@pytest.mark.parametrize("ens", [False, True], ids=["own", "ensemble"])
+def test_a_threshold_tensor_gives_the_labels_of_the_adaptive_object(ens):
+    """teacher_labels(threshold=[2, C] tensor) called directly gives what AdaptiveThreshold.labels gives a second object in the same
+    state.  Both go through the same wrapper and the same launch, so this is no check against a second implementation (the float64
+    oracle of tests/test_gpu_pl_adaptive.py is that): it pins the public argument - the tensor is taken, the per-class entry point
+    runs, ``kept`` counts the labels that are not -100, rows without a confidence are refused.  130 rows = one full 128-row tile
+    and a ragged one; one row without a confidence in each matrix."""
+    from mm2d3d_amd import pselab
+
+    dev = _dev()
+    a, b = (torch.from_numpy(x[:130]).to(dev).clone() for x in _logits(6))
+    a[3, 2], b[129, 0] = float("nan"), float("inf")
+    one, two = (pselab.AdaptiveThreshold(6, momentum=0.5, device=dev) for _ in range(2))
+    thr = one.update(a, b, ensemble=ens)
+    want = two.labels(a, b, ensemble=ens, with_probs=True)
+    got = pselab.teacher_labels(a, b, ensemble=ens, threshold=thr, with_probs=True)
+    assert torch.equal(one.state.view(torch.int64), two.state.view(torch.int64)) and torch.equal(_bits(thr), _bits(want["threshold"]))
+    assert set(got) == set(want) - {"threshold"}
+    for k in ("label_2d", "label_3d", "kept"):
+        assert torch.equal(got[k], want[k]), (ens, k)
+    kept = [int((got[k] != -100).sum()) for k in ("label_2d", "label_3d")]
+    assert got["kept"].tolist() == kept and all(0 < k < 130 for k in kept), kept  # the thresholds bite, and not on every row
+    assert int(got["label_2d"][3]) == -100 and int(got["label_3d"][129]) == -100  # no confidence: refused under any threshold

@@ -11,95 +11,17 @@ import numpy as np
 import pytest
 import torch
 
+from _step_util import _alone_logits, _assert_same_dicts, _batch, _dev, _f, _nets, _restore_precision, _same, _trainer  # noqa: F401  (_restore_precision: the autouse fixture, for this module too)
+
 pytestmark = pytest.mark.gpu
 
-W = [1.9241476, 1.0, 2.16763851, 2.78254323, 1.54875664, 1.85686537]
-NET3D = dict(in_channels=3, m=16, full_scale=4096, num_planes=7)
-CE = [{"name": "cross_entropy", "target": "segmentation", "args": {"weight": W}}]
-DECAY, STEPS = 0.9, 3
+STEPS = 3
 PL_KEYS = ("train/pl_loss_tgt_2d", "train/pl_loss_tgt_3d")
 KEPT_KEYS = ("train/pl_kept_2d", "train/pl_kept_3d")
 
 
-def _dev():
-    import mm2d3d_amd  # noqa: F401
-
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(autouse=True)
-def _restore_precision():
-    from mm2d3d_amd import nn2d, scn
-
-    try:
-        yield
-    finally:
-        nn2d.set_precision(nn2d.DEFAULT_PRECISION)
-        scn.set_activation_dtype(torch.float32)
-
-
-def _nets(dev, seed=0, head_scale=1.0, head_scale_2d=None):
-    from mm2d3d_amd.net2d import Net2DSeg
-    from mm2d3d_amd.net3d import Net3DSeg
-
-    torch.manual_seed(seed)
-    n2, n3 = Net2DSeg(6, pretrained=False), Net3DSeg(6, True, NET3D)
-    for m in n2.modules():  # dropout is random: off, for parity between the sides
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
-    if head_scale != 1.0:  # larger logits: wider gaps between the two best classes, and confidences on both sides of a threshold
-        with torch.no_grad():
-            n2.con1_1_avg.weight.mul_(head_scale if head_scale_2d is None else head_scale_2d), n3.linear.weight.mul_(head_scale)
-    return n2.to(dev), n3.to(dev)
-
-
-def _batch(dev):
-    from mm2d3d_amd.synthetic import make_batch
-
-    return {"source": make_batch(5, 1, "nuscenes", (48, 64), device=dev), "target": make_batch(6, 1, "nuscenes", (48, 64), device=dev)}
-
-
-def _trainer(n2, n3, lr=1e-3, **kw):
-    from mm2d3d_amd.losses import Loss
-    from mm2d3d_amd.optimizers import Optimizer
-    from mm2d3d_amd.train import TrainModel
-
-    return TrainModel({"2d_net": n2, "3d_net": n3}, {k: Optimizer("adamw", lr=lr) for k in ("2d_net", "3d_net")}, Loss(CE),
-                      dict(lambda_xm_src=1.0, lambda_xm_trg=0.1, gc_freeze=False, precision="fp16", ema_decay=DECAY, **kw))
-
-
 def _teacher_trainer(n2, n3, **kw):
     return _trainer(n2, n3, lambda_pl=1.0, pseudo_label_source="teacher", **kw)
-
-
-def _bits(t):
-    t = t.detach().contiguous().reshape(-1)
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _f(t):
-    return float(t.detach())
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _assert_same_dicts(a, b, what):
-    assert list(a) == list(b), what
-    for k in a:
-        assert _same(a[k], b[k]), (what, k)
-
-
-def _alone_logits(tm, dev):
-    """The teacher's logits of the target batch ALONE: an eval forward under ``ema.applied()``, outside any step."""
-    trg = _batch(dev)["target"]
-    with torch.no_grad(), tm._use(), tm.ema.applied():
-        tm.model.eval()
-        l2 = tm(trg, model_name="2d_net")[0]["seg_logit"].clone()
-        l3 = tm(trg, model_name="3d_net")[0]["seg_logit"].clone()
-    tm.model.train()
-    return l2, l3
 
 
 def _gap64(logits):

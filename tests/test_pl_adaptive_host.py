@@ -1,5 +1,5 @@
 """Host checks of the self-adaptive per-class pseudo-label thresholds: the float64 oracle (tests/_adaptive_ref.py) on an example
-worked by hand, train_kwargs["pl_threshold"] = "adaptive" in the constructor (mm2d3d_amd/train.py), and the argument checks of the
+worked by hand, train_kwargs["pl_threshold"] = "adaptive" in the constructor (mm2d3d_amd/selftrain.py), and the argument checks of the
 three new entry-point families (include/mm2d3d.h: mm_pl_adapt, mm_teacher_labels_cls, mm_ce2s_fwd_cls / mm_ce2s_bwd_cls), every one
 of which is decided before any device call.  No GPU."""
 import ctypes
@@ -104,9 +104,11 @@ def test_the_option_adds_no_attribute_and_lambda_zero_builds_nothing():
     teacher = make(ema_decay=0.9, pseudo_label_source="teacher", pl_threshold=0.9, lambda_pl=1.0)
     adaptive = make(ema_decay=0.9, pseudo_label_source="teacher", pl_threshold="adaptive", lambda_pl=0.0, pl_threshold_warmup=True)
     assert set(vars(plain)) == set(vars(teacher)) == set(vars(adaptive))
-    assert "pl_adaptive" in vars(plain) and plain.pl_adaptive is None and teacher.pl_adaptive is None
+    assert set(vars(plain.selftrain)) == set(vars(teacher.selftrain)) == set(vars(adaptive.selftrain))  # where the options live
+    assert "pl_adaptive" in vars(plain.selftrain) and plain.pl_adaptive is None and teacher.pl_adaptive is None
     adaptive.configure_optimizers(), teacher.configure_optimizers()
     assert set(vars(teacher)) == set(vars(adaptive)) and adaptive.pl_adaptive is None
+    assert set(vars(teacher.selftrain)) == set(vars(adaptive.selftrain))
     # lambda_pl == 0: a checkpoint is taken and loaded without the object
     ckpt = adaptive.checkpoint()
     assert "pl_adaptive" not in ckpt

@@ -1,5 +1,5 @@
 """Host checks of the self-training options (train_kwargs["lambda_pl"], ["pseudo_labels"]) and of the C ABI of the two-segment
-cross entropy (include/mm2d3d.h mm_ce2_*).  No GPU."""
+cross entropy (include/mm2d3d.h mm_ce2_*).  The options live in mm2d3d_amd/selftrain.py; the trainer forwards them.  No GPU."""
 import ctypes
 import os
 import re
@@ -34,20 +34,20 @@ def test_constructor_checks_the_two_options():
 
 def test_pseudo_label_refusals_are_host_checks():
     """Raised from the batch dict alone, before a forward pass: no device is involved."""
-    tm = _trainer(lambda_pl=1.0)
+    st = _trainer(lambda_pl=1.0).selftrain
     x = [torch.zeros(5, 4, dtype=torch.int64), torch.zeros(5, 3)]
     y = torch.zeros(5, dtype=torch.int64)
     with pytest.raises(KeyError, match="pselab_paths="):
-        tm._pseudo_labels({"x": x})
+        st.batch_targets({"x": x})
     with pytest.raises(ValueError, match='pseudo_labels="ensemble"'):
-        tm._pseudo_labels({"x": x, "pseudo_label_2d": y, "pseudo_label_3d": [], "pseudo_label_ensemble": y})
+        st.batch_targets({"x": x, "pseudo_label_2d": y, "pseudo_label_3d": [], "pseudo_label_ensemble": y})
     with pytest.raises(ValueError, match="5 point rows"):
-        tm._pseudo_labels({"x": x, "pseudo_label_2d": y[:4], "pseudo_label_3d": y, "pseudo_label_ensemble": y})
-    a, b = tm._pseudo_labels({"x": x, "pseudo_label_2d": y, "pseudo_label_3d": y + 1, "pseudo_label_ensemble": y + 2})
-    assert a is y and int(b[0]) == 1
-    ens = _trainer(lambda_pl=1.0, pseudo_labels="ensemble")
-    a, b = ens._pseudo_labels({"x": x, "pseudo_label_2d": y, "pseudo_label_3d": [], "pseudo_label_ensemble": y + 2})
-    assert int(a[0]) == 2 and a is b
+        st.batch_targets({"x": x, "pseudo_label_2d": y[:4], "pseudo_label_3d": y, "pseudo_label_ensemble": y})
+    a, b = st.batch_targets({"x": x, "pseudo_label_2d": y, "pseudo_label_3d": y + 1, "pseudo_label_ensemble": y + 2})
+    assert a.value is y and int(b.value[0]) == 1 and a[1:] == b[1:] == (None, None)  # labels alone: no second matrix, no threshold
+    ens = _trainer(lambda_pl=1.0, pseudo_labels="ensemble").selftrain
+    a, b = ens.batch_targets({"x": x, "pseudo_label_2d": y, "pseudo_label_3d": [], "pseudo_label_ensemble": y + 2})
+    assert int(a.value[0]) == 2 and a.value is b.value
 
 
 def test_the_single_cross_entropy_entry_is_recognised():

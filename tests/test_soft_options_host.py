@@ -1,4 +1,4 @@
-"""Host checks of the soft mean-teacher targets: train_kwargs["pl_targets"] / ["pl_temperature"] (mm2d3d_amd/train.py) and the C ABI
+"""Host checks of the soft mean-teacher targets: train_kwargs["pl_targets"] / ["pl_temperature"] (mm2d3d_amd/selftrain.py) and the C ABI
 of the two-segment cross entropy with a soft tail (include/mm2d3d.h mm_ce2s_*).  No GPU."""
 import ctypes
 import os
@@ -62,27 +62,32 @@ def test_soft_targets_refuse_the_median_rule():
 def test_a_batch_without_teacher_logits_is_refused_before_anything_is_queued():
     """Raised from the batch dict alone: the networks below are never called (a torch.nn.Linear could not take the batch)."""
     tm = _trainer(lambda_pl=1.0, pl_targets="soft", pseudo_label_source="batch")
+    st = tm.selftrain
     x = [torch.zeros(5, 4, dtype=torch.int64), torch.zeros(5, 3)]
     l = torch.zeros(5, 6)
     src = {"x": x, "img": torch.zeros(1, 3, 4, 4), "depth": torch.zeros(1, 1, 4, 4), "seg_label": torch.zeros(5, dtype=torch.int64)}
     with pytest.raises(KeyError, match="teacher_logit_2d"):
         tm.training_step({"source": src, "target": {"x": x, "teacher_logit_3d": l}})
     with pytest.raises(KeyError, match="teacher_logit_3d"):
-        tm._teacher_logits({"x": x, "teacher_logit_2d": l})
+        st.batch_targets({"x": x, "teacher_logit_2d": l})
     with pytest.raises(ValueError, match="5 point rows"):
-        tm._teacher_logits({"x": x, "teacher_logit_2d": l[:4], "teacher_logit_3d": l})
+        st.batch_targets({"x": x, "teacher_logit_2d": l[:4], "teacher_logit_3d": l})
     with pytest.raises(ValueError, match="5 point rows"):
-        tm._teacher_logits({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": torch.zeros(5, dtype=torch.int64)})
+        st.batch_targets({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": torch.zeros(5, dtype=torch.int64)})
     with pytest.raises(ValueError, match="teacher_logit_3d"):
-        tm._teacher_logits({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": torch.zeros(5, 7)})
-    a, b = tm._teacher_logits({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": l + 1})
-    assert a is l and float(b[0, 0]) == 1.0
-    assert tm._soft_targets(a, b) == [(a, None), (b, None)]
-    ens = _trainer(lambda_pl=1.0, pl_targets="soft", pseudo_labels="ensemble")
-    assert ens._soft_targets(a, b) == [(a, b), (a, b)]
+        st.batch_targets({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": torch.zeros(5, 7)})
+    batch = {"x": x, "teacher_logit_2d": l, "teacher_logit_3d": l + 1}
+    a, b = batch["teacher_logit_2d"], batch["teacher_logit_3d"]
+    own = st.batch_targets(batch)
+    assert own[0].value is l and float(own[1].value[0, 0]) == 1.0
+    assert [tuple(t) for t in own] == [(a, None, None), (b, None, None)]  # per head (teacher, teacher_other, threshold)
+    ens = _trainer(lambda_pl=1.0, pl_targets="soft", pseudo_labels="ensemble").selftrain
+    assert [tuple(t) for t in ens.batch_targets(batch)] == [(a, b, None), (a, b, None)]
+    cut = _trainer(lambda_pl=1.0, pl_targets="soft", pseudo_labels="ensemble", pl_threshold=0.5).selftrain
+    assert [t.threshold for t in cut.batch_targets(batch)] == [0.5, 0.5]  # a fixed threshold travels with each head's target
     # hard targets of the same batch still ask for labels, and lambda_pl = 0 consults nothing of this
     with pytest.raises(KeyError, match="pseudo_label_2d"):
-        _trainer(lambda_pl=1.0)._pseudo_labels({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": l})
+        _trainer(lambda_pl=1.0).selftrain.batch_targets({"x": x, "teacher_logit_2d": l, "teacher_logit_3d": l})
     assert _trainer(pl_targets="soft", pl_temperature=2.0).lambda_pl == 0.0
 
 

@@ -1,5 +1,5 @@
 """Host checks of the online mean-teacher pseudo labels: the C ABI of mm_teacher_labels (include/mm2d3d.h, csrc/pselab.hip) and
-train_kwargs["pseudo_label_source"] / ["pl_threshold"] (mm2d3d_amd/train.py).  No GPU."""
+train_kwargs["pseudo_label_source"] / ["pl_threshold"] (mm2d3d_amd/selftrain.py, through the trainer).  No GPU."""
 import ctypes
 import os
 import re
@@ -102,6 +102,7 @@ def test_lambda_pl_zero_with_the_teacher_source_builds_what_ema_decay_alone_buil
     assert with_source.ema is not None and with_source.ema.decay == plain.ema.decay == 0.9
     assert with_source.ema._nrows == plain.ema._nrows and with_source.last_teacher is None
     assert set(vars(with_source)) == set(vars(plain))  # no state beyond the options themselves
+    assert set(vars(with_source.selftrain)) == set(vars(plain.selftrain))  # ... nor in the policy object that holds them
 
 
 def test_a_suspended_forward_claims_no_gradient_sink():
@@ -127,5 +128,19 @@ def test_the_label_helper_refuses_to_run_before_the_teacher_exists():
     """The teacher is built with the optimisers (fit_step does it); the helper raises rather than building them itself."""
     tm = _trainer(pseudo_label_source="teacher", ema_decay=0.9, lambda_pl=1.0)
     with pytest.raises(RuntimeError, match="configure_optimizers"):
-        tm._teacher_labels({}, {})
+        tm.selftrain.teacher_targets(tm, {}, {})
     assert tm.ema is None and not tm.optimizers
+
+
+def test_a_threshold_tensor_is_checked_before_anything_else():
+    """pselab.teacher_labels(threshold=tensor): float32 [2, C] on the logits' device, or a ValueError that names the argument -
+    decided from the arguments alone (a tensor that passes gets as far as the refusal of logits that are not on a GPU)."""
+    from mm2d3d_amd import pselab
+
+    l = torch.zeros(5, 6)
+    for bad in (torch.zeros(2, 6, dtype=torch.float64), torch.zeros(2, 6, dtype=torch.int64), torch.zeros(6), torch.zeros(2, 5),
+                torch.zeros(1, 6), torch.zeros(6, 2), torch.zeros(2, 6, device="meta")):
+        with pytest.raises(ValueError, match="threshold"):
+            pselab.teacher_labels(l, l, threshold=bad)
+    with pytest.raises(RuntimeError, match="logits_2d must live on the GPU"):
+        pselab.teacher_labels(l, l, threshold=torch.zeros(2, 6))

@@ -180,7 +180,7 @@ def main():
                 return orig
 
             origs = {name: wrap(name, net) for name, net in tm.model.items()}
-            inner = tm._teacher_labels
+            inner = tm.selftrain.teacher_targets
 
             def teacher_pass(*a, **kws):
                 t0 = time.perf_counter()
@@ -188,7 +188,7 @@ def main():
                 acc["teacher pass"] = acc.get("teacher pass", 0.0) + (time.perf_counter() - t0) * 1e3
                 return out
 
-            tm._teacher_labels = teacher_pass
+            tm.selftrain.teacher_targets = teacher_pass
             host, wall, parts = [], [], []
             for _ in range(args.host_steps):
                 seeded(k)
@@ -201,7 +201,7 @@ def main():
                 host.append((t1 - t0) * 1e3)
                 wall.append((time.perf_counter() - t0) * 1e3)
                 parts.append(dict(acc))
-            tm._teacher_labels = inner
+            del tm.selftrain.teacher_targets  # the instance attribute: the class's method is back
             for name, net in tm.model.items():
                 del net.forward  # the instance attribute: the class's method is back
             if host:

@@ -1,0 +1,212 @@
+"""Bits of the self-training step, for comparing two checkouts of this project (a refactor against its parent).
+
+    python tools/selftrain_bits.py dump OUT.npz [--only SUBSTRING]
+    python tools/selftrain_bits.py compare A.npz B.npz
+
+``dump`` runs every self-training option combination for three ``fit_step`` calls at the shapes of tests/test_gpu_teacher_step.py
+(1 + 1 synthetic nuScenes scenes, 48x64 images, 6 classes, fp16, dropout 0, ``ema_decay`` 0.9, heads scaled by 4; fresh nets from
+seed 0 per case) and stores, as raw bytes: per step the loss, every ``last_logs`` value and every tensor of ``last_teacher``; after
+the last step every entry of the checkpoint's "state_dict" and "ema_state_dict" and the state of ``pl_adaptive``.  It uses only
+``train_kwargs``, ``fit_step``, ``last_logs``, ``last_teacher``, ``pl_adaptive.state_dict()``, ``checkpoint()`` and
+``load_checkpoint()``, so the same file runs in either checkout (it imports the package of the checkout whose ``tools/`` it lies
+in: copy it there).  ``compare`` demands equal key lists and equal bytes, prints the
+number of arrays and the total bytes, and exits 1 on any difference.  One process per dump.
+"""
+import argparse
+import gc
+import itertools
+import os
+import sys
+import zipfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+W = [1.9241476, 1.0, 2.16763851, 2.78254323, 1.54875664, 1.85686537]
+NET3D = dict(in_channels=3, m=16, full_scale=4096, num_planes=7)
+CE = {"name": "cross_entropy", "target": "segmentation", "args": {"weight": W}}
+REGISTRY = {"single": [CE], "two_entries": [dict(CE, weight=0.5), dict(CE, weight=0.5)]}
+STEPS = 3
+ADAPTIVE = dict(pl_threshold_momentum=0.5, pl_threshold_warmup=True)  # the thresholds bite from the first step
+
+
+def cases():
+    """name -> (train_kwargs, registry, extras of the target batch, prefetch, checkpoint round trip after step 2)."""
+    out = {}
+
+    def add(name, kw, registry="single", extras=None, prefetch=False, resume=False):
+        if kw.get("pl_threshold") == "adaptive":
+            kw = dict(kw, **ADAPTIVE)
+        out[name] = (kw, registry, extras, prefetch, resume)
+
+    calls = {"joined": {}, "two_calls": dict(joint_domains=False)}
+    for mode, (call, ckw), reg in itertools.product(("own", "ensemble"), calls.items(), REGISTRY):
+        add(f"batch/hard/{mode}/{call}/{reg}", dict(lambda_pl=1.0, pseudo_labels=mode, **ckw), reg, "labels")
+    for mode, thr, T in itertools.product(("own", "ensemble"), (None, 0.9), (1.0, 2.0)):
+        add(f"batch/soft/{mode}/thr_{thr}/T_{T}", dict(lambda_pl=1.0, pseudo_labels=mode, pl_targets="soft", pl_threshold=thr, pl_temperature=T),
+            extras="logits")
+    teacher = dict(lambda_pl=1.0, pseudo_label_source="teacher")
+    for targets, thresholds in (("hard", (None, 0.9, "median", "adaptive")), ("soft", (None, 0.9, "adaptive"))):
+        for thr in thresholds:
+            for mode in ("own", "ensemble"):
+                add(f"teacher/{targets}/{mode}/thr_{thr}/joined", dict(teacher, pseudo_labels=mode, pl_targets=targets, pl_threshold=thr))
+            add(f"teacher/{targets}/own/thr_{thr}/two_calls", dict(teacher, pl_targets=targets, pl_threshold=thr, joint_domains=False))
+    add("teacher/hard/own/thr_None/prefetched", dict(teacher), prefetch=True)
+    add("teacher/lambda_pl_0", dict(lambda_pl=0.0, pseudo_label_source="teacher", pl_threshold=0.9))
+    add("teacher/hard/own/thr_adaptive/checkpoint_round_trip", dict(teacher, pl_threshold="adaptive"), resume=True)
+    return out
+
+
+def _trainer(dev, kw, registry):
+    import torch
+
+    from mm2d3d_amd.losses import Loss
+    from mm2d3d_amd.net2d import Net2DSeg
+    from mm2d3d_amd.net3d import Net3DSeg
+    from mm2d3d_amd.optimizers import Optimizer
+    from mm2d3d_amd.train import TrainModel
+
+    torch.manual_seed(0)
+    n2, n3 = Net2DSeg(6, pretrained=False), Net3DSeg(6, True, NET3D)
+    for m in n2.modules():
+        if isinstance(m, torch.nn.Dropout):
+            m.p = 0.0
+    with torch.no_grad():
+        n2.con1_1_avg.weight.mul_(4.0), n3.linear.weight.mul_(4.0)
+    return TrainModel({"2d_net": n2.to(dev), "3d_net": n3.to(dev)}, {k: Optimizer("adamw", lr=1e-3) for k in ("2d_net", "3d_net")},
+                      Loss(REGISTRY[registry]), dict(lambda_xm_src=1.0, lambda_xm_trg=0.1, gc_freeze=False, precision="fp16", ema_decay=0.9, **kw))
+
+
+def _batch(dev, extras, step):
+    import torch
+
+    from mm2d3d_amd.synthetic import make_batch
+
+    b = {"source": make_batch(5, 1, "nuscenes", (48, 64), device=dev), "target": make_batch(6, 1, "nuscenes", (48, 64), device=dev)}
+    n = int(b["target"]["x"][0].shape[0])
+    g = torch.Generator().manual_seed(50 + step)
+    if extras == "labels":  # as tests/test_gpu_pl_step.py _pseudo: about half are -100; the three arrays differ
+        for k in ("pseudo_label_2d", "pseudo_label_3d", "pseudo_label_ensemble"):
+            y = torch.randint(0, 6, (n,), generator=g)
+            y[torch.rand(n, generator=g) < 0.5] = -100
+            b["target"][k] = y.to(dev)
+    elif extras == "logits":  # a frozen teacher of the caller's own: confidences on both sides of 0.9
+        for k in ("teacher_logit_2d", "teacher_logit_3d"):
+            b["target"][k] = (3.0 * torch.randn(n, 6, generator=g)).to(dev)
+    return b
+
+
+def _raw(t):
+    import torch
+
+    return t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy()
+
+
+def _forget(tm):
+    """Lets the trainer's device memory go (the optimisers' arenas and their hooks hold each other): forty trainers in one process."""
+    import torch
+
+    for opt in tm.optimizers:
+        for a in getattr(opt, "_arenas", ()):
+            if a is not None:
+                a.clear()
+    for q in tm.model.parameters():
+        hooks = getattr(q, "_post_accumulate_grad_hooks", None)
+        if hooks is not None:
+            hooks.clear()
+        q.__dict__.pop("_mm_hooks", None)
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def dump(path, only=None):
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("selftrain_bits: needs a GPU")
+    dev = torch.device("cuda:0")
+    count = nbytes = 0
+    archive = zipfile.ZipFile(path, "w", zipfile.ZIP_STORED, allowZip64=True)  # what np.savez writes, one array at a time
+
+    def put(key, arr):
+        nonlocal count, nbytes
+        with archive.open(key + ".npy", "w", force_zip64=True) as f:
+            np.lib.format.write_array(f, arr, allow_pickle=False)
+        count, nbytes = count + 1, nbytes + arr.nbytes
+
+    for name, (kw, registry, extras, prefetch, resume) in cases().items():
+        if only and only not in name:
+            continue
+        tm = _trainer(dev, kw, registry)
+        batches = [_batch(dev, extras, s) for s in range(STEPS)]
+        for s in range(STEPS):
+            if resume and s == 2:  # a fresh trainer takes over from the checkpoint, before its first teacher pass
+                ckpt, old = tm.checkpoint(), tm
+                tm = _trainer(dev, kw, registry)
+                tm.load_checkpoint(ckpt)
+                _forget(old)
+            torch.manual_seed(100 + s)
+            loss = tm.fit_step(batches[s], **(dict(next_batch=batches[s + 1]) if prefetch and s + 1 < STEPS else {}))
+            put(f"{name}/step{s}/loss", _raw(loss))
+            for k, v in tm.last_logs.items():
+                put(f"{name}/step{s}/logs/{k}", _raw(v))
+            for k, v in (tm.last_teacher or {}).items():
+                if torch.is_tensor(v):
+                    put(f"{name}/step{s}/last_teacher/{k}", _raw(v))
+        ckpt = tm.checkpoint()
+        for part in ("state_dict", "ema_state_dict"):
+            for k, v in ckpt[part].items():
+                put(f"{name}/{part}/{k}", _raw(v))
+        if tm.pl_adaptive is not None:
+            for k, v in tm.pl_adaptive.state_dict().items():
+                put(f"{name}/pl_adaptive/{k}", _raw(v) if torch.is_tensor(v) else np.array([v], dtype=np.int64).view(np.uint8))
+        torch.cuda.synchronize()
+        print(f"{name}: loss {float(loss.detach()):.6f}, {len(tm.last_logs)} logged keys, "
+              f"last_teacher {sorted(tm.last_teacher) if tm.last_teacher else None}", flush=True)
+        _forget(tm)
+        del tm, ckpt, batches
+    archive.close()
+    print(f"{count} arrays, {nbytes} bytes -> {path}", flush=True)
+
+
+def compare(a_path, b_path):
+    a, b = np.load(a_path), np.load(b_path)
+    ka, kb = list(a.files), list(b.files)
+    bad = []
+    if ka != kb:
+        bad += [f"only in {a_path}: {k}" for k in ka if k not in set(kb)] + [f"only in {b_path}: {k}" for k in kb if k not in set(ka)]
+        bad += ["the key lists differ in order"] if not bad else []
+    total = 0
+    for k in ka:
+        if k in b.files:
+            x, y = a[k], b[k]
+            total += x.nbytes
+            if x.shape != y.shape or not np.array_equal(x, y):
+                bad.append(f"differs: {k} ({x.nbytes} / {y.nbytes} bytes)")
+    names = sorted({k.split("/step")[0] for k in ka if "/step" in k})
+    print(f"{len(names)} cases, {len(ka)} arrays, {total} bytes: " + ("all identical" if not bad else f"{len(bad)} DIFFERENCES"))
+    for line in bad[:200]:
+        print(line)
+    return 1 if bad else 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    d = sub.add_parser("dump")
+    d.add_argument("out")
+    d.add_argument("--only", default=None, help="run the cases whose name contains this")
+    c = sub.add_parser("compare")
+    c.add_argument("a")
+    c.add_argument("b")
+    args = ap.parse_args()
+    if args.cmd == "dump":
+        dump(args.out, args.only)
+    else:
+        raise SystemExit(compare(args.a, args.b))
+
+
+if __name__ == "__main__":
+    main()
