@@ -109,6 +109,42 @@ int mm_rulebook_compact(const int32_t* nbr, int K, int64_t n_out, int32_t* rin, 
 int mm_rulebook_csr(const int32_t* nbr, int K, int64_t n_out, int32_t* csr_off, int32_t* csr_pos, int no_spin, void* ws,
                     size_t ws_bytes, mm_stream_t stream);
 
+/* ---- every level in one launch per stage (same results as the per-level entry points above, bit for bit)
+ * The whole dedupe chain points -> level 0 -> ... -> level nlev-1 without waiting for a level's size: the sites of level l are
+ * the distinct (x >> l, y >> l, z >> l, batch) of the points, ranked by their smallest point index, which is the order of first
+ * occurrence among the rows of level l-1.  At most 12 launches.
+ *   coords        device int64 [n_pts,4]
+ *   tkeys/tvals   [nlev][cap], cap = mm_hash_capacity(n_pts); afterwards key -> site id, per level
+ *   item2vox      [nlev][max(n_pts,1)]    row l: items of level l (points for l = 0, rows of level l-1 otherwise) -> site id
+ *   vox_coords    [nlev][max(n_pts,1)][4]
+ *   csr_off/items [nlev][n_pts+1] / [nlev][max(n_pts,1)]
+ *   split         >= 0: counts[nlev+1+l] = rows of level l with batch index < split (mm_batch_lower_bound); < 0: left 0
+ *   counts        device int32 [2*nlev+1], written here: sites per level, then the error word (1 coordinate out of range, 2 table
+ *                 full), then the split rows */
+size_t mm_dedupe_levels_ws_bytes(int64_t n_pts, int nlev);
+int mm_voxel_dedupe_levels(const int64_t* coords, int64_t n_pts, int nlev, uint64_t* tkeys, int32_t* tvals, int64_t cap,
+                           int32_t* item2vox, int32_t* vox_coords, int32_t* csr_off, int32_t* csr_items, int32_t split,
+                           int32_t* counts, int no_spin, void* ws, size_t ws_bytes, mm_stream_t stream);
+/* Neighbour tables of several levels: mm_subm_neighbors (K = 27: vox_coords, n, spatial_size and the table of one level) and
+ * mm_down_neighbors (K = 8: vox_coords and n of the fine level, fine2coarse, n_coarse) in three launches for all of them.
+ * Host array of at most MM_META_BATCH entries. */
+#define MM_META_BATCH 32
+typedef struct mm_nbr_desc {
+  const int32_t* vox_coords; const uint64_t* tkeys; const int32_t* tvals; const int32_t* fine2coarse; int32_t* nbr;
+  int64_t n, n_coarse, cap; int32_t spatial_size, K;
+} mm_nbr_desc;
+int mm_neighbors_batch(const mm_nbr_desc* d, int nd, mm_stream_t stream);
+/* mm_rulebook_compact of several neighbour tables that lie back to back in one array nbr (table j: K * n_out words from word
+ * start; start of table 0 is 0): the rule lists of table j begin at word start of rin / rout, its K + 1 bucket offsets at word offs
+ * of offsets.  row0 >= 0: also its CSR, n_out + 1 words from word row0 of csr_off (back to back in table order, from 0) and K * n_out
+ * words from word pos0 of csr_pos.  ws: mm_rulebook_batch_ws_bytes(words of nbr, words of csr_off). */
+typedef struct mm_rulebook_desc {
+  int64_t start, n_out, row0, pos0; int32_t K, offs;
+} mm_rulebook_desc;
+size_t mm_rulebook_batch_ws_bytes(int64_t nbr_words, int64_t csr_rows);
+int mm_rulebook_compact_batch(const int32_t* nbr, const mm_rulebook_desc* d, int nd, int32_t* rin, int32_t* rout, int32_t* offsets,
+                              int32_t* csr_off, int32_t* csr_pos, int no_spin, void* ws, size_t ws_bytes, mm_stream_t stream);
+
 /* ---------------------------------------------------------------- GPU-side sample preparation (csrc/dataprep.hip)
  * The loader-side numpy code of the reference for a whole batch of scenes, bit-exact with it:
  * augment_and_scale_3d + int cast + range mask (lib/utils/augmentation_3d.py:83-158, nuscenes_dataloader.py:323-332),

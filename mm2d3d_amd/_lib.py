@@ -41,6 +41,11 @@ _PROTOS = {
     "mm_rulebook_ws_bytes": (sz, [i64, i32]),
     "mm_rulebook_compact": (i32, [vp, i32, i64, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "mm_rulebook_csr": (i32, [vp, i32, i64, vp, vp, i32, vp, sz, vp]),
+    "mm_dedupe_levels_ws_bytes": (sz, [i64, i32]),
+    "mm_voxel_dedupe_levels": (i32, [vp, i64, i32, vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, vp, sz, vp]),
+    "mm_neighbors_batch": (i32, [vp, i32, vp]),
+    "mm_rulebook_batch_ws_bytes": (sz, [i64, i64]),
+    "mm_rulebook_compact_batch": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "mm_spconv_ws_bytes": (sz, [i64, i32, i32, i32]),
     "mm_spconv_apply": (i32, [vp, i32, i32, vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, i64, i32, i32, i32, i32, vp, sz, vp]),
     "mm_spconv_apply_packed": (i32, [vp, i32, i32, vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, i64, i32, i32, i32, vp, i32, vp, sz, vp]),
@@ -205,6 +210,17 @@ class Bn2dBwdArgs(C.Structure):
                 ("yout", C.c_void_p), ("ld_y", C.c_int), ("weight", C.c_void_p), ("bias", C.c_void_p), ("save_mean", C.c_void_p),
                 ("save_invstd", C.c_void_p), ("dx", C.c_void_p), ("ld_dx", C.c_int), ("dres", C.c_void_p), ("ld_dr", C.c_int),
                 ("dweight", C.c_void_p), ("dbias", C.c_void_p)]
+
+
+class NbrDesc(C.Structure):
+    """include/mm2d3d.h mm_nbr_desc"""
+    _fields_ = [("vox_coords", C.c_void_p), ("tkeys", C.c_void_p), ("tvals", C.c_void_p), ("fine2coarse", C.c_void_p), ("nbr", C.c_void_p),
+                ("n", C.c_int64), ("n_coarse", C.c_int64), ("cap", C.c_int64), ("spatial_size", C.c_int32), ("K", C.c_int32)]
+
+
+class RulebookDesc(C.Structure):
+    """include/mm2d3d.h mm_rulebook_desc"""
+    _fields_ = [("start", C.c_int64), ("n_out", C.c_int64), ("row0", C.c_int64), ("pos0", C.c_int64), ("K", C.c_int32), ("offs", C.c_int32)]
 
 
 class HipLibraryMissing(RuntimeError):

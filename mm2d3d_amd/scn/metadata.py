@@ -246,35 +246,29 @@ class Metadata:
         dev = self.device
         n_pts = self.n_points = coords_i64.shape[0]
         nlev = max(1, min(self.prebuild_levels, max(1, int(np.log2(max(self.spatial_size, 2))))))
-        counts = torch.zeros(2 * nlev + 1, dtype=I32, device=dev)  # [n_0..n_{L-1}, err, seg_0..seg_{L-1}]
-        err = counts[nlev : nlev + 1]
+        counts = torch.empty(2 * nlev + 1, dtype=I32, device=dev)  # [n_0..n_{L-1}, err, seg_0..seg_{L-1}]
         split = self.split = domains.current()  # scenes [0, split) / [split, B) keep their own batch-norm statistics
         cap = int(L.mm_hash_capacity(n_pts))
-        ws = _lib.workspace.get(int(L.mm_dedupe_ws_bytes(n_pts)), dev)
+        ws = _lib.workspace.get(int(L.mm_dedupe_levels_ws_bytes(n_pts, nlev)), dev)
+        # one array per kind, a row per level: the whole chain is one call (no level waits for the size of the one before)
+        n1 = max(n_pts, 1)
+        tkeys = torch.empty((nlev, cap), dtype=torch.int64, device=dev)
+        tvals = torch.empty((nlev, cap), dtype=I32, device=dev)
+        item2vox = torch.empty((nlev, n1), dtype=I32, device=dev)
+        coords = torch.empty((nlev, n1, 4), dtype=I32, device=dev)
+        csr_off = torch.empty((nlev, n_pts + 1), dtype=I32, device=dev)
+        csr_items = torch.empty((nlev, n1), dtype=I32, device=dev)
+        check(
+            L.mm_voxel_dedupe_levels(ptr(coords_i64), n_pts, nlev, ptr(tkeys), ptr(tvals), cap, ptr(item2vox), ptr(coords), ptr(csr_off),
+                                     ptr(csr_items), -1 if split is None else split, ptr(counts), NO_SPIN[0], ptr(ws), ws.numel(), stream()),
+            "voxel_dedupe_levels",
+        )
         S = self.spatial_size
         prev = None
         for l in range(nlev):
             lv = Level(S)
             lv.cap = cap
-            lv.tkeys = torch.empty(cap, dtype=torch.int64, device=dev)
-            lv.tvals = torch.empty(cap, dtype=I32, device=dev)
-            lv.item2vox = torch.empty(max(n_pts, 1), dtype=I32, device=dev)
-            lv.coords = torch.empty((max(n_pts, 1), 4), dtype=I32, device=dev)
-            lv.csr_off = torch.empty(n_pts + 1, dtype=I32, device=dev)
-            lv.csr_items = torch.empty(max(n_pts, 1), dtype=I32, device=dev)
-            if l == 0:
-                src, is64, ndev, shift = coords_i64, 1, None, 0
-            else:
-                src, is64, ndev, shift = prev.coords, 0, ptr(counts[l - 1 : l]), 1
-            check(
-                L.mm_voxel_dedupe(ptr(src), is64, n_pts, ndev, shift, ptr(lv.tkeys), ptr(lv.tvals), cap,
-                                  ptr(lv.item2vox), ptr(lv.coords), ptr(lv.csr_off), ptr(lv.csr_items),
-                                  ptr(counts[l : l + 1]), ptr(err), NO_SPIN[0], ptr(ws), ws.numel(), stream()),
-                "voxel_dedupe",
-            )
-            if split is not None:
-                check(L.mm_batch_lower_bound(ptr(lv.coords), ptr(counts[l : l + 1]), split, ptr(counts[nlev + 1 + l : nlev + 2 + l]),
-                                             stream()), "batch_lower_bound")
+            lv.tkeys, lv.tvals, lv.item2vox, lv.coords, lv.csr_off, lv.csr_items = tkeys[l], tvals[l], item2vox[l], coords[l], csr_off[l], csr_items[l]
             if prev is not None:
                 prev.coarse, lv.fine = lv, prev
             self.levels.append(lv)
@@ -335,31 +329,12 @@ class Metadata:
         return lv
 
     # ------------------------------------------------------------------ rulebooks
-    def _launch_rulebook(self, K, n_out, nbr, offsets_dev, with_csr=True):
-        L = _lib.lib()
-        dev = self.device
-        rb = Rulebook(K)
-        cap = max(K * n_out, 1)
-        rb.rin = torch.empty(cap, dtype=I32, device=dev)
-        rb.rout = torch.empty(cap, dtype=I32, device=dev)
-        if with_csr:
-            rb.csr_pos = torch.empty(cap, dtype=I32, device=dev)
-            rb.csr_off = torch.empty(n_out + 1, dtype=I32, device=dev)
-        else:
-            rb.csr_pos = rb.csr_off = None
-            rb.nbr = nbr
-        rb.offsets_dev = offsets_dev
-        rb.n_out = n_out
-        ws = _lib.workspace.get(int(L.mm_rulebook_ws_bytes(n_out, K)), dev)
-        check(
-            L.mm_rulebook_compact(ptr(nbr), K, n_out, ptr(rb.rin), ptr(rb.rout), ptr(offsets_dev), ptr(rb.csr_off),
-                                  ptr(rb.csr_pos), NO_SPIN[0], ptr(ws), ws.numel(), stream()),
-            "rulebook_compact",
-        )
-        return rb
+    def _takes_os(self, n):
+        """Destination rows served by the output-stationary engine: their rulebook is built without the CSR."""
+        return n != 0 and (n >= OS_MIN_ROWS or self.act16)
 
     def _os_table(self, nbr, K, n):
-        if n == 0 or (n < OS_MIN_ROWS and not self.act16):
+        if not self._takes_os(n):
             return None
         L = _lib.lib()
         dev = self.device
@@ -392,28 +367,57 @@ class Metadata:
         if not levels:
             return
         offs = torch.zeros((len(levels), 28 + 9), dtype=I32, device=dev)
-        pending = []
+        # The neighbour tables of every rulebook of the build lie back to back in one array (submanifold [27][n], strided
+        # [8][n_coarse]), the rule lists at the same words of rin / rout, the CSRs of the tables that take one back to back in
+        # csr_off / csr_pos: one launch per stage for all of them (mm_neighbors_batch, mm_rulebook_compact_batch).
+        pending, tabs = [], []  # tabs: (rulebook, level, first table word, first csr_off word or -1, first csr_pos word, word in offs)
+        total = rows = npos = 0
         for j, lv in enumerate(levels):
-            nbr = torch.empty(max(27 * lv.n, 1), dtype=I32, device=dev)
-            check(L.mm_subm_neighbors(ptr(lv.coords), lv.n, lv.spatial_size, ptr(lv.tkeys), ptr(lv.tvals), lv.cap,
-                                      ptr(nbr), stream()), "subm_neighbors")
-            subm_os = self._os_table(nbr, 27, lv.n)
-            subm = self._launch_rulebook(27, lv.n, nbr, offs[j, :28], with_csr=subm_os is None)
-            subm.os = subm_os
-            down = None
+            subm, down = Rulebook(27), None
+            subm.n_out = lv.n
             if lv.coarse is not None and lv.down is None:
-                c = lv.coarse
-                nbr8 = torch.empty(max(8 * c.n, 1), dtype=I32, device=dev)
-                check(L.mm_down_neighbors(ptr(lv.coords), lv.n, ptr(c.item2vox), c.n, ptr(nbr8), stream()),
-                      "down_neighbors")
-                down_os = self._os_table(nbr8, 8, c.n)
-                down = self._launch_rulebook(8, c.n, nbr8, offs[j, 28:37], with_csr=down_os is None)
-                down.os = down_os
-                if OS_BUILD_UP or self.act16:  # unique-destination direction: the rulebook engine's direct scatter measured faster
-                    nbr_up = torch.empty(max(8 * lv.n, 1), dtype=I32, device=dev)
-                    check(L.mm_up_neighbors(ptr(lv.coords), lv.n, ptr(c.item2vox), ptr(nbr_up), stream()), "up_neighbors")
-                    down.os_up = self._os_table(nbr_up, 8, lv.n)
+                down = Rulebook(8)
+                down.n_out = lv.coarse.n
+            for rb, o in ((subm, 37 * j), (down, 37 * j + 28)):
+                if rb is None:
+                    continue
+                csr = not self._takes_os(rb.n_out)
+                tabs.append((rb, lv, total, rows if csr else -1, npos, o))
+                total += rb.K * rb.n_out
+                if csr:
+                    rows += rb.n_out + 1
+                    npos += rb.K * rb.n_out
             pending.append((lv, subm, down))
+        nbr, rin, rout = (torch.empty(max(total, 1), dtype=I32, device=dev) for _ in range(3))
+        csr_off = torch.empty(max(rows, 1), dtype=I32, device=dev)
+        csr_pos = torch.empty(max(npos, 1), dtype=I32, device=dev)
+        nd, rd = (_lib.NbrDesc * len(tabs))(), (_lib.RulebookDesc * len(tabs))()
+        for i, (rb, lv, start, row0, pos0, o) in enumerate(tabs):
+            w = rb.K * rb.n_out
+            rb.nbr, rb.rin, rb.rout = nbr[start : start + w], rin[start : start + w], rout[start : start + w]
+            rb.offsets_dev = offs.view(-1)[o : o + rb.K + 1]
+            if row0 >= 0:
+                rb.csr_off, rb.csr_pos = csr_off[row0 : row0 + rb.n_out + 1], csr_pos[pos0 : pos0 + w]
+            else:
+                rb.csr_off = rb.csr_pos = None
+            if rb.K == 27:
+                nd[i] = _lib.NbrDesc(ptr(lv.coords), ptr(lv.tkeys), ptr(lv.tvals), None, ptr(rb.nbr), lv.n, 0, lv.cap, lv.spatial_size, 27)
+            else:
+                nd[i] = _lib.NbrDesc(ptr(lv.coords), None, None, ptr(lv.coarse.item2vox), ptr(rb.nbr), lv.n, lv.coarse.n, 0, 0, 8)
+            rd[i] = _lib.RulebookDesc(start, rb.n_out, row0, pos0, rb.K, o)
+        check(L.mm_neighbors_batch(nd, len(tabs), stream()), "neighbors_batch")
+        for rb, lv, *_ in tabs:  # the tile tables stay one call per table (csrc/ostable.hip)
+            rb.os = self._os_table(rb.nbr, rb.K, rb.n_out)
+            if rb.K == 8 and (OS_BUILD_UP or self.act16):  # unique-destination direction: the rulebook engine's direct scatter measured faster
+                nbr_up = torch.empty(max(8 * lv.n, 1), dtype=I32, device=dev)
+                check(L.mm_up_neighbors(ptr(lv.coords), lv.n, ptr(lv.coarse.item2vox), ptr(nbr_up), stream()), "up_neighbors")
+                rb.os_up = self._os_table(nbr_up, 8, lv.n)
+        ws = _lib.workspace.get(int(L.mm_rulebook_batch_ws_bytes(total, rows)), dev)
+        check(L.mm_rulebook_compact_batch(ptr(nbr), rd, len(tabs), ptr(rin), ptr(rout), ptr(offs), ptr(csr_off), ptr(csr_pos), NO_SPIN[0],
+                                          ptr(ws), ws.numel(), stream()), "rulebook_compact_batch")
+        for rb, *_ in tabs:
+            if rb.csr_pos is not None:
+                rb.nbr = None  # kept only while the CSR has not been built (ensure_csr)
         self._pending_rulebooks = (_Readback(offs), pending)
 
     def finish_rulebooks(self):
