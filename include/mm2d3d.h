@@ -502,6 +502,26 @@ int mm_lovasz_fwd(const float* logits, int ld, int64_t N, int C, const int64_t* 
                   float* err, float* coef, float* stats, void* ws, size_t ws_bytes, mm_stream_t stream);
 int mm_lovasz_bwd(const float* logits, int ld, int64_t N, int C, const float* coef, const float* grad_out, float* dlogits,
                   int ld_d, mm_stream_t stream);
+/* Target-domain entropy (MinEnt) and diversity (the batch-mean term of information maximisation) of rows [P, N) of logits [N, C]
+ * (row pitch ld; csrc/infomax.hip).  Counted rows: the rows i of [P, N) whose C logits are all finite; n of them.  Per counted row
+ * p_i = softmax(x_i), log p_ic = (x_ic - max_i) - logf(sum_i) in float32, H_i = -sum_c p_ic log p_ic.  Then, summed in fp64:
+ *   ent     = sum_i H_i / (n ln C)                      the normalised entropy, in [0, 1];
+ *   mass_c  = (1 / n) sum_i p_ic                        the batch-mean prediction;
+ *   div     = sum_c mass_c (ln mass_c - ln pi_c) / ln C  = KL(mass || pi) / ln C >= 0; a class with mass_c == 0 contributes 0.
+ * prior: pi, fp32 [C] on the device, positive and summing to 1 (the caller's duty); NULL = uniform.  n == 0: ent = div = 0,
+ * mass = 0 and an all-zero gradient.  Outputs of the forward: stats[2] = ent, div; mass[C]; count[1] = n, exact; aux[C + 1] =
+ * g_c = ln(mass_c / pi_c) (0 where mass_c == 0), then 1 / (n ln C) (0 when n == 0) - what the backward reads, so it needs no second
+ * statistics pass.  The backward writes every one of the N rows exactly once, rows [0, P) and uncounted rows as +0, counted rows
+ *   dlogits_ik = grad_out[0] * (-p_ik (log p_ik + H_i)) / (n ln C) + grad_out[1] * p_ik (g_k - sum_c p_ic g_c) / (n ln C);
+ * grad_out[2], aux are read on the device: no host read anywhere.  2 <= C <= 32, ld >= C, ld_d >= C, 0 <= P <= N, N * C < 2^31;
+ * anything else is refused before a launch.  N == 0 and P == N are legal (the forward then runs its one-workgroup finalise alone).
+ * Two launches forward (fp64 column sums and integer row counts per workgroup of a capped grid, then one workgroup that combines
+ * them in a fixed order), one backward.  No atomics, no workgroup waits for another: bit-stable run to run. */
+size_t mm_im_ws_bytes(void);
+int mm_im_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const float* prior, float* stats, float* mass,
+              int64_t* count, float* aux, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_im_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const float* aux, const float* grad_out, float* dlogits,
+              int ld_d, mm_stream_t stream);
 /* mean_i sum_c softmax(tgt)_ic (log softmax(tgt)_ic - log softmax(pred)_ic)  (EXP/train.py:157-184) */
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws,
               size_t ws_bytes, mm_stream_t stream);

@@ -117,6 +117,9 @@ _PROTOS = {
     "mm_lovasz_ws_bytes": (sz, [i64, i32]),
     "mm_lovasz_fwd": (i32, [vp, i32, i64, i32, vp, i64, i32, vp, vp, vp, vp, sz, vp]),
     "mm_lovasz_bwd": (i32, [vp, i32, i64, i32, vp, vp, vp, i32, vp]),
+    "mm_im_ws_bytes": (sz, []),
+    "mm_im_fwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mm_im_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, i32, vp]),
     "mm_kl_fwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, sz, vp]),
     "mm_kl_bwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, i32, vp]),
     "mm_lift_index_ws_bytes": (sz, [i64]),

@@ -3,7 +3,8 @@
 ``Loss(cfg)``; ``loss("segmentation", pred=, gt=)``; ``split_by_target()``; ``update_loss_params()`` behave as
 in the reference; ``cross_entropy`` (weighted, ignore_index -100, weighted-mean reduction = torch's
 ``F.cross_entropy`` default) and the cross-modal KL of train.py:157-184 run as single fused kernels; ``lovasz_softmax`` sorts its
-errors per class with the segmented radix sort of csrc/lovasz.hip.
+errors per class with the segmented radix sort of csrc/lovasz.hip; ``target_entropy`` (entropy minimisation and its diversity guard on
+unlabelled rows) runs on the row kernels of csrc/infomax.hip.
 """
 from __future__ import annotations
 
@@ -312,6 +313,107 @@ def lovasz_softmax(pred, gt, classes="present", ignore_index=-100):
         raise ValueError(f"{who}: gt is {got}, pred has {N} rows")
     gt = gt.to(device=pred.device, dtype=torch.int64).contiguous()
     return _LovaszFn.apply(pred, gt, 1 if classes == "all" else 0, int(ignore_index))
+
+
+class _TargetEntropyFn(torch.autograd.Function):
+    """Entropy and diversity of rows [first_row, N) of ``logits`` (csrc/infomax.hip): two forward launches leave both scalars, the
+    class mass, the row count and ``aux`` (ln(mass / prior) per class, 1 / (n ln C)); ONE backward launch writes the whole gradient
+    from both upstream gradients and ``aux``."""
+
+    @staticmethod
+    def forward(ctx, logits, first_row, prior):
+        _lib.require_cuda(logits, "pred")
+        L = _lib.lib()
+        ctx.in_dtype = logits.dtype
+        logits, ld = _row_pitched(logits)
+        N, C = logits.shape
+        dev = logits.device
+        stats, mass, aux = (torch.empty(k, dtype=F32, device=dev) for k in (2, C, C + 1))
+        count = torch.empty((), dtype=torch.int64, device=dev)
+        ws = _lib.workspace.get(int(L.mm_im_ws_bytes()), dev)
+        check(L.mm_im_fwd(ptr(logits), ld, N, first_row, C, ptr(prior), ptr(stats), ptr(mass), ptr(count), ptr(aux), ptr(ws), ws.numel(),
+                          stream()), "im_fwd")
+        ctx.save_for_backward(logits, aux)
+        ctx.args = (ld, first_row)
+        ctx.mark_non_differentiable(mass, count)
+        ctx.set_materialize_grads(False)  # else every backward fills a zero gradient for ``mass`` and for ``count``: two launches
+        return stats[0], stats[1], mass, count
+
+    @staticmethod
+    def backward(ctx, g0, g1, _mass, _count):
+        if g0 is None and g1 is None:
+            return None, None, None
+        if g0 is None or g1 is None:  # one of the two scalars did not enter the loss
+            g0, g1 = (torch.zeros_like(g1), g1) if g0 is None else (g0, torch.zeros_like(g0))
+        L = _lib.lib()
+        logits, aux = ctx.saved_tensors
+        ld, first_row = ctx.args
+        N, C = logits.shape
+        g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
+        d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
+            L.mm_im_bwd(ptr(logits), ld, N, first_row, C, ptr(aux), ptr(g), ptr(d), C, stream()), "im_bwd"))
+        return d, None, None
+
+
+_PRIOR_CACHE = {}  # (normalised prior, device) -> device tensor
+
+
+def class_prior(prior, who="target_entropy"):
+    """``prior`` (None, a sequence or a 1-D tensor of positive finite numbers) as a tuple of floats that sums to 1, or None."""
+    if prior is None:
+        return None
+    vals = prior.detach().tolist() if torch.is_tensor(prior) and prior.dim() == 1 else prior
+    ok = isinstance(vals, (list, tuple)) and len(vals) > 0 and all(
+        isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 < float(v) < float("inf") for v in vals)
+    if not ok:
+        raise ValueError(f"{who}: the prior must be None or a sequence / 1-D tensor of positive finite numbers, not {prior!r}")
+    total = sum(float(v) for v in vals)
+    return tuple(float(v) / total for v in vals)
+
+
+def _device_prior(prior, device):
+    """A normalised prior (``class_prior``) on ``device``: uploaded once per device (as ``_device_weight``: a pageable upload makes
+    the host wait for the stream)."""
+    if prior is None:
+        return None
+    key = (prior, device)
+    hit = _PRIOR_CACHE.get(key)
+    if hit is None:
+        if len(_PRIOR_CACHE) > 64:
+            _PRIOR_CACHE.clear()
+        hit = _PRIOR_CACHE[key] = torch.tensor(prior, dtype=torch.float64).to(F32).to(device)
+    return hit
+
+
+def target_entropy(pred, first_row=0, prior=None):
+    """``(ent, div, mass, count)`` of the rows ``[first_row, N)`` of ``pred`` [N, C] - the unlabelled target rows of a joined
+    [source | target] pass, or with ``first_row=0`` all rows.  Counted are the rows whose logits are all finite, ``count`` of them
+    (int64 device scalar).  ``ent``: the mean over them of the softmax entropy divided by ln C, in [0, 1] - entropy minimisation
+    (MinEnt, Vu et al., CVPR 2019).  ``mass`` (fp32 [C]): their mean softmax.  ``div`` = KL(mass || prior) / ln C >= 0, the
+    diversity term of information maximisation (SHOT, Liang et al., ICML 2020), which keeps ``ent`` from collapsing onto the
+    majority class; ``prior``: None = uniform, or C positive finite numbers (a sequence or a tensor; normalised to sum 1 on the
+    host and cached per device - pass a sequence in a training loop, a device tensor is read back on every call).  Nothing counted:
+    both losses 0, ``mass`` 0, a zero gradient.
+
+    ``ent`` and ``div`` are differentiable, one autograd node and one backward launch write the whole gradient of ``pred`` (zero
+    rows before ``first_row``); ``mass`` and ``count`` are detached.  ``mass`` is the mean over THIS call's rows: under data
+    parallelism each rank's own batch mean, as batch-norm statistics are, not reduced over ranks.  ``pred`` may be fp16, bf16 or a
+    row-pitched view (``stride(1) == 1``), which is read in place.  Bit-stable run to run."""
+    who = "target_entropy"
+    if not torch.is_tensor(pred) or pred.dim() != 2:
+        raise ValueError(f"{who}: pred must be [N, C]")
+    N, C = int(pred.shape[0]), int(pred.shape[1])
+    if not 2 <= C <= 32:
+        raise ValueError(f"{who}: {C} classes, the row kernels take 2 to 32")
+    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
+        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
+    if N * C >= 1 << 31:
+        raise ValueError(f"{who}: {N} rows of {C} classes, N * C must stay below 2^31")
+    prior = class_prior(prior, who)
+    if prior is not None and len(prior) != C:
+        raise ValueError(f"{who}: the prior has {len(prior)} entries for C = {C} classes")
+    _lib.require_cuda(pred, "pred")
+    return _TargetEntropyFn.apply(pred, first_row, _device_prior(prior, pred.device))
 
 
 class _KLFn(torch.autograd.Function):

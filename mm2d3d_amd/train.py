@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, domains
+from . import _lib, domains, infomax
 from .ddp import GradAllReducer, ranks_share_a_gpu
 from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
@@ -118,6 +118,8 @@ class TrainModel(nn.Module):
         self.overlap_branches = int(train_kwargs.get("overlap_branches", os.environ.get("MM_OVERLAP_BRANCHES", "0")))
         # self-training (``lambda_pl``, ``pseudo_label*``, ``pl_*``): selftrain.SelfTraining owns options and state; forwarded below the class
         self.selftrain = SelfTraining(train_kwargs, self.ema_decay, self.overlap_metadata, self.overlap_branches)
+        # entropy / diversity terms on the target rows (``lambda_minent``, ``lambda_div``, ``div_prior``): infomax.TargetEntropy, forwarded too
+        self.target_entropy = infomax.TargetEntropy(train_kwargs)
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -217,7 +219,8 @@ class TrainModel(nn.Module):
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
-        st = self.selftrain
+        st, te = self.selftrain, self.target_entropy
+        te.begin_step(self)
         teacher = st.lambda_pl > 0 and st.pseudo_label_source == "teacher"
         pseudo = st.batch_targets(trg) if st.lambda_pl > 0 and not teacher else None
         if self._can_join(src, trg):
@@ -309,6 +312,7 @@ class TrainModel(nn.Module):
                     _, _, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo)
             xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
+            im = te.terms(l2d, l3d, P)
         else:
             if teacher:
                 own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
@@ -325,6 +329,7 @@ class TrainModel(nn.Module):
                                                aux3d["seg_logit_point"])
             if pseudo is not None:
                 _, _, pl2d, pl3d = st.losses(p2d["seg_logit"], p3d["seg_logit"], 0, pseudo)
+            im = te.terms(p2d["seg_logit"], p3d["seg_logit"], 0)
         self.last_logs = {
             f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
@@ -336,6 +341,8 @@ class TrainModel(nn.Module):
             loss_2d = loss_2d + st.lambda_pl * pl2d
             loss_3d = loss_3d + st.lambda_pl * pl3d
             st.log(self.last_logs, stage, pl2d, pl3d, trg["x"][0].shape[0])
+        if im is not None:
+            loss_2d, loss_3d = te.add(self.last_logs, stage, loss_2d, loss_3d, im)
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
@@ -655,6 +662,7 @@ class TrainModel(nn.Module):
         return loss
 
 
-for _name in FORWARDED:  # trainer.lambda_pl, ..., trainer.last_teacher: read and assigned on the policy object
-    setattr(TrainModel, _name, property(lambda self, n=_name: getattr(self.selftrain, n),
-                                        lambda self, value, n=_name: setattr(self.selftrain, n, value)))
+for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED)):
+    for _name in _names:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
+        setattr(TrainModel, _name, property(lambda self, n=_name, o=_owner: getattr(getattr(self, o), n),
+                                            lambda self, value, n=_name, o=_owner: setattr(getattr(self, o), n, value)))
