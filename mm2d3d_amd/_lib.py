@@ -460,6 +460,17 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def row_pitched(t):
+    """``(t, pitch)``: ``[N, C]`` as the fp32 tensor the row kernels read in place, and its row pitch in elements.  A row-pitched
+    view (``stride(1) == 1``) stays as it is; one row has no pitch to check (its pitch is C); anything else is copied."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    N, C = t.shape
+    if t.stride(1) != 1 or (N > 1 and t.stride(0) < C):
+        t = t.contiguous()
+    return t, (t.stride(0) if N > 1 else C)
+
+
 class _Workspace:
     """Grow-only scratch buffers, one per (device, slot, current stream): every kernel that uses a buffer is enqueued on the
     stream the buffer belongs to, so the stream's own order serialises them (ops run on the current

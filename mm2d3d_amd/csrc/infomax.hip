@@ -3,22 +3,22 @@
 //   mm_im_fwd   k_im_stats: a capped grid walks the 128-row tiles of the target rows, staged through LDS (stage_rows of rows.h).  A
 //               lane that kept 1 + C accumulators indexed by a runtime c would spill them, so each lane writes its row's softmax back
 //               INTO the staged tile (zeros for a row that is not counted) and its entropy into ent[]; then thread j sums column j
-//               over the tile's rows in ascending order into ONE fp64 accumulator that it carries across the workgroup's tiles - the
-//               shape of k_pl_stats (pselab.hip).  Row counts are ballots, integers throughout.
-//               k_im_final: one workgroup sums the <= IM_MAX_WG partials per quantity (a wave per quantity, lanes striding the
-//               workgroups, then the shuffle tree: a fixed order) and writes the two losses, the class mass, the count and what the
-//               backward reads.
+//               over the tile's rows in ascending order into ONE fp64 accumulator that it carries across the workgroup's tiles
+//               (col_sum of rows.h).  Row counts are ballots, integers throughout (wave_count, block_count).
+//               k_im_final: one workgroup of ROWS_FT threads sums the <= ROWS_MAX_WG partials per quantity (sum_partial
+//               of rows.h: a wave per quantity, sixteen waves share the 1 + C sums and the count) and writes the two
+//               losses, the class mass, the count and what the backward reads.
+//               The walk, the finish and the workspace (stats_ws) are those of k_pl_stats / k_pl_update (pselab.hip).
 //   mm_im_bwd   k_im_bwd: one 128-row tile per workgroup, staged the same way; each lane forms its gradient row in place, the
-//               workgroup writes the tile out with consecutive lanes on consecutive addresses.  Tiles of head rows alone write zeros.
+//               workgroup writes the tile out with consecutive lanes on consecutive addresses (unstage_rows).  Tiles of head rows
+//               alone write zeros.
 // No atomics of any kind, no grid barrier, no workgroup waits for another: bit-stable run to run.
 #include "common.h"
 #include "pointpred.h"
 #include "rows.h"
 
 namespace {
-constexpr int PT = 128;          // rows per tile = threads per workgroup
-constexpr int IM_MAX_WG = 1024;  // workgroups of the statistics pass = partials per quantity
-constexpr int IM_FT = 1024;      // threads of the finalise kernel: sixteen waves share the 1 + C sums and the count
+constexpr int PT = 128;  // rows per tile = threads per workgroup
 constexpr int MAXC = MM_PRED_MAXC;
 constexpr float F32_MAX = 3.402823466e38f;
 
@@ -37,17 +37,16 @@ __global__ __launch_bounds__(PT) void k_im_stats(const float* __restrict__ logit
   float* ent = tile + PT * pitch;
   const int K = C + 1, j = (int)threadIdx.x;  // the column this thread sums (threads < K): C masses, then the entropy
   double acc = 0.0;
-  unsigned n = 0;  // per wave: every lane holds the wave's count (N * C < 2^31: below 2^30 rows)
+  unsigned wn[1] = {0};  // per wave: every lane holds the wave's count (N * C < 2^31: below 2^30 rows)
   const int64_t T = N - P;
   const unsigned ntiles = (unsigned)((T + PT - 1) / PT);
   for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int64_t row0 = P + (int64_t)t * PT;
-    const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
+    const RowTile tl = row_tile<PT>(t, N, P);
     __syncthreads();  // the previous tile's columns have been summed
-    stage_rows<PT>(tile, logits + row0 * ld, ld, rows, C, pitch);
+    stage_rows<PT>(tile, logits + tl.row0 * ld, ld, tl.rows, C, pitch);
     __syncthreads();
     bool counted = false;
-    if ((int)threadIdx.x < rows) {
+    if ((int)threadIdx.x < tl.rows) {
       float* a = tile + threadIdx.x * pitch;
       counted = row_finite(a, C);
       const RowLse r = row_lse(a, C);
@@ -61,47 +60,33 @@ __global__ __launch_bounds__(PT) void k_im_stats(const float* __restrict__ logit
       }
       ent[threadIdx.x] = counted ? h : 0.f;
     }
-    n += (unsigned)__popcll(__ballot(counted));
+    wn[0] += wave_count(counted);
     __syncthreads();
     if (j < K) {
-      if (j == C) {
-        for (int r = 0; r < rows; r++) acc += (double)ent[r];
-      } else {
-        const float* q = tile + j;
-        for (int r = 0; r < rows; r++) acc += (double)q[r * pitch];
-      }
+      if (j == C) col_sum(acc, ent, 1, tl.rows);
+      else col_sum(acc, tile + j, pitch, tl.rows);
     }
   }
   if (j < K) psum[(int64_t)blockIdx.x * K + j] = acc;
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long long s = 0;
-    for (int w = 0; w < PT / 64; w++) s += (long long)wcnt[w];
-    pcnt[blockIdx.x] = s;
-  }
+  const long long n = block_count<PT>(wn, wcnt);
+  if (threadIdx.x == 0) pcnt[blockIdx.x] = n;
 }
 
 // stats[2] = ent, div; mass[C]; count[1] = n; aux[C + 1] = g_c = ln(mass_c / pi_c) (0 where mass_c == 0), then 1 / (n ln C)
 // (0 when n == 0): what k_im_bwd reads.  prior == NULL: pi_c = 1 / C.
-__global__ __launch_bounds__(IM_FT) void k_im_final(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nb, int C,
+__global__ __launch_bounds__(ROWS_FT) void k_im_final(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nb, int C,
                                                      const float* __restrict__ prior, float* __restrict__ stats, float* __restrict__ mass,
                                                      int64_t* __restrict__ count, float* __restrict__ aux) {
   __shared__ double tot[MAXC + 1];
   __shared__ double term[MAXC];
   __shared__ long long cnt;
   const int K = C + 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int q = wave; q < K + 1; q += IM_FT / 64) {  // uniform per wave
+  for (int q = wave; q < K + 1; q += ROWS_FT / 64) {  // uniform per wave
     if (q < K) {
-      double v = 0.0;
-      for (int i = lane; i < nb; i += 64) v += psum[(int64_t)i * K + q];
-      v = wave_sum64(v);
+      const double v = sum_partial(psum, nb, K, q, lane);
       if (lane == 0) tot[q] = v;
     } else {
-      long long s = 0;
-      for (int i = lane; i < nb; i += 64) s += pcnt[i];
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+      const long long s = sum_partial(pcnt, nb, 1, 0, lane);
       if (lane == 0) cnt = s;
     }
   }
@@ -136,21 +121,18 @@ __global__ __launch_bounds__(PT) void k_im_bwd(const float* __restrict__ logits,
   extern __shared__ float tile[];  // [PT][pitch]
   __shared__ float gs[MAXC + 1];
   const int pitch = C | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * PT;
-  const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
-  if (row0 + rows <= P) {  // uniform: head rows alone
-    for (int e = threadIdx.x; e < rows * C; e += PT) {
-      const int r = e / C, c = e - r * C;
-      dl[(row0 + r) * ld_d + c] = 0.f;
-    }
+  const RowTile t = row_tile<PT>(blockIdx.x, N);
+  float* out = dl + t.row0 * ld_d;
+  if (t.row0 + t.rows <= P) {  // uniform: head rows alone
+    unstage_rows<PT, true>(out, ld_d, tile, t.rows, C, pitch);
     return;
   }
   if ((int)threadIdx.x <= C) gs[threadIdx.x] = aux[threadIdx.x];
-  stage_rows<PT>(tile, logits + row0 * ld, ld, rows, C, pitch);
+  stage_rows<PT>(tile, logits + t.row0 * ld, ld, t.rows, C, pitch);
   __syncthreads();
-  if ((int)threadIdx.x < rows) {
+  if ((int)threadIdx.x < t.rows) {
     float* a = tile + threadIdx.x * pitch;
-    const bool counted = row0 + threadIdx.x >= P && row_finite(a, C);
+    const bool counted = t.row0 + threadIdx.x >= P && row_finite(a, C);
     if (counted) {
       const float scale = gs[C], g0 = gout[0], g1 = gout[1];
       const RowLse r = row_lse(a, C);
@@ -174,13 +156,8 @@ __global__ __launch_bounds__(PT) void k_im_bwd(const float* __restrict__ logits,
     }
   }
   __syncthreads();
-  for (int e = threadIdx.x; e < rows * C; e += PT) {
-    const int r = e / C, c = e - r * C;
-    dl[(row0 + r) * ld_d + c] = tile[r * pitch + c];
-  }
+  unstage_rows<PT>(out, ld_d, tile, t.rows, C, pitch);
 }
-
-inline size_t im_psum_bytes() { return mm_align((size_t)IM_MAX_WG * (MAXC + 1) * sizeof(double)); }
 
 int im_check(const char* who, const float* logits, int ld, int64_t N, int64_t P, int C) {
   MM_CHECK_ARG(C >= 2 && C <= MAXC, "%s: C must lie in [2, 32]", who);
@@ -194,25 +171,24 @@ int im_check(const char* who, const float* logits, int ld, int64_t N, int64_t P,
 
 extern "C" {
 
-size_t mm_im_ws_bytes() { return im_psum_bytes() + mm_align((size_t)IM_MAX_WG * sizeof(long long)); }
+size_t mm_im_ws_bytes() { return stats_ws(nullptr, MAXC + 1, 1).bytes; }
 
 int mm_im_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const float* prior, float* stats, float* mass, int64_t* count,
               float* aux, void* ws, size_t ws_bytes, hipStream_t s) {
-  static_assert(MAXC + 1 <= PT && MAXC + 2 <= IM_FT && PT % 64 == 0, "one thread per column, counts per 64-lane wave");
+  static_assert(MAXC + 1 <= PT && MAXC + 2 <= ROWS_FT, "one thread per column");
   if (int rc = im_check("im_fwd", logits, ld, N, P, C)) return rc;
   MM_CHECK_ARG(stats && mass && count && aux, "im_fwd: null stats, mass, count or aux");
   MM_CHECK_ARG(ws && ws_bytes >= mm_im_ws_bytes(), "im_fwd: workspace missing or too small");
-  double* psum = (double*)ws;
-  long long* pcnt = (long long*)((char*)ws + im_psum_bytes());
+  const StatsWs w = stats_ws(ws, MAXC + 1, 1);
   const int64_t nt = mm_cdiv(N - P, PT);
-  const int nb = (int)(nt > IM_MAX_WG ? IM_MAX_WG : nt);
+  const int nb = (int)(nt > ROWS_MAX_WG ? ROWS_MAX_WG : nt);
   if (nb > 0) {
     const size_t lds = ((size_t)PT * (C | 1) + PT) * sizeof(float);  // <= 17.4 KB
-    hipLaunchKernelGGL(k_im_stats, dim3(nb), dim3(PT), lds, s, logits, ld, N, P, C, psum, pcnt);
+    hipLaunchKernelGGL(k_im_stats, dim3(nb), dim3(PT), lds, s, logits, ld, N, P, C, w.psum, w.pcnt);
     MM_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_im_final, dim3(1), dim3(IM_FT), 0, s, (const double*)psum, (const long long*)pcnt, nb, C, prior, stats, mass, count,
-                     aux);
+  hipLaunchKernelGGL(k_im_final, dim3(1), dim3(ROWS_FT), 0, s, (const double*)w.psum, (const long long*)w.pcnt, nb, C, prior, stats, mass,
+                     count, aux);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

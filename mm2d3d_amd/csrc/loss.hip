@@ -107,15 +107,33 @@ __global__ __launch_bounds__(T) void k_ce_bwd(const float* __restrict__ logits, 
 constexpr int ST = 64;          // rows per tile = lanes of the one wave
 constexpr int S_MAX_PART = 2048;
 
-// sum_c softmax(t * inv_t)_c * v_c over one teacher row (tm = its maximum), v_c = lse - x_c
+// The softened teacher distribution of one teacher row t (tm = its maximum): q_c = soft_e(c) / sum_c soft_e(c), the sum
+// ascending in c.  The forward and the backward form q from this one expression.
+__device__ __forceinline__ float soft_e(const float* t, int c, float tm, float inv_t) { return expf((t[c] - tm) * inv_t); }
+
+// sum_c q_c * v_c over one teacher row, v_c = lse - x_c
 __device__ inline float soft_dot(const float* t, float tm, float inv_t, const float* x, float lse, int C) {
   float s = 0.f, n = 0.f;
   for (int c = 0; c < C; c++) {
-    const float e = expf((t[c] - tm) * inv_t);
+    const float e = soft_e(t, c, tm, inv_t);
     s += e;
     n += e * (lse - x[c]);
   }
   return n / s;
+}
+
+// The tile of k_ce2s_*: tile = [HAS_B ? 3 : 2][ST][pitch] holds the logits rows and, for the tail rows [h, rows) alone, the teacher
+// rows (row0 + r - P) at the same r; h = tile_head(P, row0, rows).  The caller synchronises.
+template <bool HAS_B>
+__device__ __forceinline__ void stage_ce2s(float* tile, const RowTile& t, int h, int64_t P, int C, int pitch,
+                                           const float* __restrict__ logits, int ld, const float* __restrict__ ta, int ld_a,
+                                           const float* __restrict__ tb, int ld_b) {
+  stage_rows<ST>(tile, logits + t.row0 * ld, ld, t.rows, C, pitch);
+  if (h < t.rows) {
+    const int64_t t0 = t.row0 + h - P;
+    stage_rows<ST>(tile + (ST + h) * pitch, ta + t0 * ld_a, ld_a, t.rows - h, C, pitch);
+    if (HAS_B) stage_rows<ST>(tile + (2 * ST + h) * pitch, tb + t0 * ld_b, ld_b, t.rows - h, C, pitch);
+  }
 }
 
 // partial[b] = (sum w*nll, sum w) of the head, (sum of the kept rows' soft cross entropies, kept rows) of the tail
@@ -133,17 +151,11 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
   long long k1 = 0;
   const int64_t ntiles = (N + ST - 1) / ST;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int64_t row0 = t * ST;
-    const int rows = (int)((N - row0) < (int64_t)ST ? (N - row0) : (int64_t)ST);
-    // the tile's tail rows are [h, rows): teacher row (row0 + r - P)
-    const int h = (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
+    const RowTile tl = row_tile<ST>(t, N);
+    const int64_t row0 = tl.row0;
+    const int rows = tl.rows, h = tile_head(P, row0, rows);
     __syncthreads();  // the previous tile's rows have been read
-    stage_rows<ST>(sx, logits + row0 * ld, ld, rows, C, pitch);
-    if (h < rows) {
-      const int64_t t0 = row0 + h - P;
-      stage_rows<ST>(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
-      if (HAS_B) stage_rows<ST>(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
-    }
+    stage_ce2s<HAS_B>(tile, tl, h, P, C, pitch, logits, ld, ta, ld_a, tb, ld_b);
     __syncthreads();
     const int r = threadIdx.x;
     const float* x = sx + r * pitch;
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
       }
     }
   }
-  const double a0 = wave_sum64(sl0), b0 = wave_sum64(sw0), a1 = wave_sum64(sl1), b1 = wave_sum64((double)k1);
+  const double a0 = wave_sum(sl0), b0 = wave_sum(sw0), a1 = wave_sum(sl1), b1 = wave_sum((double)k1);
   if (threadIdx.x == 0) {
     double* o = partial + 4 * (int64_t)blockIdx.x;
     o[0] = a0, o[1] = b0, o[2] = a1, o[3] = b1;
@@ -209,15 +221,10 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
   float* sx = tile;
   float* sa = tile + ST * pitch;
   float* sb = tile + 2 * ST * pitch;
-  const int64_t row0 = (int64_t)blockIdx.x * ST;
-  const int rows = (int)((N - row0) < (int64_t)ST ? (N - row0) : (int64_t)ST);
-  const int h = (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
-  stage_rows<ST>(sx, logits + row0 * ld, ld, rows, C, pitch);
-  if (h < rows) {
-    const int64_t t0 = row0 + h - P;
-    stage_rows<ST>(sa + h * pitch, ta + t0 * ld_a, ld_a, rows - h, C, pitch);
-    if (HAS_B) stage_rows<ST>(sb + h * pitch, tb + t0 * ld_b, ld_b, rows - h, C, pitch);
-  }
+  const RowTile tl = row_tile<ST>(blockIdx.x, N);
+  const int64_t row0 = tl.row0;
+  const int rows = tl.rows, h = tile_head(P, row0, rows);
+  stage_ce2s<HAS_B>(tile, tl, h, P, C, pitch, logits, ld, ta, ld_a, tb, ld_b);
   __syncthreads();
   const int r = threadIdx.x;
   if (r < rows) {
@@ -250,25 +257,21 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
       } else {
         const float ma = a[pr.ia];
         float za = 0.f, zb = 1.f, mb = 0.f;
-        for (int c = 0; c < C; c++) za += expf((a[c] - ma) * inv_t);
+        for (int c = 0; c < C; c++) za += soft_e(a, c, ma, inv_t);
         if (HAS_B) {
           mb = b[pr.ib], zb = 0.f;
-          for (int c = 0; c < C; c++) zb += expf((b[c] - mb) * inv_t);
+          for (int c = 0; c < C; c++) zb += soft_e(b, c, mb, inv_t);
         }
         for (int c = 0; c < C; c++) {
-          float q = expf((a[c] - ma) * inv_t) / za;
-          if (HAS_B) q = 0.5f * (q + expf((b[c] - mb) * inv_t) / zb);
+          float q = soft_e(a, c, ma, inv_t) / za;
+          if (HAS_B) q = 0.5f * (q + soft_e(b, c, mb, inv_t) / zb);
           x[c] = k * (expf(x[c] - m) * inv - q);
         }
       }
     }
   }
   __syncthreads();
-  float* d = dlogits + row0 * ld_d;
-  for (int e = threadIdx.x; e < rows * C; e += ST) {
-    const int rr = e / C, c = e - rr * C;
-    d[(int64_t)rr * ld_d + c] = sx[rr * pitch + c];
-  }
+  unstage_rows<ST>(dlogits + row0 * ld_d, ld_d, sx, rows, C, pitch);
 }
 
 // partial[b] = sum_i sum_c q_ic (log q_ic - log p_ic)

@@ -9,6 +9,9 @@
 //                       most-significant-digit radix select (four 8-bit passes over the order-preserving uint32 image of the
 //                       floats), threshold min(median, 0.9f), labels below it become ignore_label
 // Counts are integers and are summed with integer atomics: the result does not depend on the order of the additions.
+// The tile geometry, the staging, the counted rows of a workgroup, the column sums of a staged tile, the one-workgroup finish and
+// the workspace of the statistics pass are rows.h's (row_tile, stage_rows, wave_count / block_count, col_sum, sum_partial,
+// stats_ws), shared with infomax.hip and loss.hip: the kernels here hold what is particular to each.
 #include "common.h"
 #include "pointpred.h"
 #include "rows.h"
@@ -20,7 +23,14 @@ constexpr int RADIX = 256;   // 8 bits per pass
 constexpr int MAX_BLOCKS = 2048;
 
 // ---- prediction.  The [rows, C] blocks of both logit matrices go through LDS (stage_rows of rows.h: coalesced copies, then each
-// lane reads its own row, pitched to an odd number of words).
+// lane reads its own row, pitched to an odd number of words): tile = [HAS3 ? 2 : 1][PT][pitch].  The caller synchronises.
+template <bool HAS3 = true>
+__device__ __forceinline__ void stage_pair(float* tile, const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3,
+                                           const RowTile& t, int C, int pitch) {
+  stage_rows<PT>(tile, l2 + t.row0 * ld2, ld2, t.rows, C, pitch);
+  if (HAS3) stage_rows<PT>(tile + PT * pitch, l3 + t.row0 * ld3, ld3, t.rows, C, pitch);
+}
+
 template <bool HAS3>
 __global__ __launch_bounds__(PT) void k_pselab_predict(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3,
                                                         int64_t N, int C, float* __restrict__ p2, uint8_t* __restrict__ y2,
@@ -28,16 +38,14 @@ __global__ __launch_bounds__(PT) void k_pselab_predict(const float* __restrict__
                                                         uint8_t* __restrict__ ye) {
   extern __shared__ float tile[];  // [HAS3 ? 2 : 1][PT][pitch]
   const int pitch = C | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * PT;
-  const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
+  const RowTile t = row_tile<PT>(blockIdx.x, N);
   float* ta = tile;
   float* tb = tile + PT * pitch;
-  stage_rows<PT>(ta, l2 + row0 * ld2, ld2, rows, C, pitch);
-  if (HAS3) stage_rows<PT>(tb, l3 + row0 * ld3, ld3, rows, C, pitch);
+  stage_pair<HAS3>(tile, l2, ld2, l3, ld3, t, C, pitch);
   __syncthreads();
-  if ((int)threadIdx.x >= rows) return;
+  if ((int)threadIdx.x >= t.rows) return;
   const MMPointPred r = mm_point_predict<HAS3>(ta + threadIdx.x * pitch, tb + threadIdx.x * pitch, C);
-  const int64_t i = row0 + threadIdx.x;
+  const int64_t i = t.row0 + threadIdx.x;
   p2[i] = r.pa;
   y2[i] = (uint8_t)r.ia;
   if (HAS3) {
@@ -63,38 +71,29 @@ __global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__
   __shared__ float th[CLS ? 2 * MM_PRED_MAXC : 1];
   if (CLS && (int)threadIdx.x < 2 * C) th[threadIdx.x] = thr_cls[threadIdx.x];
   const int pitch = C | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * PT;
-  const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
+  const RowTile t = row_tile<PT>(blockIdx.x, N);
   float* ta = tile;
   float* tb = tile + PT * pitch;
-  stage_rows<PT>(ta, l2 + row0 * ld2, ld2, rows, C, pitch);
-  stage_rows<PT>(tb, l3 + row0 * ld3, ld3, rows, C, pitch);
+  stage_pair(tile, l2, ld2, l3, ld3, t, C, pitch);
   __syncthreads();
   bool k2 = false, k3 = false;
-  if ((int)threadIdx.x < rows) {
+  if ((int)threadIdx.x < t.rows) {
     const MMPointPred r = mm_point_predict<true>(ta + threadIdx.x * pitch, tb + threadIdx.x * pitch, C);
     const float pa = ENS ? r.pe : r.pa, pb = ENS ? r.pe : r.pb;
     const int ia = ENS ? r.ie : r.ia, ib = ENS ? r.ie : r.ib;
     k2 = CLS ? pa >= th[ia] : (thr < 0.f || pa >= thr);
     k3 = CLS ? pb >= th[C + ib] : (thr < 0.f || pb >= thr);
-    const int64_t i = row0 + threadIdx.x;
+    const int64_t i = t.row0 + threadIdx.x;
     y2[i] = k2 ? (int64_t)ia : ignore;
     y3[i] = k3 ? (int64_t)ib : ignore;
     if (p2) p2[i] = pa;
     if (p3) p3[i] = pb;
   }
   if (!kept) return;  // uniform
-  const unsigned n2 = (unsigned)__popcll(__ballot(k2)), n3 = (unsigned)__popcll(__ballot(k3));
+  const unsigned wn[2] = {wave_count(k2), wave_count(k3)};
   __syncthreads();  // every lane has read its rows
-  unsigned* cnt = (unsigned*)tile;  // [PT / 64][2]
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) cnt[2 * wave] = n2, cnt[2 * wave + 1] = n3;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned n = 0;
-    for (int w = 0; w < PT / 64; w++) n += cnt[2 * w + threadIdx.x];
-    if (n) atomicAdd(&kept[threadIdx.x], (unsigned long long)n);
-  }
+  const long long n = block_count<PT>(wn, (unsigned*)tile);
+  if (n) atomicAdd(&kept[threadIdx.x], (unsigned long long)n);  // n != 0: thread 0 or 1
 }
 
 // ---- self-adaptive per-class thresholds (mm_pl_adapt; include/mm2d3d.h has the definition).  Per output o the state is tau_o
@@ -102,18 +101,17 @@ __global__ __launch_bounds__(PT) void k_teacher_labels(const float* __restrict__
 // k_pl_stats: a capped grid walks the 128-row tiles, staged as in k_teacher_labels.  A lane that kept 2 * (1 + C) accumulators
 // indexed by a runtime c would spill them, so each lane writes its row's q values back INTO the staged tile (zeros for a row that
 // is not counted) and its confidences into conf[]; then thread (o, j) sums column j of output o over the tile's rows in ascending
-// order into ONE fp64 accumulator that it carries across the workgroup's tiles.  Row counts are ballots, integers throughout.
-// k_pl_update: one workgroup sums the <= PL_MAX_WG partials per quantity (a wave per quantity, lanes striding the workgroups,
-// then the shuffle tree: a fixed order), applies the update in place and writes the thresholds.  No atomics of any kind.
-constexpr int PL_MAX_WG = 1024;  // workgroups of the statistics pass = partials per quantity
-constexpr int PL_UT = 1024;      // threads of the update kernel: sixteen waves share the 2 * (1 + C) + 2 quantities
-
+// order into ONE fp64 accumulator that it carries across the workgroup's tiles (col_sum of rows.h).  Row counts are ballots,
+// integers throughout (wave_count, block_count).
+// k_pl_update: one workgroup of ROWS_FT threads sums the <= ROWS_MAX_WG partials per quantity (sum_partial of rows.h:
+// a wave per quantity, sixteen waves share the 2 * (1 + C) + 2 quantities), applies the update in place and writes the
+// thresholds.  No atomics of any kind.  The walk, the finish and the workspace (stats_ws) are those of infomax.hip.
 template <bool ENS>
 __global__ __launch_bounds__(PT) void k_pl_stats(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3, int64_t N,
                                                   int C, double* __restrict__ psum /*[grid][2][1 + C]*/,
                                                   long long* __restrict__ pcnt /*[grid][2]*/) {
   extern __shared__ float tile[];  // [2][PT][pitch], then conf [2][PT]
-  __shared__ unsigned wcnt[PT / 64][2];
+  __shared__ unsigned wcnt[PT / 64 * 2];
   const int pitch = C | 1;
   float* ta = tile;
   float* tb = tile + PT * pitch;
@@ -121,17 +119,15 @@ __global__ __launch_bounds__(PT) void k_pl_stats(const float* __restrict__ l2, i
   const int K = 1 + C;
   const int o = (int)threadIdx.x / K, j = (int)threadIdx.x - o * K;  // the column this thread sums (threads < 2 * K)
   double acc = 0.0;
-  unsigned n2 = 0, n3 = 0;  // per wave: every lane holds the wave's counts (a workgroup sees at most 2^28 rows: mm_pl_adapt)
+  unsigned wn[2] = {0, 0};  // per wave: every lane holds the wave's counts (a workgroup sees at most 2^28 rows: mm_pl_adapt)
   const unsigned ntiles = (unsigned)((N + PT - 1) / PT);  // <= 2^31 - 1 (mm_pl_adapt), so t + gridDim.x does not wrap
   for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int64_t row0 = (int64_t)t * PT;
-    const int rows = (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT);
+    const RowTile tl = row_tile<PT>(t, N);
     __syncthreads();  // the previous tile's columns have been summed
-    stage_rows<PT>(ta, l2 + row0 * ld2, ld2, rows, C, pitch);
-    stage_rows<PT>(tb, l3 + row0 * ld3, ld3, rows, C, pitch);
+    stage_pair(tile, l2, ld2, l3, ld3, tl, C, pitch);
     __syncthreads();
     bool k2 = false, k3 = false;
-    if ((int)threadIdx.x < rows) {
+    if ((int)threadIdx.x < tl.rows) {
       float* a = ta + threadIdx.x * pitch;
       float* b = tb + threadIdx.x * pitch;
       const MMPointPred r = mm_point_predict<true>(a, b, C);
@@ -156,49 +152,34 @@ __global__ __launch_bounds__(PT) void k_pl_stats(const float* __restrict__ l2, i
       conf[threadIdx.x] = k2 ? pa : 0.f;
       conf[PT + threadIdx.x] = k3 ? pb : 0.f;
     }
-    n2 += (unsigned)__popcll(__ballot(k2));
-    n3 += (unsigned)__popcll(__ballot(k3));
+    wn[0] += wave_count(k2);
+    wn[1] += wave_count(k3);
     __syncthreads();
     if ((int)threadIdx.x < 2 * K) {
-      if (j == 0) {
-        const float* p = conf + o * PT;
-        for (int r = 0; r < rows; r++) acc += (double)p[r];
-      } else {
-        const float* q = (o ? tb : ta) + (j - 1);
-        for (int r = 0; r < rows; r++) acc += (double)q[r * pitch];
-      }
+      if (j == 0) col_sum(acc, conf + o * PT, 1, tl.rows);
+      else col_sum(acc, (o ? tb : ta) + (j - 1), pitch, tl.rows);
     }
   }
   if ((int)threadIdx.x < 2 * K) psum[(int64_t)blockIdx.x * 2 * K + threadIdx.x] = acc;
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][0] = n2, wcnt[threadIdx.x >> 6][1] = n3;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    long long n = 0;
-    for (int w = 0; w < PT / 64; w++) n += (long long)wcnt[w][threadIdx.x];
-    pcnt[(int64_t)blockIdx.x * 2 + threadIdx.x] = n;
-  }
+  const long long n = block_count<PT>(wn, wcnt);
+  if (threadIdx.x < 2) pcnt[(int64_t)blockIdx.x * 2 + threadIdx.x] = n;
 }
 
 // state[2][1 + C] = (tau_o, pt_o[c]), count[2] = updates taken, thr[2][C] = float((pt_o[c] / max_c pt_o[c]) * tau_o) in fp64.
 // An output without counted rows keeps its state and its count; its thresholds are written all the same.
-__global__ __launch_bounds__(PL_UT) void k_pl_update(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nb, int C,
+__global__ __launch_bounds__(ROWS_FT) void k_pl_update(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nb, int C,
                                                       double momentum, int warmup, double* __restrict__ state,
                                                       int64_t* __restrict__ count, float* __restrict__ thr) {
   __shared__ double tot[2 * (1 + MM_PRED_MAXC)];
   __shared__ long long cnt[2];
   __shared__ double cur[2 * (1 + MM_PRED_MAXC)];
   const int K = 1 + C, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int q = wave; q < 2 * K + 2; q += PL_UT / 64) {  // uniform per wave
+  for (int q = wave; q < 2 * K + 2; q += ROWS_FT / 64) {  // uniform per wave
     if (q < 2 * K) {
-      double v = 0.0;
-      for (int i = lane; i < nb; i += 64) v += psum[(int64_t)i * 2 * K + q];
-      v = wave_sum64(v);
+      const double v = sum_partial(psum, nb, 2 * K, q, lane);
       if (lane == 0) tot[q] = v;
     } else {
-      long long n = 0;
-      for (int i = lane; i < nb; i += 64) n += pcnt[2 * i + (q - 2 * K)];
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d, 64);
+      const long long n = sum_partial(pcnt, nb, 2, q - 2 * K, lane);
       if (lane == 0) cnt[q - 2 * K] = n;
     }
   }
@@ -414,13 +395,11 @@ int mm_teacher_labels_cls(const float* logits2d, int ld2, const float* logits3d,
                         label_3d, prob_2d, prob_3d, kept, s);
 }
 
-size_t mm_pl_adapt_ws_bytes() {
-  return mm_align((size_t)PL_MAX_WG * 2 * (1 + MM_PRED_MAXC) * sizeof(double)) + mm_align((size_t)PL_MAX_WG * 2 * sizeof(long long));
-}
+size_t mm_pl_adapt_ws_bytes() { return stats_ws(nullptr, 2 * (1 + MM_PRED_MAXC), 2).bytes; }
 
 int mm_pl_adapt(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, double momentum,
                 int warmup, double* state, int64_t* count, float* thr, void* ws, size_t ws_bytes, hipStream_t s) {
-  static_assert(2 * (1 + MM_PRED_MAXC) <= PT && 2 * (1 + MM_PRED_MAXC) <= PL_UT, "one thread per (output, quantity)");
+  static_assert(2 * (1 + MM_PRED_MAXC) <= PT && 2 * (1 + MM_PRED_MAXC) <= ROWS_FT, "one thread per (output, quantity)");
   MM_CHECK_ARG(C > 0 && C <= MM_PRED_MAXC, "pl_adapt: bad C");
   MM_CHECK_ARG(N >= 0 && N <= (int64_t)PT * 0x7fffffff, "pl_adapt: bad N");
   MM_CHECK_ARG(momentum >= 0.0 && momentum < 1.0, "pl_adapt: the momentum must lie in [0, 1)");
@@ -428,20 +407,19 @@ int mm_pl_adapt(const float* logits2d, int ld2, const float* logits3d, int ld3, 
   MM_CHECK_ARG(N == 0 || (logits2d && logits3d), "pl_adapt: null logits");
   MM_CHECK_ARG(N == 0 || (ld2 >= C && ld3 >= C), "pl_adapt: row pitch below C");
   MM_CHECK_ARG(ws && ws_bytes >= mm_pl_adapt_ws_bytes(), "pl_adapt: workspace missing or too small");
-  double* psum = (double*)ws;
-  long long* pcnt = (long long*)((char*)ws + mm_align((size_t)PL_MAX_WG * 2 * (1 + MM_PRED_MAXC) * sizeof(double)));
+  const StatsWs w = stats_ws(ws, 2 * (1 + MM_PRED_MAXC), 2);
   const int64_t nt = mm_cdiv(N, PT);
-  const int nb = (int)(nt > PL_MAX_WG ? PL_MAX_WG : nt);
+  const int nb = (int)(nt > ROWS_MAX_WG ? ROWS_MAX_WG : nt);
   if (nb > 0) {
     const size_t lds = ((size_t)2 * PT * (C | 1) + 2 * PT) * sizeof(float);  // <= 34 KB
     if (ensemble)
-      hipLaunchKernelGGL(k_pl_stats<true>, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, psum, pcnt);
+      hipLaunchKernelGGL(k_pl_stats<true>, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, w.psum, w.pcnt);
     else
-      hipLaunchKernelGGL(k_pl_stats<false>, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, psum, pcnt);
+      hipLaunchKernelGGL(k_pl_stats<false>, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, w.psum, w.pcnt);
     MM_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_pl_update, dim3(1), dim3(PL_UT), 0, s, (const double*)psum, (const long long*)pcnt, nb, C, momentum, warmup ? 1 : 0,
-                     state, count, thr);
+  hipLaunchKernelGGL(k_pl_update, dim3(1), dim3(ROWS_FT), 0, s, (const double*)w.psum, (const long long*)w.pcnt, nb, C, momentum,
+                     warmup ? 1 : 0, state, count, thr);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

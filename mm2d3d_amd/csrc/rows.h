@@ -1,11 +1,24 @@
-// The row toolkit of the kernels that give a lane one row of per-point logits [N, C] (loss.hip, lovasz.hip, pselab.hip): which
-// labels count, the row's log-sum-exp, the cross-entropy gradient row, the fixed-order sums and the pitched LDS staging.  ONE
-// expression each, so that two losses over the same row agree bit for bit.  (mm_point_predict of pointpred.h keeps its own strict
-// `>` maximum scan: it also tracks the argmax and differs from fmaxf on NaN rows.)
-// Row pointers may be global memory or LDS: the address space is inferred after inlining.
+// The row toolkit of the kernels that give a lane one row of per-point logits [N, C] (loss.hip, lovasz.hip, pselab.hip, infomax.hip).
+// ONE expression each, so that two kernels over the same rows agree bit for bit:
+//   label_counted, row_lse, ce_grad_row    which labels count, the row's log-sum-exp, the cross-entropy gradient row
+//                                          (loss.hip k_ce_*, k_ce2s_*; lovasz.hip; infomax.hip)
+//   wave_sum, block_sum                    the fixed-order sums of a wave and of a workgroup
+//   sum_partials<K>                        one wave over the [nb][K] partials of the pass before (k_ce_finalize, k_ce2s_finalize,
+//                                          k_kl_finalize, lovasz.hip)
+//   sum_partial                            the same with K known at run time, one quantity per call (k_pl_update, k_im_final)
+//   row_tile, tile_head                    the rows of tile t, and where a tile's tail rows begin (k_pselab_predict,
+//                                          k_teacher_labels, k_pl_stats, k_im_stats, k_im_bwd, k_ce2s_fwd, k_ce2s_bwd)
+//   stage_rows, unstage_rows               global memory -> pitched LDS tile and back, coalesced (every kernel above; out:
+//                                          k_im_bwd, k_ce2s_bwd)
+//   wave_count, block_count                counted rows: ballots per wave, totals through LDS (k_teacher_labels, k_pl_stats,
+//                                          k_im_stats)
+//   col_sum                                a column of a staged tile into an fp64 accumulator, rows ascending (k_pl_stats, k_im_stats)
+//   stats_ws, ROWS_MAX_WG, ROWS_FT         the workspace and the sizes of a capped-grid statistics pass and its one-workgroup
+//                                          finish (mm_pl_adapt, mm_im_fwd)
+// (mm_point_predict of pointpred.h keeps its own strict `>` maximum scan: it also tracks the argmax and differs from fmaxf on NaN
+// rows.)  Row pointers may be global memory or LDS: the address space is inferred after inlining.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "common.h"
 
 // a row is counted when its label is a class and not the ignore value
 __device__ __forceinline__ bool label_counted(int64_t y, int64_t ignore, int C) { return !(y == ignore || y < 0 || y >= C); }
@@ -31,7 +44,8 @@ __device__ __forceinline__ void ce_grad_row(float* d, const float* x, int C, flo
 }
 
 // ---- sums in a fixed order: bit-stable run to run
-__device__ __forceinline__ double wave_sum64(double v) {
+template <typename V>  // double, or long long for counts
+__device__ __forceinline__ V wave_sum(V v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
   return v;
@@ -62,7 +76,28 @@ __device__ __forceinline__ void sum_partials(const double* __restrict__ partial,
     for (int k = 0; k < K; k++) v[k] += partial[K * i + k];
   }
 #pragma unroll
-  for (int k = 0; k < K; k++) v[k] = wave_sum64(v[k]);
+  for (int k = 0; k < K; k++) v[k] = wave_sum(v[k]);
+}
+
+// The same over partial[nb][K] with K known at run time: one wave per quantity q (k_pl_update, k_im_final: a wave per quantity,
+// sixteen waves).  Every lane calls; lane 0 holds the total.  V: double for the sums, long long for the integer counts beside them.
+template <typename V>
+__device__ __forceinline__ V sum_partial(const V* __restrict__ partial, int nb, int K, int q, int lane) {
+  V v = 0;
+  for (int i = lane; i < nb; i += 64) v += partial[(int64_t)i * K + q];
+  return wave_sum(v);
+}
+
+// ---- tiles: tile t of the rows [first, N) at PT rows per tile is rows [row0, row0 + rows) of the matrix
+struct RowTile { int64_t row0; int rows; };
+template <int PT>
+__device__ __forceinline__ RowTile row_tile(int64_t t, int64_t N, int64_t first = 0) {
+  const int64_t row0 = first + t * PT;
+  return {row0, (int)((N - row0) < (int64_t)PT ? (N - row0) : (int64_t)PT)};
+}
+// the head / tail split of a tile for a first tail row P: its rows [0, h) are head rows, [h, rows) are tail rows P + ...
+__device__ __forceinline__ int tile_head(int64_t P, int64_t row0, int rows) {
+  return (int)(P <= row0 ? 0 : (P - row0 < (int64_t)rows ? P - row0 : (int64_t)rows));
 }
 
 // ---- staging: a [rows, C] block (row pitch ld) copied into LDS by a workgroup of NT threads, consecutive lanes on consecutive
@@ -75,4 +110,53 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ dst, const float*
     const int r = e / C, c = e - r * C;
     dst[r * pitch + c] = src[(int64_t)r * ld + c];
   }
+}
+
+// The mirror: the tile (gradient rows formed in place) leaves LDS for dst[rows, C] (row pitch ld) the same way.  ZERO: a tile
+// that holds nothing to keep (head rows alone) writes zeros and reads no LDS.  The caller synchronises before.
+template <int NT, bool ZERO = false>
+__device__ __forceinline__ void unstage_rows(float* __restrict__ dst, int64_t ld, const float* __restrict__ src, int rows, int C,
+                                             int pitch) {
+  for (int e = threadIdx.x; e < rows * C; e += NT) {
+    const int r = e / C, c = e - r * C;
+    dst[(int64_t)r * ld + c] = ZERO ? 0.f : src[r * pitch + c];
+  }
+}
+
+// ---- counted rows: integers throughout, so the order of the additions cannot show.  wave_count: every lane holds the number of
+// its wave's lanes that count; a kernel that walks tiles adds these up per wave.  block_count: the workgroup's totals of K such
+// per-wave counters, through words[NT / 64][K] of LDS in wave order; thread k < K returns total k (the others 0).  The caller
+// makes sure that nobody still reads what `words` may alias.
+__device__ __forceinline__ unsigned wave_count(bool counted) { return (unsigned)__popcll(__ballot(counted)); }
+
+template <int NT, int K>
+__device__ __forceinline__ long long block_count(const unsigned (&n)[K], unsigned* words) {
+  static_assert(NT % 64 == 0, "counts are kept per 64-lane wave");
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; k++) words[K * wave + k] = n[k];
+  }
+  __syncthreads();
+  long long s = 0;
+  if (threadIdx.x < K)
+    for (int w = 0; w < NT / 64; w++) s += (long long)words[K * w + threadIdx.x];
+  return s;
+}
+
+// ---- a column of a staged tile: acc += p[r * stride] for r ascending - the order is part of the result bits.  The accumulator
+// is the caller's, carried across the tiles a workgroup walks.
+__device__ __forceinline__ void col_sum(double& acc, const float* p, int stride, int rows) {
+  for (int r = 0; r < rows; r++) acc += (double)p[r * stride];
+}
+
+// ---- a capped-grid statistics pass and its finish: at most ROWS_MAX_WG workgroups walk the tiles and leave K fp64 partial sums
+// and n integer counts each; one workgroup of ROWS_FT threads (sixteen waves, a wave per quantity) totals them.
+constexpr int ROWS_MAX_WG = 1024;
+constexpr int ROWS_FT = 1024;
+
+struct StatsWs { double* psum /*[ROWS_MAX_WG][K]*/; long long* pcnt /*[ROWS_MAX_WG][n]*/; size_t bytes; };
+inline StatsWs stats_ws(void* ws, int K, int n) {
+  const size_t off = mm_align((size_t)ROWS_MAX_WG * K * sizeof(double));
+  return {(double*)ws, (long long*)((char*)ws + off), off + mm_align((size_t)ROWS_MAX_WG * n * sizeof(long long))};
 }

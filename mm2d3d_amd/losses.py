@@ -70,16 +70,6 @@ def cross_entropy(pred, gt, weight=None, ignore_index=-100):
     return _CrossEntropyFn.apply(pred, gt, _device_weight(weight, pred.device), ignore_index)
 
 
-def _row_pitched(t):
-    """fp32 [N, C] that the row kernels read in place: a row-pitched view (stride(1) == 1) stays, as pselab._logits does, anything
-    else is copied."""
-    t = t.to(F32)
-    N, C = t.shape
-    if t.stride(1) != 1 or (N > 1 and t.stride(0) < C):
-        t = t.contiguous()
-    return t, (t.stride(0) if N > 1 else C)
-
-
 def _grad_rows(logits, in_dtype, launch):
     """The gradient of a row loss: ``launch(d)`` has a backward kernel write the fp32 [N, C] buffer ``d`` (row pitch C), which goes
     back in the dtype the logits came in."""
@@ -116,7 +106,7 @@ class _CrossEntropyPairFn(torch.autograd.Function):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
-        logits, ld = _row_pitched(logits)
+        logits, ld = _lib.row_pitched(logits)
         N, C = logits.shape
         stats = torch.empty(4, dtype=F32, device=logits.device)
         ws = _lib.workspace.get(int(L.mm_ce2_ws_bytes()), logits.device)
@@ -176,9 +166,9 @@ class _CrossEntropySoftPairFn(torch.autograd.Function):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
-        logits, ld = _row_pitched(logits)
-        ta, ld_a = _row_pitched(ta)
-        tb, ld_b = _row_pitched(tb) if tb is not None else (None, 0)
+        logits, ld = _lib.row_pitched(logits)
+        ta, ld_a = _lib.row_pitched(ta)
+        tb, ld_b = _lib.row_pitched(tb) if tb is not None else (None, 0)
         N, C = logits.shape
         stats = torch.empty(4, dtype=F32, device=logits.device)
         kept = torch.empty((), dtype=torch.int64, device=logits.device)
@@ -268,7 +258,7 @@ class _LovaszFn(torch.autograd.Function):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
-        logits, ld = _row_pitched(logits)
+        logits, ld = _lib.row_pitched(logits)
         N, C = logits.shape
         err = torch.empty((C, N), dtype=F32, device=logits.device)  # needed by nobody after the call: freed on return
         coef = torch.empty((C, N), dtype=F32, device=logits.device)
@@ -325,7 +315,7 @@ class _TargetEntropyFn(torch.autograd.Function):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
-        logits, ld = _row_pitched(logits)
+        logits, ld = _lib.row_pitched(logits)
         N, C = logits.shape
         dev = logits.device
         stats, mass, aux = (torch.empty(k, dtype=F32, device=dev) for k in (2, C, C + 1))

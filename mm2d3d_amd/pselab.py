@@ -35,15 +35,12 @@ MAX_CLASSES = 32  # csrc/pointpred.h MM_PRED_MAXC
 
 # ---------------------------------------------------------------------------------------------------- prediction
 def _logits(t, name, who="predict"):
+    """The checked fp32 ``[N, C]`` tensor the kernels read, and its row pitch."""
     _lib.require_cuda(t, name)
     t = t.detach()
     if t.dim() != 2:
         raise ValueError(f"pselab.{who}: {name} must be [N, C]")
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()  # a row-pitched view (stride(1) == 1) is read in place; one row has no pitch to check
-    return t
+    return _lib.row_pitched(t)  # a row-pitched view (stride(1) == 1) is read in place
 
 
 @torch.no_grad()
@@ -51,17 +48,16 @@ def predict(logits_2d, logits_3d=None):
     """Per point the confidence and the class of the 2D logits, the 3D logits and the softmax average, as device tensors under
     the keys of the pseudo-label file (fp32 probabilities, uint8 labels).  ``logits_3d=None``: a 2D-only prediction, the
     3D and ensemble entries are ``None``."""
-    a = _logits(logits_2d, "logits_2d")
-    b = None if logits_3d is None else _logits(logits_3d, "logits_3d")
+    a, ld_a = _logits(logits_2d, "logits_2d")
+    b, ld_b = (None, 0) if logits_3d is None else _logits(logits_3d, "logits_3d")
     if b is not None and (b.shape != a.shape or b.device != a.device):
         raise ValueError("pselab.predict: logits_2d and logits_3d must have the same shape and device")
     N, C = a.shape
     n_out = 1 if b is None else 3
     probs = torch.empty((n_out, N), dtype=torch.float32, device=a.device)
     labels = torch.empty((n_out, N), dtype=torch.uint8, device=a.device)
-    pitch = lambda t: t.stride(0) if N > 1 else C
     with torch.cuda.device(a.device):
-        check(_lib.lib().mm_pselab_predict(ptr(a), pitch(a), ptr(b), pitch(b) if b is not None else 0, N, C, ptr(probs[0]), ptr(labels[0]),
+        check(_lib.lib().mm_pselab_predict(ptr(a), ld_a, ptr(b), ld_b, N, C, ptr(probs[0]), ptr(labels[0]),
                                            ptr(probs[1]) if b is not None else None, ptr(labels[1]) if b is not None else None,
                                            ptr(probs[2]) if b is not None else None, ptr(labels[2]) if b is not None else None,
                                            stream()), "pselab_predict")
@@ -88,17 +84,16 @@ def teacher_labels(logits_2d, logits_3d, ensemble=False, threshold=None, ignore_
             raise ValueError(f"pselab.teacher_labels: a threshold tensor must be float32 [2, {logits_2d.shape[-1]}] on "
                              f"{logits_2d.device}, not {threshold.dtype} {tuple(threshold.shape)} on {threshold.device}")
         threshold = threshold.detach().contiguous()
-    a, b = _logits(logits_2d, "logits_2d", "teacher_labels"), _logits(logits_3d, "logits_3d", "teacher_labels")
+    (a, ld_a), (b, ld_b) = _logits(logits_2d, "logits_2d", "teacher_labels"), _logits(logits_3d, "logits_3d", "teacher_labels")
     if b.shape != a.shape or b.device != a.device:
         raise ValueError("pselab.teacher_labels: logits_2d and logits_3d must have the same shape and device")
     N, C = a.shape
     labels = torch.empty((2, N), dtype=torch.int64, device=a.device)
     probs = torch.empty((2, N), dtype=torch.float32, device=a.device) if with_probs else None
     kept = torch.zeros(2, dtype=torch.int64, device=a.device) if N == 0 else torch.empty(2, dtype=torch.int64, device=a.device)
-    pitch = lambda t: t.stride(0) if N > 1 else C
     with torch.cuda.device(a.device):
         fn = _lib.lib().mm_teacher_labels_cls if cls else _lib.lib().mm_teacher_labels
-        check(fn(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)),
+        check(fn(ptr(a), ld_a, ptr(b), ld_b, N, C, int(bool(ensemble)),
                  ptr(threshold) if cls else -1.0 if threshold is None else float(threshold), int(ignore_label), ptr(labels[0]),
                  ptr(labels[1]), ptr(probs[0]) if with_probs else None, ptr(probs[1]) if with_probs else None, ptr(kept), stream()),
               "teacher_labels_cls" if cls else "teacher_labels")
@@ -154,7 +149,7 @@ class AdaptiveThreshold:
         self.count.copy_(sd["count"].to(torch.int64))
 
     def _update(self, logits_2d, logits_3d, ensemble, who):
-        a, b = _logits(logits_2d, "logits_2d", who), _logits(logits_3d, "logits_3d", who)
+        (a, ld_a), (b, ld_b) = _logits(logits_2d, "logits_2d", who), _logits(logits_3d, "logits_3d", who)
         if b.shape != a.shape or b.device != a.device:
             raise ValueError(f"pselab.{who}: logits_2d and logits_3d must have the same shape and device")
         if a.shape[1] != self.num_classes or a.device != self.state.device:
@@ -162,11 +157,10 @@ class AdaptiveThreshold:
                              f"{self.state.device}")
         N, C = a.shape
         thr = torch.empty((2, C), dtype=torch.float32, device=a.device)
-        pitch = lambda t: t.stride(0) if N > 1 else C
         L = _lib.lib()
         with torch.cuda.device(a.device):
             ws = _lib.workspace.get(int(L.mm_pl_adapt_ws_bytes()), a.device, "pselab")
-            check(L.mm_pl_adapt(ptr(a), pitch(a), ptr(b), pitch(b), N, C, int(bool(ensemble)), self.momentum, int(self.warmup),
+            check(L.mm_pl_adapt(ptr(a), ld_a, ptr(b), ld_b, N, C, int(bool(ensemble)), self.momentum, int(self.warmup),
                                 ptr(self.state), ptr(self.count), ptr(thr), ptr(ws), ws.numel(), stream()), "pl_adapt")
         return a, b, thr
 

@@ -267,6 +267,55 @@ def test_two_objects_fed_the_same_sequence_end_with_equal_bits():
         ad.update(*_pair(5, 64, dev))
 
 
+WALK_N = 1024 * 128 + 129  # 1024 workgroups at most, 128 rows per tile: 1026 tiles
+
+
+@functools.lru_cache(maxsize=None)
+def _walk_logits(C):
+    """(2D, 3D) logits [WALK_N, C] fp32 = 3 * randn from a seed of their own, with the non-finite rows of the test below; computed
+    once, never written."""
+    rng = np.random.default_rng(4321 + C)
+    x2, x3 = ((3.0 * rng.standard_normal((WALK_N, C))).astype(np.float32) for _ in range(2))
+    x2[131100], x3[131100] = np.nan, np.nan  # a whole row of both, in tile 1024: the second tile of workgroup 0
+    x2[131200, 1] = np.inf  # of the 2D logits only, the one row of tile 1025: the second tile of workgroup 1
+    return x2, x3
+
+
+@pytest.mark.parametrize("ens", [False, True], ids=["own", "ensemble"])
+@pytest.mark.parametrize("C", [5, 32])
+def test_the_walk_over_more_tiles_than_workgroups(C, ens):
+    """mm_pl_adapt at N = 1024 * 128 + 129: workgroup 0 takes tiles 0 and 1024 (the second one full), workgroup 1 takes tiles 1 and
+    1025 (the second one a single row), every other workgroup one tile - the accumulator carried across a workgroup's tiles and
+    the barrier before restaging.  Both second tiles hold rows that are not counted."""
+    from mm2d3d_amd import pselab
+
+    dev = _dev()
+    x2, x3 = _walk_logits(C)
+    a, b = torch.from_numpy(x2).to(dev), torch.from_numpy(x3).to(dev)
+    what = f"the walk, C {C} ens {ens}"
+    ad, ref = pselab.AdaptiveThreshold(C, momentum=0.5, device=dev), AdaptiveRef(C, momentum=0.5)
+    out = ad.labels(a, b, ensemble=ens, with_probs=True)
+    ref.update(x2, x3, ensemble=ens)
+    _state_close(ad, ref, out["threshold"], what)
+    _check_against_predict(a, b, ens, out, what)
+    # the counted rows, through a momentum-0 update: tau is then the mean confidence over exactly those rows
+    z = pselab.AdaptiveThreshold(C, momentum=0.0, device=dev)
+    z.update(a, b, ensemble=ens)
+    refused = ([131100, 131200], [131100, 131200] if ens else [131100])
+    for o, (name, bad) in enumerate(zip(("2d", "3d"), refused)):
+        good = torch.ones(WALK_N, dtype=torch.bool, device=dev)
+        good[bad] = False
+        assert all(int(out[f"label_{name}"][i]) == -100 for i in bad)
+        err = abs(float(z.state[o, 0]) - float(out[f"prob_{name}"].double()[good].mean()))
+        print(f"{what}: output {o}: |tau - mean confidence of the {int(good.sum())} counted rows| {err:.2e}")
+        assert err <= 1e-12  # WALK_N - len(bad) rows, not one more or fewer
+    # two objects fed the same call end with equal bits
+    again = pselab.AdaptiveThreshold(C, momentum=0.5, device=dev)
+    thr = again.update(a, b, ensemble=ens)
+    assert torch.equal(_bits(again.state), _bits(ad.state)) and torch.equal(again.count, ad.count)
+    assert torch.equal(_bits(thr), _bits(out["threshold"]))
+
+
 def test_row_pitched_views_are_read_in_place_past_nan_padding():
     from mm2d3d_amd import pselab
 

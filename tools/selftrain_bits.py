@@ -1,16 +1,19 @@
 """Bits of the self-training step, for comparing two checkouts of this project (a refactor against its parent).
 
-    python tools/selftrain_bits.py dump OUT.npz [--only SUBSTRING]
+    python tools/selftrain_bits.py dump OUT.npz [--only SUBSTRING[,SUBSTRING...]]
     python tools/selftrain_bits.py compare A.npz B.npz
 
 ``dump`` runs every self-training option combination for three ``fit_step`` calls at the shapes of tests/test_gpu_teacher_step.py
 (1 + 1 synthetic nuScenes scenes, 48x64 images, 6 classes, fp16, dropout 0, ``ema_decay`` 0.9, heads scaled by 4; fresh nets from
 seed 0 per case) and stores, as raw bytes: per step the loss, every ``last_logs`` value and every tensor of ``last_teacher``; after
-the last step every entry of the checkpoint's "state_dict" and "ema_state_dict" and the state of ``pl_adaptive``.  It uses only
-``train_kwargs``, ``fit_step``, ``last_logs``, ``last_teacher``, ``pl_adaptive.state_dict()``, ``checkpoint()`` and
-``load_checkpoint()``, so the same file runs in either checkout (it imports the package of the checkout whose ``tools/`` it lies
-in: copy it there).  ``compare`` demands equal key lists and equal bytes, prints the
-number of arrays and the total bytes, and exits 1 on any difference.  One process per dump.
+the last step every entry of the checkpoint's "state_dict" and "ema_state_dict" and the state of ``pl_adaptive``.  Then the
+``direct/`` group: the row kernels called through ``pselab.predict``, ``pselab.teacher_labels``, ``AdaptiveThreshold.update``,
+``losses.cross_entropy_soft_pair`` and ``losses.target_entropy`` at sizes the tiny step never reaches (``DIRECT_SIZES``: a tile and a
+row, the class maximum, more tiles than workgroups of both tile sizes), contiguous and as row-pitched views, every output and
+gradient as raw bytes.  It uses only ``train_kwargs``, ``fit_step``, ``last_logs``, ``last_teacher``,
+``pl_adaptive.state_dict()``, ``checkpoint()``, ``load_checkpoint()`` and those public functions, so the same file runs in either
+checkout (it imports the package of the checkout whose ``tools/`` it lies in: copy it there).  ``compare`` demands equal key lists
+and equal bytes, prints the number of arrays and the total bytes, and exits 1 on any difference.  One process per dump.
 """
 import argparse
 import gc
@@ -30,6 +33,8 @@ CE = {"name": "cross_entropy", "target": "segmentation", "args": {"weight": W}}
 REGISTRY = {"single": [CE], "two_entries": [dict(CE, weight=0.5), dict(CE, weight=0.5)]}
 STEPS = 3
 ADAPTIVE = dict(pl_threshold_momentum=0.5, pl_threshold_warmup=True)  # the thresholds bite from the first step
+PRIOR = [0.3, 0.1, 0.2, 0.1, 0.2, 0.1]
+DIRECT_SIZES = ((129, 5), (1000, 32), (131201, 6), (300001, 6))  # (N, C)
 
 
 def cases():
@@ -56,6 +61,10 @@ def cases():
     add("teacher/hard/own/thr_None/prefetched", dict(teacher), prefetch=True)
     add("teacher/lambda_pl_0", dict(lambda_pl=0.0, pseudo_label_source="teacher", pl_threshold=0.9))
     add("teacher/hard/own/thr_adaptive/checkpoint_round_trip", dict(teacher, pl_threshold="adaptive"), resume=True)
+    infomax = dict(lambda_minent=0.1, lambda_div=0.1)  # MinEnt / InfoMax on the target rows
+    for (call, ckw), (prior, pkw) in itertools.product(calls.items(), (("uniform", {}), ("prior", dict(div_prior=PRIOR)))):
+        add(f"infomax/{call}/{prior}", dict(infomax, **ckw, **pkw))
+    add("infomax/joined/uniform/with_teacher_soft_adaptive", dict(teacher, **infomax, pl_targets="soft", pl_threshold="adaptive"))
     return out
 
 
@@ -98,6 +107,10 @@ def _batch(dev, extras, step):
     return b
 
 
+def _wanted(name, only):
+    return not only or any(part in name for part in only.split(","))
+
+
 def _raw(t):
     import torch
 
@@ -121,6 +134,70 @@ def _forget(tm):
     torch.cuda.empty_cache()
 
 
+def _direct_inputs(N, C, pitched, dev):
+    """(student logits, teacher 2D, teacher 3D, head labels) of a size, seeded; two rows are not finite.  ``pitched``: each matrix
+    a column slice of a wider NaN-filled one (stride(1) == 1, read in place)."""
+    import torch
+
+    g = torch.Generator().manual_seed(7000 + 37 * C + N % 1000)
+    mats = [3.0 * torch.randn(N, C, generator=g) for _ in range(3)]
+    mats[1][N - 2], mats[2][N - 2] = float("nan"), float("nan")  # a whole row of both teachers
+    mats[1][N // 3, 1], mats[0][N - 1, 0] = float("inf"), float("inf")  # one entry of one teacher; one of the student's target rows
+    y = torch.randint(0, C, (N,), generator=g)
+    y[torch.rand(N, generator=g) < 0.3] = -100
+    out = []
+    for k, m in enumerate(mats):
+        if pitched:
+            wide = torch.full((N, C + 3 + k), float("nan"))
+            wide[:, 1 + k : 1 + k + C] = m
+            m = wide.to(dev)[:, 1 + k : 1 + k + C]
+        out.append(m.to(dev))
+    return out[0], out[1], out[2], y.to(dev)
+
+
+def direct_cases(put, dev, only=None):
+    """The ``direct/`` group: every public entry of the row kernels at DIRECT_SIZES."""
+    import torch
+
+    from mm2d3d_amd import losses, pselab
+
+    for (N, C), pitched in itertools.product(DIRECT_SIZES, (False, True)):
+        base = f"direct/{N}_{C}/{'pitched' if pitched else 'contiguous'}"
+        if not _wanted(base, only):
+            continue
+        x, a, b, y = _direct_inputs(N, C, pitched, dev)
+        P = N // 2
+        thr2 = torch.linspace(0.35, 0.8, 2 * C, dtype=torch.float32, device=dev).reshape(2, C)
+        prior = [1.0 + c for c in range(C)]
+
+        def put_all(name, d):
+            for k, v in d.items():
+                if torch.is_tensor(v):
+                    put(f"{base}/{name}/{k}", _raw(v))
+
+        put_all("predict/2d", pselab.predict(a))
+        put_all("predict/pair", pselab.predict(a, b))
+        for ens in (False, True):
+            for tname, thr in (("scalar", 0.6), ("per_class", thr2)):
+                put_all(f"teacher_labels/ens_{ens}/{tname}", pselab.teacher_labels(a, b, ensemble=ens, threshold=thr, with_probs=True))
+            ad = pselab.AdaptiveThreshold(C, momentum=0.5, warmup=True, device=dev)
+            for k, lo in enumerate((0, N // 7, N // 3)):  # three updates in a row, different rows each time
+                put(f"{base}/adaptive_update/ens_{ens}/thr{k}", _raw(ad.update(a[lo:], b[lo:], ensemble=ens)))
+            put_all(f"adaptive_update/ens_{ens}", dict(state=ad.state, count=ad.count))
+            for (tname, thr), T in itertools.product((("scalar", 0.6), ("per_class", thr2[0].contiguous())), (1.0, 2.0)):
+                xg = x.detach().requires_grad_(True)
+                lh, lt, kept = losses.cross_entropy_soft_pair(xg, P, y[:P], a[P:], b[P:] if ens else None, temperature=T, threshold=thr)
+                (grad,) = torch.autograd.grad(lh + lt, xg)
+                put_all(f"soft_pair/ens_{ens}/{tname}/T_{T}", dict(head=lh, tail=lt, kept=kept, grad=grad))
+        for first, (pname, pr) in itertools.product((0, P), (("uniform", None), ("prior", prior))):
+            xg = x.detach().requires_grad_(True)
+            ent, div, mass, count = losses.target_entropy(xg, first, pr)
+            (grad,) = torch.autograd.grad(ent + 0.5 * div, xg)
+            put_all(f"target_entropy/first_{first}/{pname}", dict(ent=ent, div=div, mass=mass, count=count, grad=grad))
+        torch.cuda.synchronize()
+        print(f"{base}: done", flush=True)
+
+
 def dump(path, only=None):
     import torch
 
@@ -137,7 +214,7 @@ def dump(path, only=None):
         count, nbytes = count + 1, nbytes + arr.nbytes
 
     for name, (kw, registry, extras, prefetch, resume) in cases().items():
-        if only and only not in name:
+        if not _wanted(name, only):
             continue
         tm = _trainer(dev, kw, registry)
         batches = [_batch(dev, extras, s) for s in range(STEPS)]
@@ -167,6 +244,7 @@ def dump(path, only=None):
               f"last_teacher {sorted(tm.last_teacher) if tm.last_teacher else None}", flush=True)
         _forget(tm)
         del tm, ckpt, batches
+    direct_cases(put, dev, only)
     archive.close()
     print(f"{count} arrays, {nbytes} bytes -> {path}", flush=True)
 
@@ -186,7 +264,9 @@ def compare(a_path, b_path):
             if x.shape != y.shape or not np.array_equal(x, y):
                 bad.append(f"differs: {k} ({x.nbytes} / {y.nbytes} bytes)")
     names = sorted({k.split("/step")[0] for k in ka if "/step" in k})
-    print(f"{len(names)} cases, {len(ka)} arrays, {total} bytes: " + ("all identical" if not bad else f"{len(bad)} DIFFERENCES"))
+    direct = sorted({"/".join(k.split("/")[:4]) for k in ka if k.startswith("direct/")})
+    print(f"{len(names)} step cases, {len(direct)} direct calls, {len(ka)} arrays, {total} bytes: "
+          + ("all identical" if not bad else f"{len(bad)} DIFFERENCES"))
     for line in bad[:200]:
         print(line)
     return 1 if bad else 0
@@ -197,7 +277,7 @@ def main():
     sub = ap.add_subparsers(dest="cmd", required=True)
     d = sub.add_parser("dump")
     d.add_argument("out")
-    d.add_argument("--only", default=None, help="run the cases whose name contains this")
+    d.add_argument("--only", default=None, help="run the cases whose name contains one of these (comma-separated)")
     c = sub.add_parser("compare")
     c.add_argument("a")
     c.add_argument("b")
