@@ -448,6 +448,20 @@ int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
 int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* stats,
                const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
+/* The same pair with a weight per TAIL row: row_w [N - P] fp32 on the device (mm_pl_agree's weights; any finite values >= 0).
+ *   loss1 = (1 / sum_w1) * sum over the counted tail rows of row_w_i * weight1[y_i] * ce_i;
+ *   gradient row of a counted tail row: grad_out[1] * row_w_i * weight1[y_i] / sum_w1 * (softmax - onehot).
+ * sum_w1 (stats[3]) is what mm_ce2_fwd reports, the class weights of the counted rows: the row weights are NOT in the denominator,
+ * so a batch of uniformly uncertain rows pulls less instead of being renormalised.  A row with row_w == 0 is still counted and
+ * still written (a zero gradient row).  The head segment, stats[], zero_if_empty and the every-row-written-once rule are those of
+ * mm_ce2_*.  row_w == NULL launches mm_ce2_*'s kernels: the same bits; row_w all 1.0f gives the same bits too (x * 1.0f is exact).
+ * The weights are constants of the gradient.  One kernel family: the row weight is a compile-time flag of k_ce_fwd / k_ce_bwd. */
+int mm_ce2_fwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                 const int64_t* labels1, const float* weight1, int64_t ignore_index, int zero_if_empty, const float* row_w,
+                 float* stats, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_ce2_bwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                 const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* row_w, const float* stats,
+                 const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
 /* Two-segment cross entropy with a SOFT tail (mean-teacher targets).  Rows [0, P) of logits [N, C] are the head of mm_ce2_*:
  * int64 labels0, optional class weights, ignore_index, labels outside [0, C) skipped, weighted mean (0/0 = nan when nothing is
  * counted); labels0 == NULL = an unlabelled head, loss 0 and zero gradient rows.  Rows [P, N) are compared with the teacher
@@ -480,6 +494,21 @@ int mm_ce2s_fwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, co
 int mm_ce2s_bwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                     int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature,
                     const float* thr_cls, const float* stats, const float* grad_out, float* dlogits, int ld_d, mm_stream_t stream);
+/* The soft pair with a weight per TAIL row, row_w [N - P] fp32 on the device, and both kinds of threshold in one entry point: a
+ * non-NULL thr_cls [C] wins (the rule of mm_ce2s_*_cls), else the scalar thr (the rule of mm_ce2s_*).
+ *   loss = (1 / K) * sum over the K kept rows of row_w_i * sum_c q_c * (logsumexp(x) - x_c);
+ *   gradient row of a kept row: grad_out[1] * row_w_i / K * (softmax(x) - q).
+ * K (stats[3], kept) ignores row_w: thresholds decide which rows are kept, the weight scales the rows that remain; a kept row with
+ * row_w == 0 is counted and written as a zero gradient row.  Everything else is as above.  row_w == NULL launches the kernels of
+ * mm_ce2s_* / mm_ce2s_*_cls: the same bits; row_w all 1.0f gives the same bits too.  The weights are constants of the gradient. */
+int mm_ce2s_fwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                  int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                  const float* thr_cls, const float* row_w, float* stats, int64_t* kept, void* ws, size_t ws_bytes,
+                  mm_stream_t stream);
+int mm_ce2s_bwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                  int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                  const float* thr_cls, const float* row_w, const float* stats, const float* grad_out, float* dlogits, int ld_d,
+                  mm_stream_t stream);
 /* Lovasz-softmax loss (Berman et al., CVPR 2018) of logits [N, C] (row pitch ld) against int64 labels (csrc/lovasz.hip).
  * Counted rows: label != ignore_index and 0 <= label < C, as in mm_ce2_*; p = softmax(x) per row.  For every class c:
  * fg_i = [y_i == c], e_i = |fg_i - p_ic|; the counted rows are ordered by e descending, stable in the row index.  With G = sum fg,
@@ -587,6 +616,21 @@ int mm_teacher_labels_cls(const float* logits2d, int ld2, const float* logits3d,
 size_t mm_pl_adapt_ws_bytes(void);
 int mm_pl_adapt(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, int ensemble, double momentum,
                 int warmup, double* state, int64_t* count, float* thr, void* ws, size_t ws_bytes, mm_stream_t stream);
+/* Row weights from the agreement of the two modalities (the uncertainty weighting of Zheng & Yang, IJCV 2021, between the 2D and
+ * the 3D prediction of a row).  For row i with logit rows a (2D) and b (3D) of C classes, p = softmax(a), q = softmax(b),
+ * lp_c = a_c - logsumexp(a), lq_c = b_c - logsumexp(b) (no log of a probability is taken), all in float32:
+ *   D_i = 0.5 * sum_c (p_c - q_c) * (lp_c - lq_c)   half the Jeffreys divergence 0.5 * (KL(p||q) + KL(q||p)): >= 0, symmetric;
+ *         a term with p_c == q_c is 0; the sum runs ascending in c and is clamped at 0 from below;
+ *   w_i = expf(-beta * D_i)                          in [0, 1]; exactly 1 for identical rows.
+ * A row with a non-finite logit in either matrix gets w_i = 0 and is left out of the mean of D.  Outputs: w [N];
+ * stats[0] = (1 / N) sum_i w_i (0 when N == 0); stats[1] = the mean of D over the n finite rows (0 when n == 0); finite (may be
+ * NULL) receives n, exact.  Two launches: a capped grid stages 128-row tiles through LDS, writes w and leaves two fp64 sums and
+ * an integer count per workgroup; one workgroup combines them in a fixed order.  No atomics, no workgroup waits for another, no
+ * host read: bit-stable run to run.  N == 0 runs the second launch alone.  2 <= C <= 32, ld2 / ld3 >= C, beta finite and > 0,
+ * N * C < 2^31; anything else is refused before the first launch. */
+size_t mm_pl_agree_ws_bytes(void);
+int mm_pl_agree(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, float beta, float* w,
+                float* stats, int64_t* finite, void* ws, size_t ws_bytes, mm_stream_t stream);
 /* lib/utils/refine_pseudo_labels.py, exact: for every class c of [0, C) that occurs n_c > 0 times, med_c = the element of rank
  * (n_c - 1) / 2 (ascending, 0-based: torch.median's lower median) among the probs of that class, thr_c = min(med_c, 0.9f);
  * labels_out[i] = ignore_label where labels[i] == c and probs[i] < thr_c, else labels[i].  Labels outside [0, C) pass through.

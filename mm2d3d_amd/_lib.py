@@ -109,11 +109,15 @@ _PROTOS = {
     "mm_ce2_ws_bytes": (sz, []),
     "mm_ce2_fwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, i32, vp, vp, sz, vp]),
     "mm_ce2_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
+    "mm_ce2_fwd_w": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, sz, vp]),
+    "mm_ce2_bwd_w": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp]),
     "mm_ce2s_ws_bytes": (sz, []),
     "mm_ce2s_fwd": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, sz, vp]),
     "mm_ce2s_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, i32, vp]),
     "mm_ce2s_fwd_cls": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, vp, vp, vp, vp, sz, vp]),
     "mm_ce2s_bwd_cls": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, vp, vp, vp, vp, i32, vp]),
+    "mm_ce2s_fwd_w": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
+    "mm_ce2s_bwd_w": (i32, [vp, i32, i64, i64, i32, vp, vp, i64, vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, i32, vp]),
     "mm_lovasz_ws_bytes": (sz, [i64, i32]),
     "mm_lovasz_fwd": (i32, [vp, i32, i64, i32, vp, i64, i32, vp, vp, vp, vp, sz, vp]),
     "mm_lovasz_bwd": (i32, [vp, i32, i64, i32, vp, vp, vp, i32, vp]),
@@ -132,6 +136,8 @@ _PROTOS = {
     "mm_teacher_labels_cls": (i32, [vp, i32, vp, i32, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
     "mm_pl_adapt_ws_bytes": (sz, []),
     "mm_pl_adapt": (i32, [vp, i32, vp, i32, i64, i32, i32, f64, i32, vp, vp, vp, vp, sz, vp]),
+    "mm_pl_agree_ws_bytes": (sz, []),
+    "mm_pl_agree": (i32, [vp, i32, vp, i32, i64, i32, f32, vp, vp, vp, vp, sz, vp]),
     "mm_pselab_refine_ws_bytes": (sz, [i32]),
     "mm_pselab_refine": (i32, [vp, vp, i64, i32, i64, vp, vp, sz, vp]),
     "mm_grad_nonfinite": (i32, [vp, i64, vp, vp]),

@@ -20,14 +20,6 @@
 namespace {
 constexpr int PT = 128;  // rows per tile = threads per workgroup
 constexpr int MAXC = MM_PRED_MAXC;
-constexpr float F32_MAX = 3.402823466e38f;
-
-// a row is counted when every one of its logits is finite (NaN fails the comparison)
-__device__ __forceinline__ bool row_finite(const float* x, int C) {
-  bool ok = true;
-  for (int c = 0; c < C; c++) ok = ok && fabsf(x[c]) <= F32_MAX;
-  return ok;
-}
 
 __global__ __launch_bounds__(PT) void k_im_stats(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                   double* __restrict__ psum /*[grid][C + 1]*/, long long* __restrict__ pcnt /*[grid]*/) {

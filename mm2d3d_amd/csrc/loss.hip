@@ -18,12 +18,15 @@ constexpr int MAXC = MM_PRED_MAXC;
 // in ONE tensor; NSEG = 2 reads it once per direction and writes its gradient once (no slice gradients to zero-fill, copy and
 // add).  NSEG = 1 (mm_ce_*: P = N, labels required) is the same code with `tail` a compile-time false: over one labelled segment
 // the two agree bit for bit.  NSEG = 2: a NULL labels pointer = an unlabelled segment.
+// RW (mm_ce2_*_w): row_w[N - P] scales the tail rows' terms of the loss and their gradient rows, not the weight sum.  A compile-time
+// flag, as CLS below: without it the kernels are the kernels they were.
 // partial[b] = (sum w*nll, sum w) per segment
-template <int NSEG>
+template <int NSEG, bool RW = false>
 __global__ __launch_bounds__(T) void k_ce_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
                                                const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
-                                               double* __restrict__ partial) {
+                                               const float* __restrict__ row_w, double* __restrict__ partial) {
+  static_assert(!RW || NSEG == 2, "row weights belong to the tail");
   __shared__ double red[T];
   double sl[NSEG] = {}, sw[NSEG] = {};
   for (int64_t i = (int64_t)blockIdx.x * T + threadIdx.x; i < N; i += (int64_t)gridDim.x * T) {
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(T) void k_ce_fwd(const float* __restrict__ logits, 
     float nll = (r.m + logf(r.s)) - x[y];
     float w = weight ? weight[y] : 1.f;
     if (tail) {
-      sl[NSEG - 1] += (double)(w * nll);
+      sl[NSEG - 1] += (double)(RW ? row_w[i - P] * (w * nll) : w * nll);  // x * 1.0f is exact: all-one row weights change no bit
       sw[NSEG - 1] += (double)w;
     } else {
       sl[0] += (double)(w * nll);
@@ -72,13 +75,14 @@ __global__ __launch_bounds__(64) void k_ce_finalize(const double* __restrict__ p
   }
 }
 
-// every row written once: segment s: gout[s] * w[y] / sum_w_s * (softmax - onehot); ignored and unlabelled rows: zeros
-template <int NSEG>
+// every row written once: segment s: gout[s] * w[y] / sum_w_s * (softmax - onehot), RW: times row_w of a tail row; ignored and
+// unlabelled rows: zeros
+template <int NSEG, bool RW = false>
 __global__ __launch_bounds__(T) void k_ce_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                const int64_t* __restrict__ labels0, const float* __restrict__ weight0,
                                                const int64_t* __restrict__ labels1, const float* __restrict__ weight1, int64_t ignore,
-                                               const float* __restrict__ stats, const float* __restrict__ gout,
-                                               float* __restrict__ dlogits, int ld_d) {
+                                               const float* __restrict__ row_w, const float* __restrict__ stats,
+                                               const float* __restrict__ gout, float* __restrict__ dlogits, int ld_d) {
   int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;
   if (i >= N) return;
   const bool tail = NSEG == 2 && i >= P;
@@ -94,6 +98,7 @@ __global__ __launch_bounds__(T) void k_ce_bwd(const float* __restrict__ logits, 
   const float* x = logits + i * ld;
   const RowLse r = row_lse(x, C);
   float k = gout[tail] * (weight ? weight[y] : 1.f) / stats[2 * tail + 1];
+  if (RW && tail) k *= row_w[i - P];
   ce_grad_row(d, x, C, r.m, 1.f / r.s, k, (int)y);
 }
 
@@ -136,12 +141,14 @@ __device__ __forceinline__ void stage_ce2s(float* tile, const RowTile& t, int h,
   }
 }
 
-// partial[b] = (sum w*nll, sum w) of the head, (sum of the kept rows' soft cross entropies, kept rows) of the tail
-template <bool HAS_B, bool CLS>
+// partial[b] = (sum w*nll, sum w) of the head, (sum of the kept rows' soft cross entropies, kept rows) of the tail.  RW
+// (mm_ce2s_*_w): row_w[N - P] scales a kept row's term and its gradient row, not the count K.
+template <bool HAS_B, bool CLS, bool RW>
 __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                   const int64_t* __restrict__ labels0, const float* __restrict__ weight0, int64_t ignore,
                                                   const float* __restrict__ ta, int ld_a, const float* __restrict__ tb, int ld_b,
-                                                  float inv_t, float thr, const float* __restrict__ thr_cls, double* __restrict__ partial) {
+                                                  float inv_t, float thr, const float* __restrict__ thr_cls,
+                                                  const float* __restrict__ row_w, double* __restrict__ partial) {
   extern __shared__ float tile[];  // [HAS_B ? 3 : 2][ST][pitch]
   const int pitch = C | 1;
   float* sx = tile;
@@ -179,7 +186,7 @@ __global__ __launch_bounds__(ST) void k_ce2s_fwd(const float* __restrict__ logit
         const float lse = l.m + logf(l.s);
         float v = soft_dot(a, a[pr.ia], inv_t, x, lse, C);
         if (HAS_B) v = 0.5f * (v + soft_dot(b, b[pr.ib], inv_t, x, lse, C));
-        sl1 += (double)v;
+        sl1 += (double)(RW ? row_w[row0 + r - P] * v : v);
         k1 += 1;
       }
     }
@@ -208,13 +215,13 @@ __global__ __launch_bounds__(64) void k_ce2s_finalize(const double* __restrict__
 
 // One tile per workgroup, every row written once: the gradient rows are formed in place in the staged logits tile and leave it
 // with consecutive lanes on consecutive addresses.  Head: gout[0] * w[y] / sum_w * (softmax - onehot), as k_ce_bwd; kept tail
-// rows: gout[1] / K * (softmax - q), q recomputed from the teacher rows; every other row: zeros.
-template <bool HAS_B, bool CLS>
+// rows: gout[1] / K * (softmax - q), RW: times row_w of the row, q recomputed from the teacher rows; every other row: zeros.
+template <bool HAS_B, bool CLS, bool RW>
 __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logits, int ld, int64_t N, int64_t P, int C,
                                                   const int64_t* __restrict__ labels0, const float* __restrict__ weight0, int64_t ignore,
                                                   const float* __restrict__ ta, int ld_a, const float* __restrict__ tb, int ld_b,
                                                   float inv_t, float thr, const float* __restrict__ thr_cls,
-                                                  const float* __restrict__ stats,
+                                                  const float* __restrict__ row_w, const float* __restrict__ stats,
                                                   const float* __restrict__ gout, float* __restrict__ dlogits, int ld_d) {
   extern __shared__ float tile[];  // [HAS_B ? 3 : 2][ST][pitch]
   const int pitch = C | 1;
@@ -245,7 +252,7 @@ __global__ __launch_bounds__(ST) void k_ce2s_bwd(const float* __restrict__ logit
     } else {
       pr = mm_point_predict<HAS_B>(a, b, C);
       live = (HAS_B ? pr.pe : pr.pa) >= (CLS ? thr_cls[HAS_B ? pr.ie : pr.ia] : thr);
-      if (live) k = gout[1] / stats[3];
+      if (live) k = RW ? gout[1] / stats[3] * row_w[row0 + r - P] : gout[1] / stats[3];
     }
     if (!live) {
       for (int c = 0; c < C; c++) x[c] = 0.f;
@@ -357,7 +364,7 @@ int mm_ce_fwd(const float* logits, int ld, const int64_t* labels, const float* w
   }
   int nb = loss_blocks(N);
   hipLaunchKernelGGL(k_ce_fwd<1>, dim3(nb), dim3(T), 0, s, logits, ld, N, N, C, labels, weight, nullptr, nullptr, ignore_index,
-                     (double*)ws);
+                     nullptr, (double*)ws);
   hipLaunchKernelGGL(k_ce_finalize<1>, dim3(1), dim3(64), 0, s, (const double*)ws, nb, 1, 0, stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
@@ -370,17 +377,18 @@ int mm_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* w
   if (N == 0) return MM_OK;
   MM_CHECK_ARG(logits && labels && stats && grad_out && dlogits, "ce: null logits, labels, stats, grad_out or dlogits");
   hipLaunchKernelGGL(k_ce_bwd<1>, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, N, C, labels, weight, nullptr, nullptr,
-                     ignore_index, stats, grad_out, dlogits, ld_d);
+                     ignore_index, nullptr, stats, grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
 
 size_t mm_ce2_ws_bytes() { return mm_align((size_t)MAX_PART * 4 * sizeof(double)) + 256; }
 
-// stats[4] = loss and weight sum of rows [0, P), then of rows [P, N); see include/mm2d3d.h
-int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
-               const int64_t* labels1, const float* weight1, int64_t ignore_index, int zero_if_empty, float* stats, void* ws,
-               size_t ws_bytes, hipStream_t s) {
+// stats[4] = loss and weight sum of rows [0, P), then of rows [P, N); see include/mm2d3d.h.  row_w != NULL (mm_ce2_*_w): the
+// RW kernels; NULL launches the kernels of the plain entry points.
+int mm_ce2_fwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                 const int64_t* labels1, const float* weight1, int64_t ignore_index, int zero_if_empty, const float* row_w, float* stats,
+                 void* ws, size_t ws_bytes, hipStream_t s) {
   MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C, "ce2: bad C");
   MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N, "ce2: the split must lie in [0, N]");
   if (ws_bytes < (size_t)MAX_PART * 4 * sizeof(double)) {
@@ -388,24 +396,45 @@ int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const i
     return MM_ERR_WORKSPACE;
   }
   int nb = loss_blocks(N);
-  hipLaunchKernelGGL(k_ce_fwd<2>, dim3(nb), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index,
-                     (double*)ws);
+  if (row_w)
+    hipLaunchKernelGGL((k_ce_fwd<2, true>), dim3(nb), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1,
+                       ignore_index, row_w, (double*)ws);
+  else
+    hipLaunchKernelGGL(k_ce_fwd<2>, dim3(nb), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index,
+                       row_w, (double*)ws);
   hipLaunchKernelGGL(k_ce_finalize<2>, dim3(1), dim3(64), 0, s, (const double*)ws, nb, (labels0 ? 1 : 0) | (labels1 ? 2 : 0),
                      zero_if_empty, stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
 
-int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
-               const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* stats, const float* grad_out,
-               float* dlogits, int ld_d, hipStream_t s) {
+int mm_ce2_bwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                 const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* row_w, const float* stats,
+                 const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
   MM_CHECK_ARG(C > 0 && C <= MAXC && ld >= C && ld_d >= C, "ce2: bad C");
   MM_CHECK_ARG(N >= 0 && P >= 0 && P <= N, "ce2: the split must lie in [0, N]");
   if (N == 0) return MM_OK;
-  hipLaunchKernelGGL(k_ce_bwd<2>, dim3((unsigned)mm_cdiv(N, T)), dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1,
-                     ignore_index, stats, grad_out, dlogits, ld_d);
+  const dim3 grid((unsigned)mm_cdiv(N, T));
+  if (row_w)
+    hipLaunchKernelGGL((k_ce_bwd<2, true>), grid, dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index,
+                       row_w, stats, grad_out, dlogits, ld_d);
+  else
+    hipLaunchKernelGGL(k_ce_bwd<2>, grid, dim3(T), 0, s, logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index, row_w,
+                       stats, grad_out, dlogits, ld_d);
   MM_LAUNCH_CHECK();
   return MM_OK;
+}
+
+int mm_ce2_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+               const int64_t* labels1, const float* weight1, int64_t ignore_index, int zero_if_empty, float* stats, void* ws,
+               size_t ws_bytes, hipStream_t s) {
+  return mm_ce2_fwd_w(logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index, zero_if_empty, nullptr, stats, ws, ws_bytes, s);
+}
+
+int mm_ce2_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+               const int64_t* labels1, const float* weight1, int64_t ignore_index, const float* stats, const float* grad_out,
+               float* dlogits, int ld_d, hipStream_t s) {
+  return mm_ce2_bwd_w(logits, ld, N, P, C, labels0, weight0, labels1, weight1, ignore_index, nullptr, stats, grad_out, dlogits, ld_d, s);
 }
 
 size_t mm_ce2s_ws_bytes() { return mm_align((size_t)S_MAX_PART * 4 * sizeof(double)) + 256; }
@@ -426,9 +455,27 @@ static int ce2s_check(const float* logits, int ld, int64_t N, int64_t P, int C, 
   return MM_OK;
 }
 
+// the kernel of (tb != NULL, cls, row_w != NULL): LAUNCH(HAS_B, CLS, RW)
+#define MM_CE2S_DISPATCH_B(LAUNCH, CLS, RW) \
+  do {                                      \
+    if (tb) LAUNCH(true, CLS, RW);          \
+    else LAUNCH(false, CLS, RW);            \
+  } while (0)
+#define MM_CE2S_DISPATCH_C(LAUNCH, RW)                \
+  do {                                                \
+    if (cls) MM_CE2S_DISPATCH_B(LAUNCH, true, RW);    \
+    else MM_CE2S_DISPATCH_B(LAUNCH, false, RW);       \
+  } while (0)
+#define MM_CE2S_DISPATCH(LAUNCH)                      \
+  do {                                                \
+    if (row_w) MM_CE2S_DISPATCH_C(LAUNCH, true);      \
+    else MM_CE2S_DISPATCH_C(LAUNCH, false);           \
+  } while (0)
+
 static int ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                     int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
-                    const float* thr_cls, bool cls, float* stats, int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
+                    const float* thr_cls, bool cls, const float* row_w, float* stats, int64_t* kept, void* ws, size_t ws_bytes,
+                    hipStream_t s) {
   if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr, thr_cls, cls)) return rc;
   MM_CHECK_ARG(stats, "ce2s: null stats");
   if (ws_bytes < (size_t)S_MAX_PART * 4 * sizeof(double)) {
@@ -439,16 +486,10 @@ static int ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, co
   const int nb = (int)(nt > S_MAX_PART ? S_MAX_PART : nt);
   const size_t lds = (size_t)(tb ? 3 : 2) * ST * (C | 1) * sizeof(float);
   const float inv_t = 1.f / temperature;
-#define MM_CE2S_FWD(HAS_B, CLS)                                                                                                  \
-  hipLaunchKernelGGL((k_ce2s_fwd<HAS_B, CLS>), dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, \
-                     ta, ld_a, tb, ld_b, inv_t, thr, thr_cls, (double*)ws)
-  if (cls) {
-    if (tb) MM_CE2S_FWD(true, true);
-    else MM_CE2S_FWD(false, true);
-  } else {
-    if (tb) MM_CE2S_FWD(true, false);
-    else MM_CE2S_FWD(false, false);
-  }
+#define MM_CE2S_FWD(HAS_B, CLS, RW)                                                                                                  \
+  hipLaunchKernelGGL((k_ce2s_fwd<HAS_B, CLS, RW>), dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, \
+                     ta, ld_a, tb, ld_b, inv_t, thr, thr_cls, row_w, (double*)ws)
+  MM_CE2S_DISPATCH(MM_CE2S_FWD);
 #undef MM_CE2S_FWD
   hipLaunchKernelGGL(k_ce2s_finalize, dim3(1), dim3(64), 0, s, (const double*)ws, nb, labels0 ? 1 : 0, stats, kept);
   MM_LAUNCH_CHECK();
@@ -457,8 +498,8 @@ static int ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, co
 
 static int ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                     int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
-                    const float* thr_cls, bool cls, const float* stats, const float* grad_out, float* dlogits, int ld_d,
-                    hipStream_t s) {
+                    const float* thr_cls, bool cls, const float* row_w, const float* stats, const float* grad_out, float* dlogits,
+                    int ld_d, hipStream_t s) {
   if (int rc = ce2s_check(logits, ld, N, P, C, ta, ld_a, tb, ld_b, temperature, thr, thr_cls, cls)) return rc;
   MM_CHECK_ARG(ld_d >= C, "ce2s: gradient row pitch below C");
   if (N == 0) return MM_OK;
@@ -466,16 +507,10 @@ static int ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, co
   const unsigned nb = (unsigned)mm_cdiv(N, (int64_t)ST);
   const size_t lds = (size_t)(tb ? 3 : 2) * ST * (C | 1) * sizeof(float);
   const float inv_t = 1.f / temperature;
-#define MM_CE2S_BWD(HAS_B, CLS)                                                                                                  \
-  hipLaunchKernelGGL((k_ce2s_bwd<HAS_B, CLS>), dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, \
-                     ta, ld_a, tb, ld_b, inv_t, thr, thr_cls, stats, grad_out, dlogits, ld_d)
-  if (cls) {
-    if (tb) MM_CE2S_BWD(true, true);
-    else MM_CE2S_BWD(false, true);
-  } else {
-    if (tb) MM_CE2S_BWD(true, false);
-    else MM_CE2S_BWD(false, false);
-  }
+#define MM_CE2S_BWD(HAS_B, CLS, RW)                                                                                                  \
+  hipLaunchKernelGGL((k_ce2s_bwd<HAS_B, CLS, RW>), dim3(nb), dim3(ST), lds, s, logits, ld, N, P, C, labels0, weight0, ignore_index, \
+                     ta, ld_a, tb, ld_b, inv_t, thr, thr_cls, row_w, stats, grad_out, dlogits, ld_d)
+  MM_CE2S_DISPATCH(MM_CE2S_BWD);
 #undef MM_CE2S_BWD
   MM_LAUNCH_CHECK();
   return MM_OK;
@@ -485,30 +520,46 @@ static int ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, co
 int mm_ce2s_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                 int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr, float* stats,
                 int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
-  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr, nullptr, false, stats, kept,
-                  ws, ws_bytes, s);
+  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr, nullptr, false, nullptr, stats,
+                  kept, ws, ws_bytes, s);
 }
 
 int mm_ce2s_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                 int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
                 const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
-  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr, nullptr, false, stats,
-                  grad_out, dlogits, ld_d, s);
+  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr, nullptr, false, nullptr,
+                  stats, grad_out, dlogits, ld_d, s);
 }
 
 // the same pair with a threshold per class: a tail row is kept iff its confidence >= thr_cls[its arg-max class]
 int mm_ce2s_fwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                     int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, const float* thr_cls,
                     float* stats, int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
-  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, 0.f, thr_cls, true, stats, kept,
-                  ws, ws_bytes, s);
+  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, 0.f, thr_cls, true, nullptr, stats,
+                  kept, ws, ws_bytes, s);
 }
 
 int mm_ce2s_bwd_cls(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
                     int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, const float* thr_cls,
                     const float* stats, const float* grad_out, float* dlogits, int ld_d, hipStream_t s) {
-  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, 0.f, thr_cls, true, stats,
-                  grad_out, dlogits, ld_d, s);
+  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, 0.f, thr_cls, true, nullptr,
+                  stats, grad_out, dlogits, ld_d, s);
+}
+
+// the same pair with row weights of the tail rows: thr_cls != NULL wins over thr; row_w == NULL: the kernels of the entry points above
+int mm_ce2s_fwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                  int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                  const float* thr_cls, const float* row_w, float* stats, int64_t* kept, void* ws, size_t ws_bytes, hipStream_t s) {
+  return ce2s_fwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr_cls ? 0.f : thr, thr_cls,
+                  thr_cls != nullptr, row_w, stats, kept, ws, ws_bytes, s);
+}
+
+int mm_ce2s_bwd_w(const float* logits, int ld, int64_t N, int64_t P, int C, const int64_t* labels0, const float* weight0,
+                  int64_t ignore_index, const float* ta, int ld_a, const float* tb, int ld_b, float temperature, float thr,
+                  const float* thr_cls, const float* row_w, const float* stats, const float* grad_out, float* dlogits, int ld_d,
+                  hipStream_t s) {
+  return ce2s_bwd(logits, ld, N, P, C, labels0, weight0, ignore_index, ta, ld_a, tb, ld_b, temperature, thr_cls ? 0.f : thr, thr_cls,
+                  thr_cls != nullptr, row_w, stats, grad_out, dlogits, ld_d, s);
 }
 
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws, size_t ws_bytes,

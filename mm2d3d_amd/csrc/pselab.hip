@@ -5,6 +5,8 @@
 //   mm_teacher_labels_cls  the same launch with one threshold per output and class, read from the device
 //   mm_pl_adapt         the self-adaptive per-class thresholds (FreeMatch): running confidence and class mass of both outputs,
 //                       kept on the device and updated from every target batch; two launches, no atomics, no host read
+//   mm_pl_agree         per row the agreement of the 2D and the 3D prediction, w = exp(-beta * half the Jeffreys divergence of the
+//                       two softmaxes): the row weights of the pseudo-label losses; two launches, no atomics, no host read
 //   mm_pselab_refine    lib/utils/refine_pseudo_labels.py, exact: per class the lower median of the confidences by a
 //                       most-significant-digit radix select (four 8-bit passes over the order-preserving uint32 image of the
 //                       floats), threshold min(median, 0.9f), labels below it become ignore_label
@@ -210,6 +212,79 @@ __global__ __launch_bounds__(ROWS_FT) void k_pl_update(const double* __restrict_
       for (int c = 1; c < C; c++) mx = pt[c] > mx ? pt[c] : mx;
       thr[o * C + (j - 1)] = (float)((pt[j - 1] / mx) * cur[o * K]);
     }
+  }
+}
+
+// ---- 2D/3D agreement weights (mm_pl_agree; include/mm2d3d.h has the definition): per row D = half the Jeffreys divergence of the
+// two softmaxes and w = exp(-beta * D).  k_pl_agree: a capped grid walks the 128-row tiles, staged as in k_teacher_labels; a lane
+// owns a row, writes its w and carries two fp64 sums (w over all its rows, D over its finite rows, rows ascending) across the
+// workgroup's tiles; block_sum / block_count finish the workgroup.  k_pl_agree_final: one workgroup, a wave per quantity
+// (sum_partial of rows.h).  No atomics of any kind; the walk and the workspace (stats_ws) are those of k_pl_stats.
+constexpr int AGREE_FT = 256;  // threads of the finish: three quantities, a wave each
+
+__global__ __launch_bounds__(PT) void k_pl_agree(const float* __restrict__ l2, int ld2, const float* __restrict__ l3, int ld3, int64_t N,
+                                                  int C, float beta, float* __restrict__ w, double* __restrict__ psum /*[grid][2]*/,
+                                                  long long* __restrict__ pcnt /*[grid]*/) {
+  extern __shared__ float tile[];  // [2][PT][pitch]
+  __shared__ double red[PT];
+  __shared__ unsigned wcnt[PT / 64];
+  const int pitch = C | 1;
+  double sw = 0.0, sd = 0.0;
+  unsigned wn[1] = {0};  // per wave: every lane holds the wave's count (N * C < 2^31: below 2^30 rows)
+  const unsigned ntiles = (unsigned)((N + PT - 1) / PT);
+  for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const RowTile tl = row_tile<PT>(t, N);
+    __syncthreads();  // the previous tile's rows have been read
+    stage_pair(tile, l2, ld2, l3, ld3, tl, C, pitch);
+    __syncthreads();
+    bool finite = false;
+    if ((int)threadIdx.x < tl.rows) {
+      const float* a = tile + threadIdx.x * pitch;
+      const float* b = tile + (PT + threadIdx.x) * pitch;
+      finite = row_finite(a, C) && row_finite(b, C);
+      float wi = 0.f;
+      if (finite) {
+        const RowLse ra = row_lse(a, C), rb = row_lse(b, C);
+        const float la = ra.m + logf(ra.s), lb = rb.m + logf(rb.s);
+        float d = 0.f;
+#pragma unroll 1
+        for (int c = 0; c < C; c++) {
+          const float dp = expf(a[c] - ra.m) / ra.s - expf(b[c] - rb.m) / rb.s;
+          if (dp != 0.f) d += dp * ((a[c] - la) - (b[c] - lb));  // dp == 0: the limit 0 (a log ratio may be infinite for logits 2^128 apart)
+        }
+        d = fmaxf(0.5f * d, 0.f);  // every term is >= 0 up to rounding
+        wi = expf(-beta * d);
+        sw += (double)wi;
+        sd += (double)d;
+      }
+      w[tl.row0 + threadIdx.x] = wi;
+    }
+    wn[0] += wave_count(finite);
+  }
+  const double a = block_sum<PT>(sw, red), b = block_sum<PT>(sd, red);
+  if (threadIdx.x == 0) psum[2 * (int64_t)blockIdx.x] = a, psum[2 * (int64_t)blockIdx.x + 1] = b;
+  const long long n = block_count<PT>(wn, wcnt);
+  if (threadIdx.x == 0) pcnt[blockIdx.x] = n;
+}
+
+// stats[0] = sum w / N (0 when N == 0), stats[1] = sum D / n over the n finite rows (0 when n == 0), finite[0] = n
+__global__ __launch_bounds__(AGREE_FT) void k_pl_agree_final(const double* __restrict__ psum, const long long* __restrict__ pcnt, int nb,
+                                                             int64_t N, float* __restrict__ stats, int64_t* __restrict__ finite) {
+  __shared__ double tot[2];
+  __shared__ long long cnt;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave < 2) {  // uniform per wave
+    const double v = sum_partial(psum, nb, 2, wave, lane);
+    if (lane == 0) tot[wave] = v;
+  } else if (wave == 2) {
+    const long long n = sum_partial(pcnt, nb, 1, 0, lane);
+    if (lane == 0) cnt = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    stats[0] = N > 0 ? (float)(tot[0] / (double)N) : 0.f;
+    stats[1] = cnt > 0 ? (float)(tot[1] / (double)cnt) : 0.f;
+    if (finite) finite[0] = (int64_t)cnt;
   }
 }
 
@@ -420,6 +495,30 @@ int mm_pl_adapt(const float* logits2d, int ld2, const float* logits3d, int ld3, 
   }
   hipLaunchKernelGGL(k_pl_update, dim3(1), dim3(ROWS_FT), 0, s, (const double*)w.psum, (const long long*)w.pcnt, nb, C, momentum,
                      warmup ? 1 : 0, state, count, thr);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+size_t mm_pl_agree_ws_bytes() { return stats_ws(nullptr, 2, 1).bytes; }
+
+int mm_pl_agree(const float* logits2d, int ld2, const float* logits3d, int ld3, int64_t N, int C, float beta, float* w, float* stats,
+                int64_t* finite, void* ws, size_t ws_bytes, hipStream_t s) {
+  MM_CHECK_ARG(C >= 2 && C <= MM_PRED_MAXC, "pl_agree: C must lie in [2, 32]");
+  MM_CHECK_ARG(ld2 >= C && ld3 >= C, "pl_agree: row pitch below C");
+  MM_CHECK_ARG(beta > 0.f && beta <= 3.0e38f, "pl_agree: beta must be a finite number > 0");
+  MM_CHECK_ARG(N >= 0 && N <= (((int64_t)1 << 31) - 1) / C, "pl_agree: N * C must stay below 2^31");
+  MM_CHECK_ARG(N == 0 || (logits2d && logits3d && w), "pl_agree: null logits or w");
+  MM_CHECK_ARG(stats, "pl_agree: null stats");
+  MM_CHECK_ARG(ws && ws_bytes >= mm_pl_agree_ws_bytes(), "pl_agree: workspace missing or too small");
+  const StatsWs p = stats_ws(ws, 2, 1);
+  const int64_t nt = mm_cdiv(N, PT);
+  const int nb = (int)(nt > ROWS_MAX_WG ? ROWS_MAX_WG : nt);
+  if (nb > 0) {
+    const size_t lds = (size_t)2 * PT * (C | 1) * sizeof(float);  // <= 33 KB
+    hipLaunchKernelGGL(k_pl_agree, dim3(nb), dim3(PT), lds, s, logits2d, ld2, logits3d, ld3, N, C, beta, w, p.psum, p.pcnt);
+    MM_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_pl_agree_final, dim3(1), dim3(AGREE_FT), 0, s, (const double*)p.psum, (const long long*)p.pcnt, nb, N, stats, finite);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

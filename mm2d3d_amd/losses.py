@@ -4,7 +4,8 @@
 in the reference; ``cross_entropy`` (weighted, ignore_index -100, weighted-mean reduction = torch's
 ``F.cross_entropy`` default) and the cross-modal KL of train.py:157-184 run as single fused kernels; ``lovasz_softmax`` sorts its
 errors per class with the segmented radix sort of csrc/lovasz.hip; ``target_entropy`` (entropy minimisation and its diversity guard on
-unlabelled rows) runs on the row kernels of csrc/infomax.hip.
+unlabelled rows) runs on the row kernels of csrc/infomax.hip; ``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
+tail row (``pselab.agreement_weights``) through a compile-time flag of the same kernels.
 """
 from __future__ import annotations
 
@@ -99,10 +100,11 @@ def _class_weights(w, C, device, who, which):
 
 class _CrossEntropyPairFn(torch.autograd.Function):
     """Rows [0, split) of ``logits`` against (labels0, weight0), rows [split, N) against (labels1, weight1): one forward call,
-    and ONE backward launch that writes the whole gradient from both upstream gradients (csrc/loss.hip k_ce_*<2>)."""
+    and ONE backward launch that writes the whole gradient from both upstream gradients (csrc/loss.hip k_ce_*<2>).  ``row_w``
+    (float32 [N - split], a constant of the gradient, or None): the tail's row weights, through mm_ce2_*_w."""
 
     @staticmethod
-    def forward(ctx, logits, split, labels0, weight0, labels1, weight1, ignore_index, zero_bits):
+    def forward(ctx, logits, split, labels0, weight0, labels1, weight1, ignore_index, zero_bits, row_w=None):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
@@ -110,27 +112,51 @@ class _CrossEntropyPairFn(torch.autograd.Function):
         N, C = logits.shape
         stats = torch.empty(4, dtype=F32, device=logits.device)
         ws = _lib.workspace.get(int(L.mm_ce2_ws_bytes()), logits.device)
-        check(L.mm_ce2_fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
-                           zero_bits, ptr(stats), ptr(ws), ws.numel(), stream()), "ce2_fwd")
-        ctx.save_for_backward(logits, labels0, weight0, labels1, weight1, stats)
+        if row_w is None:
+            check(L.mm_ce2_fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                               zero_bits, ptr(stats), ptr(ws), ws.numel(), stream()), "ce2_fwd")
+        else:
+            check(L.mm_ce2_fwd_w(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                                 zero_bits, ptr(row_w), ptr(stats), ptr(ws), ws.numel(), stream()), "ce2_fwd_w")
+        ctx.save_for_backward(logits, labels0, weight0, labels1, weight1, stats, row_w)
         ctx.args = (ld, split, ignore_index)
         return stats[0], stats[2]
 
     @staticmethod
     def backward(ctx, g0, g1):
         L = _lib.lib()
-        logits, labels0, weight0, labels1, weight1, stats = ctx.saved_tensors
+        logits, labels0, weight0, labels1, weight1, stats, row_w = ctx.saved_tensors
         ld, split, ignore_index = ctx.args
         N, C = logits.shape
         g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
-        d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
-            L.mm_ce2_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
-                         ptr(stats), ptr(g), ptr(d), C, stream()), "ce2_bwd"))
-        return d, None, None, None, None, None, None, None
+        if row_w is None:
+            launch = lambda d: check(
+                L.mm_ce2_bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                             ptr(stats), ptr(g), ptr(d), C, stream()), "ce2_bwd")
+        else:
+            launch = lambda d: check(
+                L.mm_ce2_bwd_w(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ptr(labels1), ptr(weight1), ignore_index,
+                               ptr(row_w), ptr(stats), ptr(g), ptr(d), C, stream()), "ce2_bwd_w")
+        return _grad_rows(logits, ctx.in_dtype, launch), None, None, None, None, None, None, None, None
+
+
+def _row_weight(w, n, device, who, which):
+    """The checked row weights of a segment of ``n`` rows: a float32 ``[n]`` tensor on ``device`` that does not require grad (the
+    weights are constants of the gradient), contiguous; ``None`` stays ``None``."""
+    if w is None:
+        return None
+    if not torch.is_tensor(w) or w.dtype != F32 or tuple(w.shape) != (n,):
+        got = f"{w.dtype} {tuple(w.shape)}" if torch.is_tensor(w) else type(w).__name__
+        raise ValueError(f"{who}: {which} must be a float32 tensor [{n}] (one weight per tail row), not {got}")
+    if w.requires_grad:
+        raise ValueError(f"{who}: {which} requires grad, but the row weights are not differentiated: detach it")
+    if w.device != device:
+        raise ValueError(f"{who}: {which} lives on {w.device}, pred on {device}")
+    return w.contiguous()
 
 
 def cross_entropy_pair(pred, split, gt_head=None, gt_tail=None, weight_head=None, weight_tail=None, ignore_index=-100,
-                       zero_if_empty=(False, True)):
+                       zero_if_empty=(False, True), row_weight_tail=None):
     """``(loss_head, loss_tail)``: the cross entropy of rows ``[0, split)`` of ``pred`` [N, C] against ``gt_head`` and of rows
     ``[split, N)`` against ``gt_tail`` - each ``cross_entropy``'s weighted mean over its own counted rows - from one pass over
     ``pred`` per direction (the joined [source | target] step: supervised loss on the source rows, pseudo-label loss on the target
@@ -141,28 +167,35 @@ def cross_entropy_pair(pred, split, gt_head=None, gt_tail=None, weight_head=None
 
     ``zero_if_empty[s]``: a segment in which nothing is counted (every label ignored, or no rows) gives loss ``0.0`` and a zero
     gradient.  This DEVIATES from ``F.cross_entropy`` (and from ``cross_entropy``), which return nan = 0/0: a target batch whose
-    pseudo labels were all refined away must not poison the step, so the tail's default is True; the head keeps torch's nan."""
+    pseudo labels were all refined away must not poison the step, so the tail's default is True; the head keeps torch's nan.
+
+    ``row_weight_tail`` (float32 device tensor ``[N - split]``, e.g. ``pselab.agreement_weights``; not differentiated, a tensor
+    that requires grad is refused): ``loss_tail`` = ``sum_i row_w_i * w[y_i] * ce_i / sum_i w[y_i]`` over the counted tail rows -
+    the weights scale the rows' terms and gradient rows and are NOT in the denominator, so an uncertain batch pulls less.  A row
+    of weight 0 is still counted.  ``None``: the call is launch for launch the call without the option."""
     if pred.dim() != 2:
         raise ValueError("cross_entropy_pair: pred must be [N, C]")
     N, split = int(pred.shape[0]), int(split)
     if not 0 <= split <= N:
         raise ValueError(f"cross_entropy_pair: split {split} outside [0, {N}]")
     who, dev, C = "cross_entropy_pair", pred.device, int(pred.shape[1])
+    row_weight_tail = _row_weight(row_weight_tail, N - split, dev, who, "row_weight_tail")
     gt_head = _labels(gt_head, split, dev, ignore_index, who, "gt_head")
     gt_tail = _labels(gt_tail, N - split, dev, ignore_index, who, "gt_tail")
     weight_head = _class_weights(weight_head, C, dev, who, "weight_head")
     weight_tail = _class_weights(weight_tail, C, dev, who, "weight_tail")
     bits = (1 if zero_if_empty[0] else 0) | (2 if zero_if_empty[1] else 0)
-    return _CrossEntropyPairFn.apply(pred, split, gt_head, weight_head, gt_tail, weight_tail, int(ignore_index), bits)
+    return _CrossEntropyPairFn.apply(pred, split, gt_head, weight_head, gt_tail, weight_tail, int(ignore_index), bits, row_weight_tail)
 
 
 class _CrossEntropySoftPairFn(torch.autograd.Function):
     """Rows [0, split) of ``logits`` against (labels0, weight0), rows [split, N) against the softened distribution of the teacher
     logits: one forward call, and ONE backward launch that writes the whole gradient, recomputing the teacher's distribution
-    (csrc/loss.hip k_ce2s_*)."""
+    (csrc/loss.hip k_ce2s_*).  ``row_w`` (float32 [N - split], a constant of the gradient, or None): the tail's row weights, through
+    mm_ce2s_*_w."""
 
     @staticmethod
-    def forward(ctx, logits, split, labels0, weight0, ta, tb, temperature, thr, ignore_index):
+    def forward(ctx, logits, split, labels0, weight0, ta, tb, temperature, thr, ignore_index, row_w=None):
         _lib.require_cuda(logits, "pred")
         L = _lib.lib()
         ctx.in_dtype = logits.dtype
@@ -174,10 +207,15 @@ class _CrossEntropySoftPairFn(torch.autograd.Function):
         kept = torch.empty((), dtype=torch.int64, device=logits.device)
         ws = _lib.workspace.get(int(L.mm_ce2s_ws_bytes()), logits.device)
         cls = torch.is_tensor(thr)  # float32 [C] on the device: one threshold per class (mm_ce2s_*_cls)
-        fwd = L.mm_ce2s_fwd_cls if cls else L.mm_ce2s_fwd
-        check(fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
-                  temperature, ptr(thr) if cls else thr, ptr(stats), ptr(kept), ptr(ws), ws.numel(), stream()), "ce2s_fwd")
-        ctx.save_for_backward(logits, labels0, weight0, ta, tb, stats, thr if cls else None)
+        if row_w is None:
+            fwd = L.mm_ce2s_fwd_cls if cls else L.mm_ce2s_fwd
+            check(fwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                      temperature, ptr(thr) if cls else thr, ptr(stats), ptr(kept), ptr(ws), ws.numel(), stream()), "ce2s_fwd")
+        else:  # one entry point for both kinds of threshold: a non-NULL thr_cls wins
+            check(L.mm_ce2s_fwd_w(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                                  temperature, 0.0 if cls else thr, ptr(thr) if cls else None, ptr(row_w), ptr(stats), ptr(kept),
+                                  ptr(ws), ws.numel(), stream()), "ce2s_fwd_w")
+        ctx.save_for_backward(logits, labels0, weight0, ta, tb, stats, thr if cls else None, row_w)
         ctx.args = (ld, ld_a, ld_b, split, temperature, None if cls else thr, ignore_index)
         ctx.mark_non_differentiable(kept)
         return stats[0], stats[2], kept
@@ -185,19 +223,25 @@ class _CrossEntropySoftPairFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g0, g1, _):
         L = _lib.lib()
-        logits, labels0, weight0, ta, tb, stats, thr_cls = ctx.saved_tensors
+        logits, labels0, weight0, ta, tb, stats, thr_cls, row_w = ctx.saved_tensors
         ld, ld_a, ld_b, split, temperature, thr, ignore_index = ctx.args
         N, C = logits.shape
         g = torch.stack((g0, g1)).to(F32)  # the two upstream scalars side by side: the kernel's grad_out[2]
-        bwd = L.mm_ce2s_bwd if thr_cls is None else L.mm_ce2s_bwd_cls
-        d = _grad_rows(logits, ctx.in_dtype, lambda d: check(
-            bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
-                temperature, thr if thr_cls is None else ptr(thr_cls), ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd"))
-        return d, None, None, None, None, None, None, None, None
+        if row_w is None:
+            bwd = L.mm_ce2s_bwd if thr_cls is None else L.mm_ce2s_bwd_cls
+            launch = lambda d: check(
+                bwd(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                    temperature, thr if thr_cls is None else ptr(thr_cls), ptr(stats), ptr(g), ptr(d), C, stream()), "ce2s_bwd")
+        else:
+            launch = lambda d: check(
+                L.mm_ce2s_bwd_w(ptr(logits), ld, N, split, C, ptr(labels0), ptr(weight0), ignore_index, ptr(ta), ld_a, ptr(tb), ld_b,
+                                temperature, 0.0 if thr is None else thr, ptr(thr_cls), ptr(row_w), ptr(stats), ptr(g), ptr(d), C,
+                                stream()), "ce2s_bwd_w")
+        return _grad_rows(logits, ctx.in_dtype, launch), None, None, None, None, None, None, None, None, None
 
 
 def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, weight_head=None, temperature=1.0, threshold=None,
-                            ignore_index=-100):
+                            ignore_index=-100, row_weight=None):
     """``(loss_head, loss_tail, kept)``: rows ``[0, split)`` of ``pred`` [N, C] against the labels ``gt_head`` exactly as in
     :func:`cross_entropy_pair` (``None`` = unlabelled: loss 0, zero gradient rows), rows ``[split, N)`` against a teacher's
     DISTRIBUTION - the consistency loss of mean-teacher training, of which hard pseudo labels are the limit.
@@ -211,6 +255,11 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
     KL(q || softmax(x)) plus the entropy of q; there is no ``T^2`` factor.  Nothing kept: loss 0 and a zero gradient.  ``kept``:
     the number of kept rows, an int64 device scalar.
 
+    ``row_weight`` (float32 device tensor ``[N - split]``, e.g. ``pselab.agreement_weights``; not differentiated, a tensor that
+    requires grad is refused): ``loss_tail`` = ``(1 / K) * sum over the K kept rows of row_w_i * sum_c q_c * (logsumexp(x) - x_c)``.
+    The thresholds decide which rows are kept, the weights scale those that remain; ``kept`` ignores the weights.  ``None``: the
+    call is launch for launch the call without the option.
+
     One autograd node and one backward launch write the whole gradient of ``pred``; all three matrices may be row-pitched views
     (``stride(1) == 1``) and are read in place."""
     who = "cross_entropy_soft_pair"
@@ -221,6 +270,7 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
         raise ValueError(f"{who}: split {split} outside [0, {N}]")
     if C > 32:
         raise ValueError(f"{who}: {C} classes, the row kernels take at most 32")
+    row_weight = _row_weight(row_weight, N - split, pred.device, who, "row_weight")
     if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0.0 < float(temperature) < float("inf"):
         raise ValueError(f"{who}: temperature must be a finite number > 0, not {temperature!r}")
     if torch.is_tensor(threshold):  # one threshold per class (pselab.AdaptiveThreshold's rows); the values stay on the device
@@ -246,7 +296,7 @@ def cross_entropy_soft_pair(pred, split, gt_head, teacher, teacher_other=None, w
     weight_head = _class_weights(weight_head, C, pred.device, who, "weight_head")
     return _CrossEntropySoftPairFn.apply(pred, split, gt_head, weight_head, teacher, teacher_other, float(temperature),
                                          threshold if torch.is_tensor(threshold) else 0.0 if threshold is None else float(threshold),
-                                         int(ignore_index))
+                                         int(ignore_index), row_weight)
 
 
 class _LovaszFn(torch.autograd.Function):

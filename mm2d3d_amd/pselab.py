@@ -12,6 +12,8 @@ its class (uint8) of the 2D network, of the 3D network and of their average (tra
     AdaptiveThreshold(num_classes)           self-adaptive per-class thresholds for those labels (mm_pl_adapt): running state
                                              on the device, ``update`` / ``labels`` per target batch
                                              (selftrain.py pl_threshold="adaptive")
+    agreement_weights(logits_2d, logits_3d, beta)  per row exp(-beta * half the Jeffreys divergence of the two softmaxes): the
+                                             row weights of the pseudo-label losses (mm_pl_agree; selftrain.py pl_agreement)
     PseudoLabelWriter(path)                  collects scenes, ``close()`` writes the file
     export_pseudo_labels(trainer, dataset, path)   walks a dataset through ``TrainModel.predict_step`` into a writer
     refine_pseudo_labels(probs, labels)      lib/utils/refine_pseudo_labels.py on the GPU (mm_pselab_refine), exact: what the
@@ -99,6 +101,40 @@ def teacher_labels(logits_2d, logits_3d, ensemble=False, threshold=None, ignore_
               "teacher_labels_cls" if cls else "teacher_labels")
     out = {"label_2d": labels[0], "label_3d": labels[1], "kept": kept}
     return dict(out, prob_2d=probs[0], prob_3d=probs[1]) if with_probs else out
+
+
+def agreement_beta(beta, who="pselab.agreement_weights"):
+    """``beta`` as a float, or ``ValueError``: a finite number > 0 (a bool is not a number here)."""
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 < float(beta) < float("inf"):
+        raise ValueError(f"{who}: beta must be a finite number > 0, not {beta!r}")
+    return float(beta)
+
+
+@torch.no_grad()
+def agreement_weights(logits_2d, logits_3d, beta):
+    """Row weights from the agreement of the two modalities (mm_pl_agree; the definition is in include/mm2d3d.h): per row
+    ``D`` = half the Jeffreys divergence of ``softmax(logits_2d)`` and ``softmax(logits_3d)`` and ``w = exp(-beta * D)``, 1 where
+    the two predictions agree and towards 0 where they contradict each other; a row with a non-finite logit gets 0.  Returns
+    ``dict(weight, mean_weight, mean_div, finite)``: float32 ``[N]``, the mean of ``w`` over all rows, the mean of ``D`` over the
+    finite rows (float32 scalars) and their number (int64 scalar) - device tensors all, no host read; detached.  Row-pitched views
+    (``stride(1) == 1``) are read in place.  Two launches, bit-stable run to run."""
+    who = "agreement_weights"
+    beta = agreement_beta(beta)
+    (a, ld_a), (b, ld_b) = _logits(logits_2d, "logits_2d", who), _logits(logits_3d, "logits_3d", who)
+    if b.shape != a.shape or b.device != a.device:
+        raise ValueError(f"pselab.{who}: logits_2d and logits_3d must have the same shape and device")
+    N, C = a.shape
+    if not 2 <= C <= MAX_CLASSES:
+        raise ValueError(f"pselab.{who}: {C} classes, the row kernels take 2 to {MAX_CLASSES}")
+    w = torch.empty(N, dtype=torch.float32, device=a.device)
+    stats = torch.empty(2, dtype=torch.float32, device=a.device)
+    finite = torch.empty((), dtype=torch.int64, device=a.device)
+    L = _lib.lib()
+    with torch.cuda.device(a.device):
+        ws = _lib.workspace.get(int(L.mm_pl_agree_ws_bytes()), a.device, "pselab")
+        check(L.mm_pl_agree(ptr(a), ld_a, ptr(b), ld_b, N, C, beta, ptr(w), ptr(stats), ptr(finite), ptr(ws), ws.numel(), stream()),
+              "pl_agree")
+    return {"weight": w, "mean_weight": stats[0], "mean_div": stats[1], "finite": finite}
 
 
 # ---------------------------------------------------------------------------------------------------- adaptive thresholds

@@ -8,7 +8,8 @@ from . import gradsink, pselab
 from .losses import cross_entropy_pair, cross_entropy_soft_pair
 
 FORWARDED = ("lambda_pl", "pseudo_labels", "pseudo_label_source", "pl_threshold", "pl_threshold_momentum", "pl_threshold_warmup",
-             "pl_targets", "pl_temperature", "pl_adaptive", "last_teacher")  # the options and the state the trainer forwards by name
+             "pl_targets", "pl_temperature", "pl_adaptive", "last_teacher", "pl_agreement",
+             "last_agreement")  # the options and the state the trainer forwards by name
 
 
 class Target(NamedTuple):
@@ -70,7 +71,19 @@ class SelfTraining:
     confidence at temperature 1 against ``pl_threshold`` (None or a float; "median" works on labels and is refused), mean
     over the kept rows, no T^2 factor.  Source "teacher": the teacher pass runs as above without the label launch, and
     ``last_teacher`` = dict(logit_2d, logit_3d, kept); source "batch": the target batch carries ``teacher_logit_2d`` /
-    ``teacher_logit_3d`` [n, C] (a frozen teacher of the caller's own).  Both log ``train/pl_kept_2d`` / ``_3d``."""
+    ``teacher_logit_3d`` [n, C] (a frozen teacher of the caller's own).  Both log ``train/pl_kept_2d`` / ``_3d``.
+    ``pl_agreement`` (consulted only with ``lambda_pl`` > 0): None (default) = the step is launch for launch the step without the
+    option.  A finite number > 0 = ``beta``: every target row's pseudo-label term, in both heads, is scaled by
+    w = exp(-beta * D), D = half the Jeffreys divergence between the 2D and the 3D prediction of the row
+    (pselab.agreement_weights, mm_pl_agree) - the second signal next to the confidence: two sensors that contradict each other
+    at high confidence pull less, two that agree keep their full weight.  The thresholds decide which rows are counted or kept
+    exactly as without the option and ``pl_kept_*`` is unchanged; the weights scale the rows that remain and are not in the
+    losses' denominators (losses.cross_entropy_pair ``row_weight_tail``, cross_entropy_soft_pair ``row_weight``); they carry no
+    gradient.  Works with every source / targets / "own" - "ensemble" / threshold combination.  The two logit matrices: source
+    "teacher": the teacher's (one extra call in the teacher pass); source "batch" with soft targets: the batch's
+    ``teacher_logit_2d`` / ``_3d``; source "batch" with hard labels (the file-based round): the student's own main-head target
+    rows of this step, detached.  No state: nothing to checkpoint or to reduce.  ``last_agreement`` = dict(weight [n],
+    mean_weight, mean_div), logged as ``train/pl_agree_w`` / ``train/pl_agree_div``; device tensors all."""
 
     def __init__(self, train_kwargs, ema_decay=None, overlap_metadata=False, overlap_branches=0):
         def option(name, default, ok, must):
@@ -99,14 +112,19 @@ class SelfTraining:
         if self.pl_targets == "soft" and thr == "median":
             raise ValueError("train_kwargs['pl_threshold'] = 'median' is refused with pl_targets='soft': the refinement works on "
                              "labels; give a number in (0, 1] or None")
+        self.pl_agreement = option("pl_agreement", None, lambda v: v is None or (number(v) and 0.0 < v < float("inf")),
+                                   "None or a finite number > 0 (beta of w = exp(-beta * D))")
+        if self.pl_agreement is not None:
+            self.pl_agreement = float(self.pl_agreement)
         # checked whatever lambda_pl is: a schedule that starts at 0 must not hide a configuration that cannot run later
         why = ("ema_decay is None (the teacher is the EMA of the weights)" if ema_decay is None else
                "overlap_metadata is on" if overlap_metadata else f"overlap_branches is {overlap_branches}" if overlap_branches != 0 else None)
         if self.pseudo_label_source == "teacher" and why is not None:
             raise ValueError(f"train_kwargs['pseudo_label_source'] = 'teacher' is refused: {why}; the teacher pass runs on the "
                              "step's one stream (the side-stream modes are experimental and not extended to it)")
-        self.pl_adaptive = self.last_teacher = None
+        self.pl_adaptive = self.last_teacher = self.last_agreement = None
         self._kept = None  # this step's kept rows: the share [2] of the teacher's labels, or the counts of the two soft loss calls
+        self._agree = None  # this step's pselab.agreement_weights (pl_agreement): the teacher pass or losses() fills it
 
     def _soft(self, l2, l3, thr):
         """Per head the soft targets ("own": the head's own modality, "ensemble": both) and its row of a [2, C] threshold tensor."""
@@ -154,6 +172,8 @@ class SelfTraining:
             l2 = trainer(batch_2d, model_name=trainer.modules_name[0])[0]["seg_logit"]
             l3 = trainer(batch_3d, model_name=trainer.modules_name[1])[0]["seg_logit"][first_row:]
             C = int(l2.shape[1])
+            if self.pl_agreement is not None:  # the two matrices are at hand here: both heads' loss calls read the one vector
+                self._agree = pselab.agreement_weights(l2, l3, self.pl_agreement)
             if adaptive:  # the state takes this batch in, then judges it
                 if self.pl_adaptive is None:
                     self.pl_adaptive = pselab.AdaptiveThreshold(C, self.pl_threshold_momentum, self.pl_threshold_warmup, device=l2.device)
@@ -180,11 +200,22 @@ class SelfTraining:
     def losses(self, logits_2d, logits_3d, split, targets, gt_head=None, weight_head=None):
         """``(seg2d, seg3d, pl2d, pl3d)``, one pass per head: rows ``[0, split)`` against ``gt_head`` with the class weights, rows
         ``[split, N)`` against the head's target.  ``gt_head=None``: unlabelled head rows; the first two results are to be ignored."""
+        rw = None
+        if self.pl_agreement is not None:
+            if self.pseudo_label_source == "batch":
+                if self.pl_targets == "soft":  # the batch's teacher_logit_2d / _3d ("own": one per head; "ensemble": both in each)
+                    a, b = targets[0].value, targets[1].value if targets[0].other is None else targets[0].other
+                    a, b = a.to(logits_2d.device), b.to(logits_2d.device)
+                else:  # file-based labels: the student's own main-head target rows of this step
+                    a, b = logits_2d[split:].detach(), logits_3d[split:].detach()
+                self._agree = pselab.agreement_weights(a, b, self.pl_agreement)
+            rw = self._agree["weight"]
+
         def pair(logits, t):
             if self.pl_targets == "soft":
                 return cross_entropy_soft_pair(logits, split, gt_head, t.value, t.other, weight_head=weight_head,
-                                               temperature=self.pl_temperature, threshold=t.threshold)
-            return (*cross_entropy_pair(logits, split, gt_head, t.value, weight_head=weight_head), None)
+                                               temperature=self.pl_temperature, threshold=t.threshold, row_weight=rw)
+            return (*cross_entropy_pair(logits, split, gt_head, t.value, weight_head=weight_head, row_weight_tail=rw), None)
 
         (seg2d, pl2d, k2), (seg3d, pl3d, k3) = pair(logits_2d, targets[0]), pair(logits_3d, targets[1])
         if self.pl_targets == "soft":  # the rows the two loss calls kept: counted in their forward launches
@@ -202,6 +233,10 @@ class SelfTraining:
                 self.last_teacher["kept"] = counts
         if kept is not None:
             logs[f"{stage}/pl_kept_2d"], logs[f"{stage}/pl_kept_3d"] = kept[0], kept[1]
+        if self.pl_agreement is not None:
+            ag = self._agree
+            self.last_agreement = {k: ag[k] for k in ("weight", "mean_weight", "mean_div")}
+            logs[f"{stage}/pl_agree_w"], logs[f"{stage}/pl_agree_div"] = ag["mean_weight"], ag["mean_div"]
         if teacher and self.pl_adaptive is not None:  # this step's confidence levels, a copy: the state moves on with the next batch
             tau = self.pl_adaptive.state[:, 0].to(torch.float32)
             logs[f"{stage}/pl_tau_2d"], logs[f"{stage}/pl_tau_3d"] = tau[0], tau[1]

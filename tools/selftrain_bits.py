@@ -1,6 +1,6 @@
 """Bits of the self-training step, for comparing two checkouts of this project (a refactor against its parent).
 
-    python tools/selftrain_bits.py dump OUT.npz [--only SUBSTRING[,SUBSTRING...]]
+    python tools/selftrain_bits.py dump OUT.npz [--only SUBSTRING[,SUBSTRING...]] [--skip SUBSTRING[,SUBSTRING...]]
     python tools/selftrain_bits.py compare A.npz B.npz
 
 ``dump`` runs every self-training option combination for three ``fit_step`` calls at the shapes of tests/test_gpu_teacher_step.py
@@ -12,7 +12,9 @@ the last step every entry of the checkpoint's "state_dict" and "ema_state_dict" 
 row, the class maximum, more tiles than workgroups of both tile sizes), contiguous and as row-pitched views, every output and
 gradient as raw bytes.  It uses only ``train_kwargs``, ``fit_step``, ``last_logs``, ``last_teacher``,
 ``pl_adaptive.state_dict()``, ``checkpoint()``, ``load_checkpoint()`` and those public functions, so the same file runs in either
-checkout (it imports the package of the checkout whose ``tools/`` it lies in: copy it there).  ``compare`` demands equal key lists
+checkout (it imports the package of the checkout whose ``tools/`` it lies in: copy it there).  The ``agreement/`` cases and the
+``agreement`` direct calls (``pl_agreement``, ``pselab.agreement_weights``, the pairs' row weights) exist from the commit that added
+them on: against an older checkout dump both sides with ``--skip agreement``.  ``compare`` demands equal key lists
 and equal bytes, prints the number of arrays and the total bytes, and exits 1 on any difference.  One process per dump.
 """
 import argparse
@@ -34,6 +36,7 @@ REGISTRY = {"single": [CE], "two_entries": [dict(CE, weight=0.5), dict(CE, weigh
 STEPS = 3
 ADAPTIVE = dict(pl_threshold_momentum=0.5, pl_threshold_warmup=True)  # the thresholds bite from the first step
 PRIOR = [0.3, 0.1, 0.2, 0.1, 0.2, 0.1]
+AGREEMENT_BETA = 0.5
 DIRECT_SIZES = ((129, 5), (1000, 32), (131201, 6), (300001, 6))  # (N, C)
 
 
@@ -65,6 +68,14 @@ def cases():
     for (call, ckw), (prior, pkw) in itertools.product(calls.items(), (("uniform", {}), ("prior", dict(div_prior=PRIOR)))):
         add(f"infomax/{call}/{prior}", dict(infomax, **ckw, **pkw))
     add("infomax/joined/uniform/with_teacher_soft_adaptive", dict(teacher, **infomax, pl_targets="soft", pl_threshold="adaptive"))
+    agree = dict(pl_agreement=AGREEMENT_BETA)  # pseudo-label losses weighted by 2D/3D agreement
+    add("agreement/teacher/hard/own/joined", dict(teacher, **agree))
+    add("agreement/teacher/hard/ensemble/thr_median/joined", dict(teacher, **agree, pseudo_labels="ensemble", pl_threshold="median"))
+    add("agreement/teacher/hard/own/two_calls", dict(teacher, **agree, joint_domains=False))
+    add("agreement/teacher/soft/ensemble/thr_adaptive/joined", dict(teacher, **agree, pseudo_labels="ensemble", pl_targets="soft", pl_threshold="adaptive"))
+    add("agreement/batch/hard/own/joined", dict(lambda_pl=1.0, **agree), extras="labels")
+    add("agreement/batch/soft/own/thr_0.9/T_2.0", dict(lambda_pl=1.0, **agree, pl_targets="soft", pl_threshold=0.9, pl_temperature=2.0),
+        extras="logits")
     return out
 
 
@@ -107,7 +118,9 @@ def _batch(dev, extras, step):
     return b
 
 
-def _wanted(name, only):
+def _wanted(name, only, skip=None):
+    if skip and any(part in name for part in skip.split(",")):
+        return False
     return not only or any(part in name for part in only.split(","))
 
 
@@ -155,7 +168,7 @@ def _direct_inputs(N, C, pitched, dev):
     return out[0], out[1], out[2], y.to(dev)
 
 
-def direct_cases(put, dev, only=None):
+def direct_cases(put, dev, only=None, skip=None):
     """The ``direct/`` group: every public entry of the row kernels at DIRECT_SIZES."""
     import torch
 
@@ -163,7 +176,7 @@ def direct_cases(put, dev, only=None):
 
     for (N, C), pitched in itertools.product(DIRECT_SIZES, (False, True)):
         base = f"direct/{N}_{C}/{'pitched' if pitched else 'contiguous'}"
-        if not _wanted(base, only):
+        if not _wanted(base, only, skip):
             continue
         x, a, b, y = _direct_inputs(N, C, pitched, dev)
         P = N // 2
@@ -194,11 +207,24 @@ def direct_cases(put, dev, only=None):
             ent, div, mass, count = losses.target_entropy(xg, first, pr)
             (grad,) = torch.autograd.grad(ent + 0.5 * div, xg)
             put_all(f"target_entropy/first_{first}/{pname}", dict(ent=ent, div=div, mass=mass, count=count, grad=grad))
+        if _wanted(f"{base}/agreement", only, skip):  # the weights of the tail rows, then both pairs under them
+            ag = pselab.agreement_weights(a[P:], b[P:], AGREEMENT_BETA)
+            put_all("agreement/weights", ag)
+            y1 = y[P:].roll(1)
+            for tname, thr in (("scalar", 0.6), ("per_class", thr2[0].contiguous())):
+                xg = x.detach().requires_grad_(True)
+                lh, lt, kept = losses.cross_entropy_soft_pair(xg, P, y[:P], a[P:], b[P:], temperature=2.0, threshold=thr, row_weight=ag["weight"])
+                (grad,) = torch.autograd.grad(lh + lt, xg)
+                put_all(f"agreement/soft_pair/{tname}", dict(head=lh, tail=lt, kept=kept, grad=grad))
+            xg = x.detach().requires_grad_(True)
+            lh, lt = losses.cross_entropy_pair(xg, P, y[:P], y1, weight_head=prior, row_weight_tail=ag["weight"])
+            (grad,) = torch.autograd.grad(lh + lt, xg)
+            put_all("agreement/hard_pair", dict(head=lh, tail=lt, grad=grad))
         torch.cuda.synchronize()
         print(f"{base}: done", flush=True)
 
 
-def dump(path, only=None):
+def dump(path, only=None, skip=None):
     import torch
 
     if not torch.cuda.is_available():
@@ -214,7 +240,7 @@ def dump(path, only=None):
         count, nbytes = count + 1, nbytes + arr.nbytes
 
     for name, (kw, registry, extras, prefetch, resume) in cases().items():
-        if not _wanted(name, only):
+        if not _wanted(name, only, skip):
             continue
         tm = _trainer(dev, kw, registry)
         batches = [_batch(dev, extras, s) for s in range(STEPS)]
@@ -232,6 +258,8 @@ def dump(path, only=None):
             for k, v in (tm.last_teacher or {}).items():
                 if torch.is_tensor(v):
                     put(f"{name}/step{s}/last_teacher/{k}", _raw(v))
+            for k, v in (getattr(tm, "last_agreement", None) or {}).items():
+                put(f"{name}/step{s}/last_agreement/{k}", _raw(v))
         ckpt = tm.checkpoint()
         for part in ("state_dict", "ema_state_dict"):
             for k, v in ckpt[part].items():
@@ -244,7 +272,7 @@ def dump(path, only=None):
               f"last_teacher {sorted(tm.last_teacher) if tm.last_teacher else None}", flush=True)
         _forget(tm)
         del tm, ckpt, batches
-    direct_cases(put, dev, only)
+    direct_cases(put, dev, only, skip)
     archive.close()
     print(f"{count} arrays, {nbytes} bytes -> {path}", flush=True)
 
@@ -278,12 +306,13 @@ def main():
     d = sub.add_parser("dump")
     d.add_argument("out")
     d.add_argument("--only", default=None, help="run the cases whose name contains one of these (comma-separated)")
+    d.add_argument("--skip", default=None, help="leave out the cases and direct calls whose name contains one of these (comma-separated)")
     c = sub.add_parser("compare")
     c.add_argument("a")
     c.add_argument("b")
     args = ap.parse_args()
     if args.cmd == "dump":
-        dump(args.out, args.only)
+        dump(args.out, args.only, args.skip)
     else:
         raise SystemExit(compare(args.a, args.b))
 
