@@ -551,6 +551,37 @@ int mm_im_fwd(const float* logits, int ld, int64_t N, int64_t P, int C, const fl
               int64_t* count, float* aux, void* ws, size_t ws_bytes, mm_stream_t stream);
 int mm_im_bwd(const float* logits, int ld, int64_t N, int64_t P, int C, const float* aux, const float* grad_out, float* dlogits,
               int ld_d, mm_stream_t stream);
+/* Correlation alignment of two row segments (Deep CORAL, Sun & Saenko, ECCV-W 2016; Deep LogCORAL, Morerio et al., ICLR 2018;
+ * csrc/coral.hip).  x: fp32 [N, d], row pitch ld, 2 <= d <= 32.  Rows [0, P) are segment s (source), rows [P, N) segment t (target).
+ * A row is counted when its d values are all finite; n_s, n_t of them.  Per segment a, in fp64 from fp64 sums of x and of x xT:
+ *   m_a = the mean of the counted rows (0 when there is none);
+ *   C_a = 1 / (n_a - 1) * sum_i (x_i - m_a)(x_i - m_a)T      (0 when n_a < 2).
+ * mode 0 (plain, Deep CORAL):    L = || C_s - C_t ||_F^2 / (4 d^2);
+ * mode 1 (log, Deep LogCORAL):   L = || log(C_s + eps I) - log(C_t + eps I) ||_F^2 / d^2, log the matrix logarithm through the
+ *   symmetric eigendecomposition C_a + eps I = V diag(lambda) VT (cyclic Jacobi in fp64, in the kernel), eps > 0 a ridge: a
+ *   segment with fewer counted rows than d, or a constant column, has a singular covariance.  An eigenvalue that rounding has
+ *   pushed below eps is taken as eps.  Eigenvector signs and order do not enter the result.
+ * n_s < 2 or n_t < 2: L = 0 and the gradient is zero (never 0 / 0).
+ * Gradient, for both segments: dL/dx_i = 2 / (n_a - 1) * (x_i - m_a) * G_a for a counted row, +0 in every bit for any other row
+ * (the derivative of the mean drops out: the centred rows sum to zero).  plain: G_s = -G_t = (C_s - C_t) / (2 d^2).  log, with
+ * Delta = log(C_s + eps I) - log(C_t + eps I): G_a = +- (2 / d^2) * V [(VT Delta V) o K] VT (+ for s, - for t; Daleckii-Krein),
+ * K_ii = 1 / lambda_i (0 for an eigenvalue that was raised to eps), K_ij = (log lambda_i - log lambda_j) / (lambda_i - lambda_j),
+ * evaluated as log1p(t) / (t lambda_j), t = (lambda_i - lambda_j) / lambda_j, from the smaller eigenvalue, with its series for
+ * tiny t: close or equal eigenvalues lose no digits and never divide by zero.
+ * Outputs of the forward: loss[1]; count[2] = n_s, n_t (int64, exact); mean[2][d], cov[2][d][d] (fp32, for callers and logs);
+ * aux[4 d + 2 d^2] = m_s, m_t in fp32, then what that rounding left of the fp64 means (so that x_i - m_a rounds once in the
+ * backward, also for a row close to the mean), then the two matrices 2 / (n_a - 1) * G_a, row-major - what the backward reads.
+ * The backward writes every one of the N rows once: dx_i = grad_out[0] * (x_i - m_a) * aux_a in fp32.  grad_out and aux are read on the
+ * device: no host read anywhere.  Refused before any launch, with no output touched: d outside [2, 32], ld or ld_dx below d,
+ * P outside [0, N], N * d >= 2^31, a null operand, a missing or short workspace, eps not finite or <= 0, an unknown mode.
+ * N == 0 and P == N are legal and give loss 0.  mm_coral_ws_bytes returns 0 for a d outside the limits.  Two launches forward
+ * (fp64 sums and integer row counts per workgroup of a capped grid; one workgroup that totals them in a fixed order, diagonalises
+ * and writes the outputs), one backward.  No atomics, no workgroup waits for another: bit-stable run to run. */
+size_t mm_coral_ws_bytes(int d);
+int mm_coral_fwd(const float* x, int ld, int64_t N, int64_t P, int d, int mode, float eps, float* loss, int64_t* count, float* mean,
+                 float* cov, float* aux, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_coral_bwd(const float* x, int ld, int64_t N, int64_t P, int d, const float* aux, const float* grad_out, float* dx, int ld_dx,
+                 mm_stream_t stream);
 /* mean_i sum_c softmax(tgt)_ic (log softmax(tgt)_ic - log softmax(pred)_ic)  (EXP/train.py:157-184) */
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws,
               size_t ws_bytes, mm_stream_t stream);

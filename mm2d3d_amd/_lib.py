@@ -124,6 +124,9 @@ _PROTOS = {
     "mm_im_ws_bytes": (sz, []),
     "mm_im_fwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mm_im_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, i32, vp]),
+    "mm_coral_ws_bytes": (sz, [i32]),
+    "mm_coral_fwd": (i32, [vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mm_coral_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, i32, vp]),
     "mm_kl_fwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, sz, vp]),
     "mm_kl_bwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, i32, vp]),
     "mm_lift_index_ws_bytes": (sz, [i64]),

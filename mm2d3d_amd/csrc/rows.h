@@ -1,21 +1,24 @@
-// The row toolkit of the kernels that give a lane one row of per-point logits [N, C] (loss.hip, lovasz.hip, pselab.hip, infomax.hip).
+// The row toolkit of the kernels that give a lane one row of per-point logits [N, C] (loss.hip, lovasz.hip, pselab.hip, infomax.hip,
+// coral.hip).
 // ONE expression each, so that two kernels over the same rows agree bit for bit:
 //   label_counted, row_lse, ce_grad_row    which labels count, the row's log-sum-exp, the cross-entropy gradient row
 //                                          (loss.hip k_ce_*, k_ce2s_*; lovasz.hip; infomax.hip)
-//   row_finite                             a row without a NaN or an infinity (k_im_stats, k_im_bwd, k_pl_agree)
+//   row_finite                             a row without a NaN or an infinity (k_im_stats, k_im_bwd, k_pl_agree, k_coral_*)
 //   wave_sum, block_sum                    the fixed-order sums of a wave and of a workgroup
 //   sum_partials<K>                        one wave over the [nb][K] partials of the pass before (k_ce_finalize, k_ce2s_finalize,
 //                                          k_kl_finalize, lovasz.hip)
-//   sum_partial                            the same with K known at run time, one quantity per call (k_pl_update, k_im_final)
+//   sum_partial                            the same with K known at run time, one quantity per call (k_pl_update, k_im_final,
+//                                          k_coral_final)
 //   row_tile, tile_head                    the rows of tile t, and where a tile's tail rows begin (k_pselab_predict,
-//                                          k_teacher_labels, k_pl_stats, k_pl_agree, k_im_stats, k_im_bwd, k_ce2s_fwd, k_ce2s_bwd)
+//                                          k_teacher_labels, k_pl_stats, k_pl_agree, k_im_stats, k_im_bwd, k_ce2s_fwd, k_ce2s_bwd,
+//                                          k_coral_stats, k_coral_bwd)
 //   stage_rows, unstage_rows               global memory -> pitched LDS tile and back, coalesced (every kernel above; out:
-//                                          k_im_bwd, k_ce2s_bwd)
+//                                          k_im_bwd, k_ce2s_bwd, k_coral_bwd)
 //   wave_count, block_count                counted rows: ballots per wave, totals through LDS (k_teacher_labels, k_pl_stats,
-//                                          k_im_stats)
+//                                          k_im_stats, k_coral_stats)
 //   col_sum                                a column of a staged tile into an fp64 accumulator, rows ascending (k_pl_stats, k_im_stats)
 //   stats_ws, ROWS_MAX_WG, ROWS_FT         the workspace and the sizes of a capped-grid statistics pass and its one-workgroup
-//                                          finish (mm_pl_adapt, mm_pl_agree, mm_im_fwd)
+//                                          finish (mm_pl_adapt, mm_pl_agree, mm_im_fwd, mm_coral_fwd)
 // (mm_point_predict of pointpred.h keeps its own strict `>` maximum scan: it also tracks the argmax and differs from fmaxf on NaN
 // rows.)  Row pointers may be global memory or LDS: the address space is inferred after inlining.
 #pragma once

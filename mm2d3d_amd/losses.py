@@ -4,7 +4,8 @@
 in the reference; ``cross_entropy`` (weighted, ignore_index -100, weighted-mean reduction = torch's
 ``F.cross_entropy`` default) and the cross-modal KL of train.py:157-184 run as single fused kernels; ``lovasz_softmax`` sorts its
 errors per class with the segmented radix sort of csrc/lovasz.hip; ``target_entropy`` (entropy minimisation and its diversity guard on
-unlabelled rows) runs on the row kernels of csrc/infomax.hip; ``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
+unlabelled rows) runs on the row kernels of csrc/infomax.hip; ``coral`` (Deep CORAL / LogCORAL alignment of the source and the target
+rows' covariances) on those of csrc/coral.hip; ``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
 tail row (``pselab.agreement_weights``) through a compile-time flag of the same kernels.
 """
 from __future__ import annotations
@@ -454,6 +455,82 @@ def target_entropy(pred, first_row=0, prior=None):
         raise ValueError(f"{who}: the prior has {len(prior)} entries for C = {C} classes")
     _lib.require_cuda(pred, "pred")
     return _TargetEntropyFn.apply(pred, first_row, _device_prior(prior, pred.device))
+
+
+CORAL_MODES = {"plain": 0, "log": 1}  # the ``mode`` of mm_coral_fwd
+
+
+class _CoralFn(torch.autograd.Function):
+    """Correlation alignment of the rows [0, first_row) and [first_row, N) of ``x`` (csrc/coral.hip): two forward launches leave the
+    loss, the two row counts, means and covariances and ``aux`` (the means as fp32 pairs and the two matrices 2 / (n_a - 1) * G_a); ONE backward
+    launch writes the whole gradient from the upstream gradient and ``aux``."""
+
+    @staticmethod
+    def forward(ctx, x, first_row, mode, eps):
+        _lib.require_cuda(x, "x")
+        L = _lib.lib()
+        ctx.in_dtype = x.dtype
+        x, ld = _lib.row_pitched(x)
+        N, d = x.shape
+        dev = x.device
+        loss = torch.empty((), dtype=F32, device=dev)
+        mean, cov, aux = (torch.empty(s, dtype=F32, device=dev) for s in ((2, d), (2, d, d), (4 * d + 2 * d * d,)))
+        count = torch.empty(2, dtype=torch.int64, device=dev)
+        ws = _lib.workspace.get(int(L.mm_coral_ws_bytes(d)), dev)
+        check(L.mm_coral_fwd(ptr(x), ld, N, first_row, d, mode, eps, ptr(loss), ptr(count), ptr(mean), ptr(cov), ptr(aux), ptr(ws),
+                             ws.numel(), stream()), "coral_fwd")
+        ctx.save_for_backward(x, aux)
+        ctx.args = (ld, first_row)
+        ctx.mark_non_differentiable(count, mean, cov)
+        ctx.set_materialize_grads(False)  # else every backward fills zero gradients for the three detached outputs
+        return loss, count, mean, cov
+
+    @staticmethod
+    def backward(ctx, g, _count, _mean, _cov):
+        if g is None:
+            return None, None, None, None
+        L = _lib.lib()
+        x, aux = ctx.saved_tensors
+        ld, first_row = ctx.args
+        N, d = x.shape
+        g = g.to(F32).contiguous()
+        dx = _grad_rows(x, ctx.in_dtype, lambda dx: check(
+            L.mm_coral_bwd(ptr(x), ld, N, first_row, d, ptr(aux), ptr(g), ptr(dx), d, stream()), "coral_bwd"))
+        return dx, None, None, None
+
+
+def coral(x, first_row, mode="log", eps=1e-4):
+    """Correlation alignment of two row segments of ``x`` [N, d]: rows ``[0, first_row)`` (source) against rows ``[first_row, N)``
+    (target) of a joined [source | target] pass.  Returns ``dict(loss, count, mean, cov)``, all device tensors.  Counted are the
+    rows whose values are all finite, ``count`` (int64 [2]) of them per segment; ``mean`` [2, d] and ``cov`` [2, d, d] (fp32) are
+    their means and unbiased covariances C_s, C_t.  ``mode="plain"``: Deep CORAL (Sun & Saenko, ECCV-W 2016), ``loss`` =
+    ||C_s - C_t||_F^2 / (4 d^2).  ``mode="log"`` (default): Deep LogCORAL (Morerio et al., ICLR 2018; the uni-modal baseline of the
+    xMUDA comparison), ``loss`` = ||log(C_s + eps I) - log(C_t + eps I)||_F^2 / d^2 with the matrix logarithm of the symmetric
+    eigendecomposition, which the kernel computes itself (cyclic Jacobi in fp64); the ridge ``eps`` > 0 keeps a singular covariance (fewer
+    counted rows than d, a constant column) finite.  A segment with fewer than two counted rows: loss 0, a zero gradient.
+
+    ``loss`` is differentiable with respect to BOTH segments' rows; one autograd node, two forward launches and one backward
+    launch, no host read; ``count``, ``mean`` and ``cov`` are detached.  The statistics are those of THIS call's rows: under
+    data parallelism each rank's own batch's, as batch-norm statistics are, not reduced over ranks.  Generic in d (2 to 32): the
+    class logits of a head, or a feature matrix such as the 3D branch's 16-channel ``feats``.  ``x`` may be fp16, bf16 or a
+    row-pitched view (``stride(1) == 1``), which is read in place.  Bit-stable run to run."""
+    who = "coral"
+    if not isinstance(mode, str) or mode not in CORAL_MODES:
+        raise ValueError(f'{who}: mode must be "log" or "plain", not {mode!r}')
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < float(eps) < float("inf"):
+        raise ValueError(f"{who}: eps must be a finite number > 0, not {eps!r}")
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"{who}: x must be [N, d]")
+    N, d = int(x.shape[0]), int(x.shape[1])
+    if not 2 <= d <= 32:
+        raise ValueError(f"{who}: {d} columns, the row kernels take 2 to 32")
+    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
+        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
+    if N * d >= 1 << 31:
+        raise ValueError(f"{who}: {N} rows of {d} columns, N * d must stay below 2^31")
+    _lib.require_cuda(x, "x")
+    loss, count, mean, cov = _CoralFn.apply(x, first_row, CORAL_MODES[mode], float(eps))
+    return dict(loss=loss, count=count, mean=mean, cov=cov)
 
 
 class _KLFn(torch.autograd.Function):

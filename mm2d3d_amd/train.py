@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, domains, infomax
+from . import _lib, coral, domains, infomax
 from .ddp import GradAllReducer, ranks_share_a_gpu
 from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
@@ -120,6 +120,8 @@ class TrainModel(nn.Module):
         self.selftrain = SelfTraining(train_kwargs, self.ema_decay, self.overlap_metadata, self.overlap_branches)
         # entropy / diversity terms on the target rows (``lambda_minent``, ``lambda_div``, ``div_prior``): infomax.TargetEntropy, forwarded too
         self.target_entropy = infomax.TargetEntropy(train_kwargs)
+        # correlation alignment of the source and the target rows' logits (``lambda_coral``, ``coral``, ``coral_eps``): coral.DomainAlignment, forwarded too
+        self.alignment = coral.DomainAlignment(train_kwargs)
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -219,7 +221,7 @@ class TrainModel(nn.Module):
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
-        st, te = self.selftrain, self.target_entropy
+        st, te, al = self.selftrain, self.target_entropy, self.alignment
         te.begin_step(self)
         teacher = st.lambda_pl > 0 and st.pseudo_label_source == "teacher"
         pseudo = st.batch_targets(trg) if st.lambda_pl > 0 and not teacher else None
@@ -313,6 +315,7 @@ class TrainModel(nn.Module):
             xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
             im = te.terms(l2d, l3d, P)
+            ca = al.terms(l2d, l3d, P)
         else:
             if teacher:
                 own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
@@ -323,6 +326,7 @@ class TrainModel(nn.Module):
             seg3d = self.loss("segmentation", pred=p3d["seg_logit"], gt=src["seg_label"])
             xs2d, xs3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
                                                aux3d["seg_logit_point"])
+            src2d, src3d = p2d["seg_logit"], p3d["seg_logit"]
             p2d, _, _, aux2d = self(trg, model_name=n2d)
             p3d, _, aux3d = self(trg, model_name=n3d)
             xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
@@ -330,6 +334,8 @@ class TrainModel(nn.Module):
             if pseudo is not None:
                 _, _, pl2d, pl3d = st.losses(p2d["seg_logit"], p3d["seg_logit"], 0, pseudo)
             im = te.terms(p2d["seg_logit"], p3d["seg_logit"], 0)
+            # the two calls' logits side by side, as the joined pass has them: the source's rows first
+            ca = al.terms(torch.cat((src2d, p2d["seg_logit"])), torch.cat((src3d, p3d["seg_logit"])), int(src2d.shape[0])) if al.active else None
         self.last_logs = {
             f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
@@ -343,6 +349,8 @@ class TrainModel(nn.Module):
             st.log(self.last_logs, stage, pl2d, pl3d, trg["x"][0].shape[0])
         if im is not None:
             loss_2d, loss_3d = te.add(self.last_logs, stage, loss_2d, loss_3d, im)
+        if ca is not None:
+            loss_2d, loss_3d = al.add(self.last_logs, stage, loss_2d, loss_3d, ca)
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
@@ -662,7 +670,7 @@ class TrainModel(nn.Module):
         return loss
 
 
-for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED)):
+for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED), ("alignment", coral.FORWARDED)):
     for _name in _names:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
         setattr(TrainModel, _name, property(lambda self, n=_name, o=_owner: getattr(getattr(self, o), n),
                                             lambda self, value, n=_name, o=_owner: setattr(getattr(self, o), n, value)))

@@ -1,0 +1,144 @@
+"""Correlation alignment in the training step: train_kwargs["lambda_coral"], ["coral"] and ["coral_eps"] (mm2d3d_amd/coral.py,
+losses.coral).  Shapes and helpers of tests/_step_util.py: 1 + 1 synthetic nuScenes scenes with 48x64 images, 6 classes, fp16,
+dropout p = 0.  The two new terms are held to ``losses.coral`` evaluated on the logits the heads produced in that very step (forward
+hooks): the same kernels on the same rows, so the same bits; tests/test_gpu_coral.py holds those kernels to the float64 reference."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import _step_util as T
+from _step_util import _BUILT, _release_memory, _restore_precision  # noqa: F401  (the autouse fixtures, for this module too)
+
+pytestmark = pytest.mark.gpu
+
+NEW_KEYS = ("train/coral_2d", "train/coral_3d")
+OLD_KEYS = ("train/loss_segmentation", "train/loss_segmentation_3d", "train/xm_loss_src_2d", "train/xm_loss_tgt_2d", "train/xm_loss_src_3d",
+            "train/xm_loss_tgt_3d")
+
+
+def _trainer(n2, n3, **kw):
+    _BUILT.append(T._trainer(n2, n3, **kw))
+    return _BUILT[-1]
+
+
+def _hook_logits(tm):
+    """The main heads' logits of every forward of the two networks, in call order, kept on the device as they were."""
+    seen = {"2d_net": [], "3d_net": []}
+    for name in seen:
+        tm.model[name].register_forward_hook(lambda m, i, out, name=name: seen[name].append(out[0]["seg_logit"].detach().clone()))
+    return seen
+
+
+class _CountCalls:
+    """Counts the entries into the mm_coral_* bindings of the loaded library."""
+
+    def __init__(self, monkeypatch):
+        from mm2d3d_amd import _lib
+
+        L = _lib.lib()
+        self.n = {}
+        for name in ("mm_coral_ws_bytes", "mm_coral_fwd", "mm_coral_bwd"):
+            self.n[name] = 0
+            monkeypatch.setattr(L, name, self._wrap(name, getattr(L, name)))
+
+    def _wrap(self, name, fn):
+        def call(*a):
+            self.n[name] += 1
+            return fn(*a)
+
+        return call
+
+
+def test_weight_zero_is_the_step_without_the_options(monkeypatch):
+    dev = T._dev()
+    n2, n3 = T._nets(dev)
+    A = _trainer(copy.deepcopy(n2), copy.deepcopy(n3))
+    B = _trainer(n2, n3, lambda_coral=0.0, coral="plain", coral_eps=1e-3)
+    calls = _CountCalls(monkeypatch)
+    for s in range(2):
+        la, lb = A.fit_step(T._batch(dev)), B.fit_step(T._batch(dev))
+        assert T._same(la, lb), s
+        assert list(A.last_logs) == list(B.last_logs) == list(OLD_KEYS)  # no coral key
+        T._assert_same_dicts(A.last_logs, B.last_logs, f"logs of step {s}")
+    torch.cuda.synchronize()
+    T._assert_same_dicts(A.model.state_dict(), B.model.state_dict(), "weights and running statistics")
+    assert A.last_coral is None and B.last_coral is None
+    assert calls.n == {"mm_coral_ws_bytes": 0, "mm_coral_fwd": 0, "mm_coral_bwd": 0}
+    # the counter counts: the same trainer with the weight raised enters the bindings
+    B.lambda_coral = 0.5
+    B.fit_step(T._batch(dev))
+    assert calls.n["mm_coral_fwd"] == 2 and calls.n["mm_coral_bwd"] == 2 and "train/coral_2d" in B.last_logs
+
+
+@pytest.mark.parametrize("joint", [True, False], ids=["joined", "two_calls"])
+@pytest.mark.parametrize("mode", ["log", "plain"])
+def test_step_adds_the_weighted_terms(mode, joint):
+    from mm2d3d_amd.losses import coral
+
+    dev = T._dev()
+    lam, eps = 0.7, 1e-3
+    n2, n3 = T._nets(dev)
+    off = _trainer(copy.deepcopy(n2), copy.deepcopy(n3), joint_domains=joint)
+    tm = _trainer(n2, n3, joint_domains=joint, lambda_coral=lam, coral=mode, coral_eps=eps)
+    seen = _hook_logits(tm)
+    batch = T._batch(dev)
+    P = int(batch["source"]["x"][0].shape[0])
+    loss = tm.fit_step(batch)
+    base = off.fit_step(T._batch(dev))
+    torch.cuda.synchronize()
+    assert list(tm.last_logs) == list(OLD_KEYS) + list(NEW_KEYS) and all(v.is_cuda and v.dim() == 0 for v in tm.last_logs.values())
+    for k in OLD_KEYS:  # every other term unchanged in every bit
+        assert T._same(tm.last_logs[k], off.last_logs[k]), k
+    # the logged terms are losses.coral on this step's logits: one joined forward per network, or the source pass then the target pass
+    last = tm.last_coral
+    assert set(last) == {"cov_2d", "cov_3d", "count"}
+    for net, tag in (("2d_net", "2d"), ("3d_net", "3d")):
+        assert len(seen[net]) == (1 if joint else 2)
+        x = seen[net][0] if joint else torch.cat(seen[net])
+        assert x.shape[1] == 6 and x.shape[0] > P > 0 and (joint or seen[net][0].shape[0] == P)
+        want = coral(x, P, mode, eps)
+        got = tm.last_logs[f"train/coral_{tag}"]
+        print(f"{mode} {tag}: logged {T._f(got):.7g}, losses.coral on the step's logits {T._f(want['loss']):.7g}, count {want['count'].tolist()}")
+        assert T._same(got, want["loss"]) and T._f(got) > 0.0 and np.isfinite(T._f(got))
+        assert T._same(last[f"cov_{tag}"], want["cov"]) and last[f"cov_{tag}"].shape == (2, 6, 6) and not last[f"cov_{tag}"].requires_grad
+        assert want["count"].tolist() == [P, x.shape[0] - P]
+    assert last["count"].tolist() == [P, x.shape[0] - P] and last["count"].is_cuda
+    # the total is the base loss plus lambda times the two terms: both totals carry the float32 roundings of their sums of some
+    # ten terms, 1.2e-6 relative each (tests/test_gpu_infomax_step.py), and the two products and sums add as much again
+    extra = lam * (T._f(tm.last_logs["train/coral_2d"]) + T._f(tm.last_logs["train/coral_3d"]))
+    print(f"loss {T._f(loss):.7f} = base {T._f(base):.7f} + {extra:.7f}")
+    assert extra > 0.0 and abs(T._f(loss) - T._f(base) - extra) <= 4e-6 * max(1.0, abs(T._f(loss)))
+    # and the step learnt from them: after one step the weights differ from the twin's without the option
+    for name in ("2d_net", "3d_net"):
+        a, b = tm.model[name].state_dict(), off.model[name].state_dict()
+        assert any(not T._same(a[k], b[k]) for k in a if a[k].is_floating_point() and "running" not in k), name
+    assert all(bool(torch.isfinite(v).all()) for v in tm.model.state_dict().values() if v.is_floating_point())
+
+
+def test_composes_with_pseudo_labels_and_entropy_minimisation():
+    dev = T._dev()
+
+    def batch():
+        b = T._batch(dev)
+        n = int(b["target"]["x"][0].shape[0])
+        g = torch.Generator().manual_seed(5)
+        for k in ("pseudo_label_2d", "pseudo_label_3d"):
+            y = torch.randint(0, 6, (n,), generator=g)
+            y[torch.rand(n, generator=g) < 0.5] = -100
+            b["target"][k] = y.to(dev)
+        return b
+
+    others = dict(lambda_pl=0.5, lambda_minent=0.3)
+    n2, n3 = T._nets(dev)
+    plain = _trainer(copy.deepcopy(n2), copy.deepcopy(n3), **others)
+    both = _trainer(n2, n3, lambda_coral=0.7, **others)
+    la, lb = plain.fit_step(batch()), both.fit_step(batch())
+    torch.cuda.synchronize()
+    assert list(both.last_logs) == list(plain.last_logs) + list(NEW_KEYS) and len(plain.last_logs) > len(OLD_KEYS)
+    for k in plain.last_logs:  # the pseudo-label and entropy terms, and every other one, unchanged in every bit
+        assert T._same(plain.last_logs[k], both.last_logs[k]), k
+    extra = 0.7 * sum(T._f(both.last_logs[k]) for k in NEW_KEYS)
+    assert extra > 0.0 and abs(T._f(lb) - T._f(la) - extra) <= 4e-6 * max(1.0, abs(T._f(lb)))
+    assert both.last_target_mass is not None and both.last_coral is not None
