@@ -920,12 +920,18 @@ int mm_copy_rows_bf16(const void* src, int64_t ld_s, void* dst, int64_t ld_d, in
 /* torch.cat(parts, dim=1) of NHWC bf16 maps in one launch (decoder concat [depth, up, rgb], 2d_net/model.py:104-123);
  * split != 0 is its backward: parts[i] = channel slice i of wide.  Channel counts multiples of 8, 1..4 parts. */
 int mm_concat_bf16(void* const* parts, const int* channels, int nparts, void* wide, int64_t N, int split, mm_stream_t stream);
+/* MaxPool2d(3, 2, 1): y and idx dense [B, Ho, Wo, C] (Ho = (H - 1) / 2 + 1), idx = winning tap kh * 3 + kw, the first maximum in scan
+ * order over the taps inside the image.  C and the pitches multiples of 8 and >= C, map pointers 16-byte aligned, idx 8-byte
+ * aligned: anything else is MM_ERR_ARG before any launch. */
 int mm_maxpool3x3s2_fwd(const void* x, int ldx, int B, int H, int W, int C, void* y, void* idx, mm_stream_t stream);
 /* dy2 (optional): a second gradient of the pooled map (it had two consumers), summed with dy in fp32; ld_dy / ld_dy2 = pixel pitches */
 int mm_maxpool3x3s2_bwd(const void* dy, int ld_dy, const void* dy2, int ld_dy2, const void* idx, int B, int H, int W, int C, void* dx,
                         mm_stream_t stream);
 size_t mm_head_ws_bytes(int B, int h, int w, int Hp, int Wp, int C, int NJ);
-/* AvgPool2d(5,1,2) + Conv2d 1x1 of both heads (EXP/2d_net/model.py:59-60,129-130,158,163-164): out NHWC fp32 [B,h,w,NJ] */
+/* AvgPool2d(5,1,2) + Conv2d 1x1 of both heads (EXP/2d_net/model.py:59-60,129-130,158,163-164): out NHWC fp32 [B,h,w,NJ].
+ * x: NHWC [B,Hp,Wp,C] with pixel pitch ld, of which the crop [:h, :w] is read; bias may be NULL.  MM_ERR_ARG before any launch
+ * unless h <= Hp, w <= Wp, C <= ld, ld % 8 == 0, x (and dx) 16-byte aligned, NJ <= 32, NJ * C * 4 <= 60 KB (backward: C == 64).
+ * mm_head_bwd writes +0 to dx outside the crop. */
 int mm_head_fwd(const void* x, int B, int Hp, int Wp, int ld, int h, int w, int C, const float* Wj, const float* bias,
                 int NJ, float* out, void* ws, size_t ws_bytes, mm_stream_t stream);
 int mm_head_bwd(const void* x, int B, int Hp, int Wp, int ld, int h, int w, int C, const float* Wj, int NJ,

@@ -463,6 +463,8 @@ int mm_concat_bf16(void* const* parts, const int* channels, int nparts, void* wi
 int MM_SYM(mm_maxpool3x3s2_fwd)(const void* x, int ldx, int B, int H, int W, int C, void* y, void* idx, hipStream_t s) {
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   MM_CHECK_ARG(C % 8 == 0 && ldx % 8 == 0 && ldx >= C, "maxpool: C and the input pitch must be multiples of 8");
+  MM_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)idx % 8) == 0,
+               "maxpool: x and y must be 16-byte aligned, idx 8-byte aligned");
   int64_t total = (int64_t)B * Ho * Wo * (C / 8);
   if (total == 0) return MM_OK;
   MM_CHECK_ARG(total < (1ll << 32) - 4096, "maxpool: too many elements for 32-bit thread indices");
@@ -476,6 +478,9 @@ int MM_SYM(mm_maxpool3x3s2_bwd)(const void* dy, int ld_dy, const void* dy2, int 
                         hipStream_t s) {
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   MM_CHECK_ARG(C % 8 == 0 && ld_dy % 8 == 0 && (!dy2 || ld_dy2 % 8 == 0), "maxpool: C and the pitches must be multiples of 8");
+  MM_CHECK_ARG(ld_dy >= C && (!dy2 || ld_dy2 >= C), "maxpool: a gradient pitch is below C");
+  MM_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)dy2 % 16) == 0 && ((uintptr_t)dx % 16) == 0 && ((uintptr_t)idx % 8) == 0,
+               "maxpool: dy, dy2 and dx must be 16-byte aligned, idx 8-byte aligned");
   int64_t total = (int64_t)B * H * W * (C / 8);
   if (total == 0) return MM_OK;
   MM_CHECK_ARG(total < (1ll << 32) - 4096, "maxpool: too many elements for 32-bit thread indices");
@@ -494,20 +499,23 @@ size_t MM_SYM(mm_head_ws_bytes)(int B, int h, int w, int Hp, int Wp, int C, int 
 // out [B,h,w,NJ] fp32 (NHWC) = box5x5( x[.., :h, :w, :] . Wj^T ) + bias      (x: NHWC bf16 [B,Hp,Wp,C] with pitch ld)
 int MM_SYM(mm_head_fwd)(const void* x, int B, int Hp, int Wp, int ld, int h, int w, int C, const float* Wj, const float* bias, int NJ,
                 float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-  MM_CHECK_ARG(NJ > 0 && NJ <= MAXJ && C % 8 == 0 && (size_t)NJ * C * 4 <= 60 * 1024, "head: bad NJ/C");
-  size_t zb = mm_align((size_t)B * h * w * NJ * sizeof(float));
+  MM_CHECK_ARG(NJ > 0 && NJ <= MAXJ && C > 0 && C % 8 == 0 && (size_t)NJ * C * 4 <= 60 * 1024, "head: bad NJ/C");
+  MM_CHECK_ARG(B >= 0 && h >= 0 && w >= 0 && h <= Hp && w <= Wp && ld >= C, "head: the crop must lie inside the map, the pitch must hold C");
+  MM_CHECK_ARG(ld % 8 == 0 && ((uintptr_t)x % 16) == 0, "head: x must be 16-byte aligned, its pitch a multiple of 8");  // 16-byte loads
+  int64_t npix = (int64_t)B * h * w;
+  MM_CHECK_ARG(npix < (1ll << 31), "head: too many pixels");
+  MM_CHECK_ARG(npix * NJ < (1ll << 32) - 4096, "head: too many elements for 32-bit thread indices");
+  size_t zb = mm_align((size_t)npix * NJ * sizeof(float));
   if (ws_bytes < zb) {
     mm_set_error("head_fwd: workspace too small");
     return MM_ERR_WORKSPACE;
   }
   float* z = (float*)ws;
-  int64_t npix = (int64_t)B * h * w;
   if (npix == 0) return MM_OK;
-  MM_CHECK_ARG(npix < (1ll << 31), "head: too many pixels");
 #define MM_HEAD_PROJ(MJ)                                                                                                          \
   hipLaunchKernelGGL(k_head_proj<MJ>, dim3((unsigned)mm_cdiv(npix, T)), dim3(T), (size_t)NJ * C * 4, s, (const u16*)x, Hp, Wp, ld, B, h, \
                      w, C, Wj, NJ, z)
-  if (C == 64 && NJ <= 16 && ld % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)z % 16) == 0) {
+  if (C == 64 && NJ <= 16 && ((uintptr_t)z % 16) == 0) {
     const int groups = (int)mm_cdiv(npix, 16);
     int nb = (int)mm_cdiv(groups, (T / 64) * 4);  // ~4 pixel groups per wave
     if (nb > 8192) nb = 8192;
@@ -517,7 +525,6 @@ int MM_SYM(mm_head_fwd)(const void* x, int B, int Hp, int Wp, int ld, int h, int
   else if (NJ <= 20) MM_HEAD_PROJ(20);
   else MM_HEAD_PROJ(32);
 #undef MM_HEAD_PROJ
-  MM_CHECK_ARG((int64_t)B * h * w * NJ < (1ll << 32) - 4096, "head: too many elements for 32-bit thread indices");
   launch_box5(z, B, h, w, NJ, bias, out, s);
   MM_LAUNCH_CHECK();
   return MM_OK;
@@ -527,6 +534,9 @@ int MM_SYM(mm_head_fwd)(const void* x, int B, int Hp, int Wp, int ld, int h, int
 int MM_SYM(mm_head_bwd)(const void* x, int B, int Hp, int Wp, int ld, int h, int w, int C, const float* Wj, int NJ, const float* dout,
                 void* dx, float* dWj, void* ws, size_t ws_bytes, hipStream_t s) {
   MM_CHECK_ARG(NJ > 0 && NJ <= MAXJ && C == 64, "head_bwd: C must be 64");
+  MM_CHECK_ARG(B >= 0 && h >= 0 && w >= 0 && h <= Hp && w <= Wp && ld >= C, "head_bwd: the crop must lie inside the map, the pitch must hold C");
+  MM_CHECK_ARG(ld % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0,
+               "head_bwd: x and dx must be 16-byte aligned, their pitch a multiple of 8");  // 8-byte loads and stores
   MM_CHECK_ARG((int64_t)B * Hp * Wp < (1ll << 31), "head_bwd: too many pixels");
   size_t zb = mm_align((size_t)B * h * w * NJ * sizeof(float));
   const int64_t total = (int64_t)B * Hp * Wp;

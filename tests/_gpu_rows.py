@@ -1,5 +1,5 @@
 """Device operands of the tests that call the C ABI directly (test_gpu_point_rows.py, test_gpu_loss_rows.py,
-test_gpu_lift_index.py, test_gpu_bn_rows.py): pitched views into wider buffers whose padding is NaN for inputs and a sentinel, which
+test_gpu_lift_index.py, test_gpu_bn_rows.py, test_gpu_misc2d.py): pitched views into wider buffers whose padding is NaN for inputs and a sentinel, which
 must survive, for outputs.  No tests here; importing this needs no GPU."""
 import numpy as np
 import torch
@@ -19,14 +19,14 @@ def abi():
     return _lib.lib(), _lib
 
 
-DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
-_BITS = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16}
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16, "u8": torch.uint8}
+_BITS = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.uint8: torch.uint8}
 
 
 class Rows:
     """An [n, c] operand on the device: a view, rows ``ld`` apart, ``off`` elements into a wider flat buffer that holds ``fill``
     everywhere else (before the first row, between rows, behind the last one).  ``dtype``: torch.float32 (default), bfloat16 or
-    float16 (or "fp32" / "bf16" / "fp16"); data and fill are rounded to it (nearest even).  ``tight``: the buffer ends with the last
+    float16 (or "fp32" / "bf16" / "fp16"; "u8": bytes, such as the max-pool's taps); data and fill are rounded to it (nearest even).  ``tight``: the buffer ends with the last
     element of the last row (a channel slice that reaches the end of its allocation)."""
 
     def __init__(self, data, n, c, ld, off=0, fill=float("nan"), dtype=torch.float32, tight=False):
