@@ -582,6 +582,25 @@ int mm_coral_fwd(const float* x, int ld, int64_t N, int64_t P, int d, int mode, 
                  float* cov, float* aux, void* ws, size_t ws_bytes, mm_stream_t stream);
 int mm_coral_bwd(const float* x, int ld, int64_t N, int64_t P, int d, const float* aux, const float* grad_out, float* dx, int ld_dx,
                  mm_stream_t stream);
+/* Fourier domain adaptation of the source images (FDA, Yang & Soatto, CVPR 2020; csrc/fda.hip).  src: fp32 [Bs, C, H, W], trg: fp32
+ * [Bt, C, H, W], out: fp32 [Bs, C, H, W], all dense.  Per channel, source image i takes the amplitudes of target image i mod Bt on
+ * the (2 band + 1) x (2 band + 1) lowest frequencies and keeps its own phases; with F the 2D DFT,
+ *   dF[k] = F_src[k] (|F_trg[k]| / |F_src[k]| - 1),  or |F_trg[k]| where F_src[k] is exactly 0 (angle(0) = 0),  |ky|, |kx| <= band,
+ *   out[y, x] = src[y, x] + 1 / (H W) * Re sum_k dF[k] e^{+2 pi i (ky y / H + kx x / W)}:
+ * what fft2, fftshift, the window [n / 2 - band, n / 2 + band] on both axes, ifftshift, ifft2 and the real part give.  band = 0
+ * swaps the DC term alone.  mean, std: fp32 [C] on the device, or both null.  Given, the tensors hold (pixel - mean) / std and the swap
+ * is that of the pixels: every term but the DC term scales by 1 / std on both sides, the DC term is taken as std F[0] + mean H W; no
+ * de-normalised image is formed.  A non-finite pixel is not special-cased: it spoils its image-channel.
+ * mse: fp32 [Bs], the mean over C H W of (out - src)^2 before out is rounded, by Parseval: sum_k |dF[k]|^2 / (H W)^2, averaged over
+ * the channels; no pass over the images.  Every sum and every twiddle factor is fp64, phases are reduced in integers, every sum has a
+ * fixed order: no atomics, no host read, the same bits on every call.  Three launches: the row DFT of all images onto the
+ * band's column frequencies with each row tile's share of the column DFT, one workgroup per (source image, channel) that totals
+ * the shares and makes the swap, and the apply pass, which takes the inverse column transform of its own rows first.  Refused before any launch, with no output touched: a null src, trg, out or mse; mean and std not
+ * both null or both set; Bs, Bt, H or W < 1; Bs or Bt > 2^20; C outside [1, 4]; H or W > 2048 (the LDS twiddle tables); band outside
+ * [0, 32] or 2 band + 1 > min(H, W); a missing or short workspace.  mm_fda_ws_bytes returns 0 for sizes outside these limits. */
+size_t mm_fda_ws_bytes(int Bs, int Bt, int C, int H, int W, int band);
+int mm_fda_transfer(const float* src, int Bs, const float* trg, int Bt, int C, int H, int W, int band, const float* mean,
+                    const float* std, float* out, float* mse, void* ws, size_t ws_bytes, mm_stream_t stream);
 /* mean_i sum_c softmax(tgt)_ic (log softmax(tgt)_ic - log softmax(pred)_ic)  (EXP/train.py:157-184) */
 int mm_kl_fwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N, int C, float* loss, void* ws,
               size_t ws_bytes, mm_stream_t stream);

@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, coral, domains, infomax
+from . import _lib, coral, domains, fda, infomax
 from .ddp import GradAllReducer, ranks_share_a_gpu
 from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
@@ -122,6 +122,8 @@ class TrainModel(nn.Module):
         self.target_entropy = infomax.TargetEntropy(train_kwargs)
         # correlation alignment of the source and the target rows' logits (``lambda_coral``, ``coral``, ``coral_eps``): coral.DomainAlignment, forwarded too
         self.alignment = coral.DomainAlignment(train_kwargs)
+        # the source images in the target images' style before the 2D network sees them (``fda_beta``, ``fda_image_norm``): fda.InputStyle, forwarded too
+        self.input_style = fda.InputStyle(train_kwargs)
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -223,6 +225,9 @@ class TrainModel(nn.Module):
         n2d, n3d = self.modules_name[0], self.modules_name[1]
         st, te, al = self.selftrain, self.target_entropy, self.alignment
         te.begin_step(self)
+        styled = stage == "train" and self.input_style.active
+        if styled:
+            src = self.input_style.style(src, trg)  # a shallow copy with the styled images: the caller's batch stays as it is
         teacher = st.lambda_pl > 0 and st.pseudo_label_source == "teacher"
         pseudo = st.batch_targets(trg) if st.lambda_pl > 0 and not teacher else None
         if self._can_join(src, trg):
@@ -230,6 +235,8 @@ class TrainModel(nn.Module):
             self._pipelined = None
             if pre is not None:  # joined one step ahead by prefetch(): its sparse metadata is already built (or queued)
                 both, B = pre["both"], pre["B"]
+                if styled:  # joined before the images were styled
+                    both = dict(both, img=torch.cat([src["img"], trg["img"]], 0))
             else:
                 both, B = self._join(src, trg)
             P = src["x"][0].shape[0]  # point rows [0, P) are the source's
@@ -351,6 +358,8 @@ class TrainModel(nn.Module):
             loss_2d, loss_3d = te.add(self.last_logs, stage, loss_2d, loss_3d, im)
         if ca is not None:
             loss_2d, loss_3d = al.add(self.last_logs, stage, loss_2d, loss_3d, ca)
+        if styled:
+            self.input_style.log(self.last_logs, stage)
         return loss_2d + loss_3d
 
     def training_step(self, batch, batch_idx=0):
@@ -670,7 +679,8 @@ class TrainModel(nn.Module):
         return loss
 
 
-for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED), ("alignment", coral.FORWARDED)):
+for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED), ("alignment", coral.FORWARDED),
+                       ("input_style", fda.FORWARDED)):
     for _name in _names:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
         setattr(TrainModel, _name, property(lambda self, n=_name, o=_owner: getattr(getattr(self, o), n),
                                             lambda self, value, n=_name, o=_owner: setattr(getattr(self, o), n, value)))
