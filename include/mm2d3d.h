@@ -582,6 +582,37 @@ int mm_coral_fwd(const float* x, int ld, int64_t N, int64_t P, int d, int mode, 
                  float* cov, float* aux, void* ws, size_t ws_bytes, mm_stream_t stream);
 int mm_coral_bwd(const float* x, int ld, int64_t N, int64_t P, int d, const float* aux, const float* grad_out, float* dx, int ld_dx,
                  mm_stream_t stream);
+/* Adversarial alignment in the output space with a point-wise discriminator (AdaptSegNet, Tsai et al., CVPR 2018; AdvEnt, Vu et
+ * al., CVPR 2019; csrc/adv.hip).  x: fp32 [N, C], row pitch ld, 2 <= C <= 32.  Rows [0, P) are source (domain 0), rows [P, N) target
+ * (domain 1).  A row is counted when its C logits are all finite; n_s, n_t of them.  Per counted row, in fp32: p = softmax(x_i)
+ * (m = max_c x_c, s = sum_c expf(x_c - m), p_c = expf(x_c - m) / s), and the discriminator's input
+ *   mode 0 (softmax, AdaptSegNet):  u_c = p_c;
+ *   mode 1 (selfinfo, AdvEnt):      u_c = -p_c ln p_c / ln C, ln p_c taken as (x_c - m) - logf(s); p_c == 0 gives u_c = 0, never NaN.
+ * The discriminator: a = w3 . lrelu(W2 lrelu(W1 u + b1) + b2) + b3, lrelu(z) = z > 0 ? z : 0.2 z (its derivative at 0 is 0.2),
+ * hidden width H = 16, 32 or 64.  params: ONE flat fp32 buffer of mm_adv_param_count(C, H) = H C + H H + 3 H + 1 floats, in this
+ * order: W1 [H][C] row-major, b1 [H], W2 [H][H] row-major, b2 [H], w3 [H], b3.  With softplus(a) = max(a, 0) + log1p(exp(-|a|)):
+ *   loss_D = 0.5 / n_s * sum_src softplus(a_i) + 0.5 / n_t * sum_trg softplus(-a_i)     (a domain without a counted row adds 0);
+ *   loss_G = 1 / n_t * sum_trg softplus(a_i)          (the target rows called "source"; 0 when n_t == 0).
+ * Outputs of mm_adv_fwd: stats[2] = loss_D, loss_G (fp32); count[2] = n_s, n_t (int64, exact); correct[2] (int64) = the counted
+ * source rows with a <= 0 and the counted target rows with a > 0; dparams[param_count] = dloss_D / dparams in the order of params,
+ * written, not accumulated; gx [N, C], row pitch ld_gx: dloss_G / dx_i on the counted target rows, +0 in every bit on any other
+ * row, every row written exactly once.  Through the input transform dL/dx_k = p_k (v_k - sum_c p_c v_c) with v_c = dL/du_c (mode
+ * 0) or dL/du_c * (-(ln p_c + 1) / ln C) (mode 1); a class with p_c == 0 contributes exactly 0.
+ * mm_adv_bwd: dx = grad_out[0] * gx for every row (a zero stays +0); grad_out is read on the device: no host read anywhere.
+ * Products are fp32: the layers' dot products have C and H terms, and an entry of a weight gradient is summed in fp32 over the at
+ * most 128 rows of a tile, rows ascending; across the tiles of a workgroup, across workgroups, and for the softplus sums, fp64 in a
+ * fixed order.  Refused before any launch, with no output touched: C outside [2, 32], H not 16, 32 or 64, a pitch below C, P
+ * outside [0, N], N * C >= 2^31, a null operand (x and gx may be null when N == 0), a missing or short workspace, an unknown mode.
+ * N == 0 and P == N are legal.  mm_adv_ws_bytes and mm_adv_param_count return 0 for a C or H outside the limits.  Three launches
+ * forward: the row counts per workgroup of a capped grid - 1 / n_s and 1 / n_t enter every row's share of dparams and gx, and a row
+ * of gx is written once, so the counts come first -; the row pass over a capped grid, which stages the parameters into LDS once per
+ * workgroup and leaves a slab of fp64 sums each; the pass that totals the slabs.  One launch backward.  No atomics, no workgroup
+ * waits for another: bit-stable run to run. */
+int64_t mm_adv_param_count(int C, int H);
+size_t mm_adv_ws_bytes(int C, int H);
+int mm_adv_fwd(const float* x, int ld, int64_t N, int64_t P, int C, int H, int mode, const float* params, float* stats, int64_t* count,
+               int64_t* correct, float* dparams, float* gx, int ld_gx, void* ws, size_t ws_bytes, mm_stream_t stream);
+int mm_adv_bwd(const float* gx, int ld_gx, int64_t N, int C, const float* grad_out, float* dx, int ld_dx, mm_stream_t stream);
 /* Fourier domain adaptation of the source images (FDA, Yang & Soatto, CVPR 2020; csrc/fda.hip).  src: fp32 [Bs, C, H, W], trg: fp32
  * [Bt, C, H, W], out: fp32 [Bs, C, H, W], all dense.  Per channel, source image i takes the amplitudes of target image i mod Bt on
  * the (2 band + 1) x (2 band + 1) lowest frequencies and keeps its own phases; with F the 2D DFT,

@@ -127,6 +127,10 @@ _PROTOS = {
     "mm_coral_ws_bytes": (sz, [i32]),
     "mm_coral_fwd": (i32, [vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mm_coral_bwd": (i32, [vp, i32, i64, i64, i32, vp, vp, vp, i32, vp]),
+    "mm_adv_param_count": (i64, [i32, i32]),
+    "mm_adv_ws_bytes": (sz, [i32, i32]),
+    "mm_adv_fwd": (i32, [vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "mm_adv_bwd": (i32, [vp, i32, i64, i32, vp, vp, i32, vp]),
     "mm_fda_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "mm_fda_transfer": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "mm_kl_fwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, sz, vp]),

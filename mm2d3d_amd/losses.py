@@ -5,7 +5,8 @@ in the reference; ``cross_entropy`` (weighted, ignore_index -100, weighted-mean 
 ``F.cross_entropy`` default) and the cross-modal KL of train.py:157-184 run as single fused kernels; ``lovasz_softmax`` sorts its
 errors per class with the segmented radix sort of csrc/lovasz.hip; ``target_entropy`` (entropy minimisation and its diversity guard on
 unlabelled rows) runs on the row kernels of csrc/infomax.hip; ``coral`` (Deep CORAL / LogCORAL alignment of the source and the target
-rows' covariances) on those of csrc/coral.hip; ``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
+rows' covariances) on those of csrc/coral.hip; ``adversarial`` (a point discriminator on the softmax or self-information of the
+source and the target rows, AdaptSegNet / AdvEnt) on those of csrc/adv.hip; ``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
 tail row (``pselab.agreement_weights``) through a compile-time flag of the same kernels.
 """
 from __future__ import annotations
@@ -531,6 +532,93 @@ def coral(x, first_row, mode="log", eps=1e-4):
     _lib.require_cuda(x, "x")
     loss, count, mean, cov = _CoralFn.apply(x, first_row, CORAL_MODES[mode], float(eps))
     return dict(loss=loss, count=count, mean=mean, cov=cov)
+
+
+ADV_MODES = {"softmax": 0, "selfinfo": 1}  # the ``mode`` of mm_adv_fwd
+ADV_HIDDEN = (16, 32, 64)
+
+
+def adversarial_param_count(C, hidden):
+    """The length of the discriminator's flat parameter buffer: W1 [H][C], b1 [H], W2 [H][H], b2 [H], w3 [H], b3."""
+    return hidden * C + hidden * hidden + 3 * hidden + 1
+
+
+class _AdversarialFn(torch.autograd.Function):
+    """The point discriminator on the rows [0, first_row) (source) and [first_row, N) (target) of ``x`` (csrc/adv.hip): the forward
+    leaves both losses, the counts, the discriminator's parameter gradient and ``gx`` = dloss_G / dx; ONE backward launch scales the
+    saved ``gx`` by the upstream gradient.  ``params`` gets no gradient from autograd: the caller steps it with ``grad_params``."""
+
+    @staticmethod
+    def forward(ctx, x, first_row, params, mode, hidden):
+        _lib.require_cuda(x, "x")
+        L = _lib.lib()
+        ctx.in_dtype = x.dtype
+        x, ld = _lib.row_pitched(x)
+        N, C = x.shape
+        dev = x.device
+        stats = torch.empty(2, dtype=F32, device=dev)
+        count, correct = (torch.empty(2, dtype=torch.int64, device=dev) for _ in range(2))
+        dparams = torch.empty(params.numel(), dtype=F32, device=dev)
+        gx = torch.empty((N, C), dtype=F32, device=dev)
+        ws = _lib.workspace.get(int(L.mm_adv_ws_bytes(C, hidden)), dev)
+        check(L.mm_adv_fwd(ptr(x), ld, N, first_row, C, hidden, mode, ptr(params), ptr(stats), ptr(count), ptr(correct), ptr(dparams),
+                           ptr(gx), C, ptr(ws), ws.numel(), stream()), "adv_fwd")
+        ctx.save_for_backward(gx)
+        loss_g, loss_d = stats[1], stats[0]
+        ctx.mark_non_differentiable(loss_d, dparams, count, correct)
+        ctx.set_materialize_grads(False)  # else every backward fills zero gradients for the four detached outputs
+        return loss_g, loss_d, dparams, count, correct
+
+    @staticmethod
+    def backward(ctx, g, _d, _p, _n, _c):
+        if g is None:
+            return None, None, None, None, None
+        L = _lib.lib()
+        (gx,) = ctx.saved_tensors
+        N, C = gx.shape
+        g = g.to(F32).contiguous()
+        dx = _grad_rows(gx, ctx.in_dtype, lambda dx: check(L.mm_adv_bwd(ptr(gx), C, N, C, ptr(g), ptr(dx), C, stream()), "adv_bwd"))
+        return dx, None, None, None, None
+
+
+def adversarial(x, first_row, params, mode="selfinfo", hidden=64):
+    """Adversarial alignment in the output space: a point-wise discriminator D on the rows of ``x`` [N, C], rows ``[0, first_row)``
+    source (domain 0) and ``[first_row, N)`` target (domain 1) of a joined [source | target] pass.  D reads ``u`` = softmax(x_i)
+    (``mode="softmax"``, AdaptSegNet, Tsai et al., CVPR 2018) or the weighted self-information -p ln p / ln C
+    (``mode="selfinfo"``, default; AdvEnt, Vu et al., CVPR 2019) and is the MLP ``a = w3 . lrelu(W2 lrelu(W1 u + b1) + b2) + b3``
+    with slope 0.2 and ``hidden`` = 16, 32 or 64 units per layer.  ``params``: its weights as ONE flat fp32 device tensor of
+    ``adversarial_param_count(C, hidden)`` elements in the order W1 [H][C], b1, W2 [H][H], b2, w3, b3.
+
+    Returns ``dict(loss_g, loss_d, grad_params, count, correct)``, all device tensors.  Counted are the rows whose logits are all
+    finite, ``count`` (int64 [2]) per domain.  ``loss_d`` = 0.5 mean_src softplus(a) + 0.5 mean_trg softplus(-a), the
+    discriminator's binary cross entropy, and ``grad_params`` its gradient with respect to ``params``, for the caller to step D
+    with; ``loss_g`` = mean_trg softplus(a), the target rows called "source" - the term the segmentation network minimises.
+    ``correct`` (int64 [2]): source rows with a <= 0 and target rows with a > 0.  Only ``loss_g`` is differentiable, and only with
+    respect to ``x``: its gradient was formed in the forward with the weights D had THEN, so ``params`` may be stepped before the
+    backward runs, and autograd never sees ``params``.  One autograd node, three forward launches and one backward launch, no host
+    read.  The statistics are those of THIS call's rows.  ``x`` may be fp16, bf16 or a row-pitched view (``stride(1) == 1``),
+    which is read in place.  Bit-stable run to run."""
+    who = "adversarial"
+    if not isinstance(mode, str) or mode not in ADV_MODES:
+        raise ValueError(f'{who}: mode must be "selfinfo" or "softmax", not {mode!r}')
+    if isinstance(hidden, bool) or not isinstance(hidden, int) or hidden not in ADV_HIDDEN:
+        raise ValueError(f"{who}: hidden must be 16, 32 or 64, not {hidden!r}")
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"{who}: x must be [N, C]")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    if not 2 <= C <= 32:
+        raise ValueError(f"{who}: {C} classes, the row kernels take 2 to 32")
+    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
+        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
+    if N * C >= 1 << 31:
+        raise ValueError(f"{who}: {N} rows of {C} classes, N * C must stay below 2^31")
+    need = adversarial_param_count(C, hidden)
+    if not torch.is_tensor(params) or params.dtype != F32 or params.dim() != 1 or params.numel() != need or not params.is_contiguous():
+        raise ValueError(f"{who}: params must be a flat contiguous float32 tensor of {need} elements for C = {C}, hidden = {hidden}")
+    _lib.require_cuda(x, "x")
+    _lib.require_cuda(params, "params")
+    loss_g, loss_d, dparams, count, correct = _AdversarialFn.apply(x, first_row, params.detach(), ADV_MODES[mode], hidden)
+    return dict(loss_g=loss_g, loss_d=loss_d, grad_params=dparams, count=count, correct=correct)
 
 
 class _KLFn(torch.autograd.Function):

@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, coral, domains, fda, infomax
+from . import _lib, adversarial, coral, domains, fda, infomax
 from .ddp import GradAllReducer, ranks_share_a_gpu
 from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
@@ -122,6 +122,9 @@ class TrainModel(nn.Module):
         self.target_entropy = infomax.TargetEntropy(train_kwargs)
         # correlation alignment of the source and the target rows' logits (``lambda_coral``, ``coral``, ``coral_eps``): coral.DomainAlignment, forwarded too
         self.alignment = coral.DomainAlignment(train_kwargs)
+        # a point discriminator on each main head's logits and the adversarial term that fools it (``lambda_adv``, ``adv_*``):
+        # adversarial.OutputAdversary owns options, discriminators and their optimisers (NOT in self.optimizers); forwarded too
+        self.adversary = adversarial.OutputAdversary(train_kwargs)
         # the source images in the target images' style before the 2D network sees them (``fda_beta``, ``fda_image_norm``): fda.InputStyle, forwarded too
         self.input_style = fda.InputStyle(train_kwargs)
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
@@ -162,6 +165,7 @@ class TrainModel(nn.Module):
             self.optimizers.append(opt)
             self.schedulers.append(sched)
         self.reducer = GradAllReducer(self.optimizers)
+        self.adversary.check_reducer(self.reducer)  # the discriminators are not reduced over ranks
         # the 2D trunk runs as two HIP graphs (mm2d3d_amd/graph2d.py); under an active data-parallel reducer only on request
         # (``ddp_graph``): its bucket hooks overlap more when the parameters' gradients complete one by one during backward
         n2d = self.model[self.modules_name[0]]
@@ -223,7 +227,7 @@ class TrainModel(nn.Module):
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
-        st, te, al = self.selftrain, self.target_entropy, self.alignment
+        st, te, al, adv = self.selftrain, self.target_entropy, self.alignment, self.adversary
         te.begin_step(self)
         styled = stage == "train" and self.input_style.active
         if styled:
@@ -323,6 +327,7 @@ class TrainModel(nn.Module):
             xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
             im = te.terms(l2d, l3d, P)
             ca = al.terms(l2d, l3d, P)
+            ad = adv.terms(l2d, l3d, P) if adv.active else None
         else:
             if teacher:
                 own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
@@ -343,6 +348,7 @@ class TrainModel(nn.Module):
             im = te.terms(p2d["seg_logit"], p3d["seg_logit"], 0)
             # the two calls' logits side by side, as the joined pass has them: the source's rows first
             ca = al.terms(torch.cat((src2d, p2d["seg_logit"])), torch.cat((src3d, p3d["seg_logit"])), int(src2d.shape[0])) if al.active else None
+            ad = adv.terms(torch.cat((src2d, p2d["seg_logit"])), torch.cat((src3d, p3d["seg_logit"])), int(src2d.shape[0])) if adv.active else None
         self.last_logs = {
             f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
@@ -358,6 +364,8 @@ class TrainModel(nn.Module):
             loss_2d, loss_3d = te.add(self.last_logs, stage, loss_2d, loss_3d, im)
         if ca is not None:
             loss_2d, loss_3d = al.add(self.last_logs, stage, loss_2d, loss_3d, ca)
+        if ad is not None:
+            loss_2d, loss_3d = adv.add(self.last_logs, stage, loss_2d, loss_3d, ad)
         if styled:
             self.input_style.log(self.last_logs, stage)
         return loss_2d + loss_3d
@@ -538,6 +546,7 @@ class TrainModel(nn.Module):
                     "ema_state_dict": {self._ckpt_key(k): v for k, v in self.ema.teacher_state_dict().items()}}
                    if self.ema is not None else {}),
                 **self.selftrain.state_dict(),  # "pl_adaptive": the self-adaptive pseudo-label thresholds, once built
+                **self.adversary.state_dict(),  # "adversary": the two discriminators and their optimisers, once built
                 # Lightning's key for the GradScaler of a ``precision: 16`` run
                 **({"native_amp_scaling_state": self.scaler.state_dict()} if self.scaler is not None else {})}
 
@@ -580,6 +589,7 @@ class TrainModel(nn.Module):
             else:
                 self.ema.reset()  # a checkpoint without a teacher: it starts from the loaded weights
         self.selftrain.load_state_dict(ckpt, next((p.device for p in self.model.parameters() if p.is_cuda), None))
+        self.adversary.load_state_dict(ckpt, next((p.device for p in self.model.parameters() if p.is_cuda), None))
         # the loss scale resumes where it was; the scaler itself is rebuilt by the next fit_step (its device step counters start
         # from the optimisers' restored step counts)
         self._scaler_state = ckpt.get("native_amp_scaling_state")
@@ -680,7 +690,7 @@ class TrainModel(nn.Module):
 
 
 for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED), ("alignment", coral.FORWARDED),
-                       ("input_style", fda.FORWARDED)):
+                       ("adversary", adversarial.FORWARDED), ("input_style", fda.FORWARDED)):
     for _name in _names:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
         setattr(TrainModel, _name, property(lambda self, n=_name, o=_owner: getattr(getattr(self, o), n),
                                             lambda self, value, n=_name, o=_owner: setattr(getattr(self, o), n, value)))
