@@ -645,6 +645,28 @@ int mm_kl_bwd(const float* pred, int ld_p, const float* tgt, int ld_t, int64_t N
 size_t mm_lift_index_ws_bytes(int64_t n);
 int mm_lift_index(const int64_t* rc, const int64_t* counts, int nb, int64_t n, int H, int W, int no_spin, int32_t* key, int32_t* skey,
                   int32_t* order, int32_t* err, void* ws, size_t ws_bytes, mm_stream_t stream);
+/* The stable sort of mm_lift_index alone, over keys the caller supplies, each in [0, nkeys) (the matched pixels of mm_xm_search
+ * change every step): skey / order [n] as above.  Same radix configuration, workspace (mm_lift_index_ws_bytes(n)) and no_spin rule. */
+int mm_lift_sort_keys(const int32_t* key, int64_t n, int64_t nkeys, int no_spin, int32_t* skey, int32_t* order, void* ws,
+                      size_t ws_bytes, mm_stream_t stream);
+/* Sparse-to-dense cross-modal matching (the window search of DsCML, Peng et al., ICCV 2021; csrc/xmdense.hip).  seg: a dense fp32
+ * logit map of B images, H x W pixels, C classes (2 <= C <= 32), element (b, y, x, c) at seg[b*sb + y*sy + x*sx + c*sc] - a channel
+ * slice of a wider NHWC buffer or an NCHW map alike.  key [N]: the pixel id (b*H + y)*W + x of every point (mm_lift_index);
+ * rows: fp32 [N, C] with row pitch ld, the points' own logits.  The candidates of point i are the pixels (b, y+dy, x+dx) with
+ * |dy|, |dx| <= r (0 <= r <= 3) inside image b, in the order: the centre, then the others row-major (dy ascending, then dx).
+ *   direction 0: value_j = KL(softmax(rows_i) || softmax(seg_j))   (the point row teaches the map);
+ *   direction 1: value_j = KL(softmax(seg_j) || softmax(rows_i))   (the map teaches the point row);
+ * in fp32, sum_c exp(lq_c) * (lq_c - lp_c) over the two log-softmax rows, as mm_kl_fwd forms it.  sel [N] = the key of the candidate
+ * with the smallest value, the earliest among equal ones; a NaN value is skipped; nothing left: the centre.  klmin [N] = that
+ * candidate's value.  A key outside [0, B*H*W) reads nothing: sel = key, klmin = NaN.  counts (int64 [4]): the number of rows of
+ * [0, P) and of [P, N) whose match left the centre, then the sums of their Chebyshev displacements max(|dy|, |dx|).
+ * r = 0 is legal: sel == key, klmin the centre's value.  Refused before any launch: r outside [0, 3], C outside [2, 32], a
+ * direction other than 0 / 1, P outside [0, N], N * C >= 2^31, ld < C, a map of 2^31 pixels or more, a null operand, a short
+ * workspace.  Two launches; no atomics, no host read: bit-stable run to run. */
+size_t mm_xm_search_ws_bytes(void);
+int mm_xm_search(const float* seg, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int B, int H, int W, int C, const int32_t* key,
+                 const float* rows, int ld, int64_t N, int64_t P, int r, int direction, int32_t* sel, float* klmin, int64_t* counts,
+                 void* ws, size_t ws_bytes, mm_stream_t stream);
 /* out[p][c] = seg[b*sb + row*sy + col*sx + c*sc] at the pixel of point p (2d_net/model.py:131-137) */
 int mm_lift_gather_key(const float* seg, int64_t sb, int64_t sy, int64_t sx, int64_t sc, const int32_t* key, int64_t N, int C, int H,
                        int W, float* out, mm_stream_t stream);

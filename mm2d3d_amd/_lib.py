@@ -137,6 +137,9 @@ _PROTOS = {
     "mm_kl_bwd": (i32, [vp, i32, vp, i32, i64, i32, vp, vp, i32, vp]),
     "mm_lift_index_ws_bytes": (sz, [i64]),
     "mm_lift_index": (i32, [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "mm_lift_sort_keys": (i32, [vp, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "mm_xm_search_ws_bytes": (sz, []),
+    "mm_xm_search": (i32, [vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "mm_lift_gather_key": (i32, [vp, i64, i64, i64, i64, vp, i64, i32, i32, i32, vp, vp]),
     "mm_lift_scatter_key": (i32, [vp, i32, vp, vp, i64, i32, i32, i64, i64, i64, i64, vp, vp]),
     "mm_eval_confusion": (i32, [vp, i32, vp, i32, vp, i64, i32, i64, vp, vp]),

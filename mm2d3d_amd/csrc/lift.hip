@@ -119,6 +119,28 @@ int mm_lift_index(const int64_t* rc, const int64_t* counts, int nb, int64_t n, i
   return MM_OK;
 }
 
+// The sort of mm_lift_index alone, over keys the caller supplies (each in [0, nkeys); the matched pixels of csrc/xmdense.hip change
+// every step): skey [n] / order [n] = the keys ascending and the point of each sorted position (stable).  Same radix
+// configuration, same workspace (mm_lift_index_ws_bytes), same no_spin rule.
+int mm_lift_sort_keys(const int32_t* key, int64_t n, int64_t nkeys, int no_spin, int32_t* skey, int32_t* order, void* ws, size_t ws_bytes,
+                      hipStream_t s) {
+  MM_CHECK_ARG(n >= 0 && n < (1ll << 31) && nkeys > 0 && nkeys < (1ll << 31), "lift_sort_keys: bad shape (n=%lld nkeys=%lld)", (long long)n,
+               (long long)nkeys);
+  if (n == 0) return MM_OK;
+  MM_CHECK_ARG(key && skey && order && ws, "lift_sort_keys: null key, skey, order or workspace");
+  size_t tb = sort_bytes(n);
+  if (ws_bytes < tb) {
+    mm_set_error("lift_sort_keys: workspace too small (%zu < %zu)", ws_bytes, tb);
+    return MM_ERR_WORKSPACE;
+  }
+  unsigned bits = 1;
+  while (bits < 32 && ((int64_t)1 << bits) < nkeys) bits++;
+  if (no_spin) MM_HIP(sort_keys<SortCfgMerge>(ws, tb, key, skey, order, n, bits, s));
+  else MM_HIP(sort_keys<SortCfg>(ws, tb, key, skey, order, n, bits, s));
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
 // out[p][c] = seg[b*sb + row*sy + col*sx + c*sc] at the pixel of point p
 int mm_lift_gather_key(const float* seg, int64_t sb, int64_t sy, int64_t sx, int64_t sc, const int32_t* key, int64_t N, int C, int H, int W,
                        float* out, hipStream_t s) {

@@ -49,6 +49,9 @@ class PixelIndex:
         # (nn2d._HeadsFn.backward takes them for the 1x1 heads' bias gradients).  Scoped to the batch's index object (a
         # process-wide address-keyed table could hand a stale sum to an unrelated map the allocator placed at the same address)
         self._colsums = {}
+        # slices (base, channel offset) of joint buffers whose last scatter went to SELECTED pixels (lift_at): an index that serves
+        # several steps (a batch dict that is reused) must clear such a slice before the next scatter, which stores at other pixels
+        self._dirty = set()
         self._err = None  # device flag: an index was outside the map (device-side lists only; host lists are checked on the host)
         if len(img_indices) and all(isinstance(ix, torch.Tensor) and ix.is_cuda for ix in img_indices):
             counts = [int(ix.shape[0]) for ix in img_indices]
@@ -113,33 +116,108 @@ class _LiftFn(torch.autograd.Function):
         ctx.index, ctx.shape = index, seg.shape
         # seg may be a channel slice of a wider NHWC map (the two heads of nn2d.fused_heads are the halves of ONE [B, h, w, 2 nc]
         # buffer): remember the layout, the backward then writes its slice of ONE joint gradient buffer instead of a map of its own
-        ctx.slice = None
-        if seg.stride(1) == 1 and seg.stride(3) > C and seg.stride(2) == W * seg.stride(3) and seg.stride(0) == H * W * seg.stride(3):
-            off = seg.storage_offset() % seg.stride(3)
-            ctx.slice = (seg.data_ptr() - 4 * off, int(seg.stride(3)), int(off))
+        ctx.slice = _map_slice(seg)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
-        index = ctx.index
-        B, C, H, W = ctx.shape
-        dout = dout.to(F32).contiguous()
-        # gradient map in NHWC (what the fused heads' backward reads coalesced); logical shape stays [B,C,H,W]
-        if ctx.slice is not None:
-            base, pitch, off = ctx.slice
-            joint = index._joint.get(base)
-            if joint is None or joint.shape != (B, H, W, pitch):
-                joint = index._joint[base] = torch.zeros((B, H, W, pitch), dtype=F32, device=dout.device)
-            dseg = joint[..., off:off + C].permute(0, 3, 1, 2)
+        return _scatter(ctx, dout, ctx.index.skey, ctx.index.order, False), None
+
+
+def _scatter(ctx, dout, skey, order, selected):
+    """The gradient map of a lifted map from its row gradients ``dout``: the sum per pixel over the runs of the sorted keys
+    (``selected``: the keys of a ``lift_at``, not the points' own pixels)."""
+    L = _lib.lib()
+    index = ctx.index
+    B, C, H, W = ctx.shape
+    dout = dout.to(F32).contiguous()
+    # gradient map in NHWC (what the fused heads' backward reads coalesced); logical shape stays [B,C,H,W]
+    if ctx.slice is not None:
+        base, pitch, off = ctx.slice
+        joint = index._joint.get(base)
+        if joint is None or joint.shape != (B, H, W, pitch):
+            joint = index._joint[base] = torch.zeros((B, H, W, pitch), dtype=F32, device=dout.device)
+        dseg = joint[..., off:off + C].permute(0, 3, 1, 2)
+        if (base, off) in index._dirty:  # a buffer from an earlier step of this index, last filled at selected pixels
+            dseg.zero_()
+        if selected:
+            index._dirty.add((base, off))
         else:
-            dseg = torch.zeros((B, H, W, C), dtype=F32, device=dout.device).permute(0, 3, 1, 2)
-        check(L.mm_lift_scatter_key(ptr(dout), C, ptr(index.order), ptr(index.skey), index.n, H, W, dseg.stride(0), dseg.stride(2),
-                                    dseg.stride(3), dseg.stride(1), ptr(dseg), stream()), "lift_scatter")
-        # the per-channel sum of the dense gradient map = the sum over the points (what a bias behind the map needs): [N, C] instead
-        # of a reduction over the whole map
-        index._colsums[dseg.data_ptr()] = (dout.sum(0), dseg.shape)
-        return dseg, None
+            index._dirty.discard((base, off))
+    else:
+        dseg = torch.zeros((B, H, W, C), dtype=F32, device=dout.device).permute(0, 3, 1, 2)
+    check(L.mm_lift_scatter_key(ptr(dout), C, ptr(order), ptr(skey), index.n, H, W, dseg.stride(0), dseg.stride(2), dseg.stride(3),
+                                dseg.stride(1), ptr(dseg), stream()), "lift_scatter")
+    # the per-channel sum of the dense gradient map = the sum over the points (what a bias behind the map needs): [N, C] instead
+    # of a reduction over the whole map
+    index._colsums[dseg.data_ptr()] = (dout.sum(0), dseg.shape)
+    return dseg
+
+
+def _map_slice(seg):
+    """``(base address, pixel pitch, channel offset)`` if ``seg`` [B,C,H,W] is a channel slice of a wider NHWC buffer, else None."""
+    B, C, H, W = seg.shape
+    if seg.stride(1) == 1 and seg.stride(3) > C and seg.stride(2) == W * seg.stride(3) and seg.stride(0) == H * W * seg.stride(3):
+        off = seg.storage_offset() % seg.stride(3)
+        return (seg.data_ptr() - 4 * off, int(seg.stride(3)), int(off))
+    return None
+
+
+class SelectedKeys:
+    """Pixel keys chosen for the points of ``index`` (``losses.cross_modal_dense``: one key per point, inside the map) and, built
+    lazily by the first backward pass that needs it, their stable sort - once per selection."""
+
+    def __init__(self, index: PixelIndex, key):
+        if key.dtype != torch.int32 or key.dim() != 1 or key.shape[0] != max(index.n, 1) or not key.is_contiguous():
+            raise ValueError(f"lift_at: the selected keys must be a contiguous int32 tensor [{max(index.n, 1)}], not {key.dtype} {tuple(key.shape)}")
+        self.index, self.key = index, key
+        self.skey = self.order = None
+
+    def sorted(self, B):
+        if self.skey is None:
+            L = _lib.lib()
+            n, dev = self.index.n, self.key.device
+            self.skey, self.order = torch.empty_like(self.key), torch.empty_like(self.key)
+            ws = _lib.workspace.get(int(L.mm_lift_index_ws_bytes(n)), dev)
+            from .scn import metadata as _md
+
+            check(L.mm_lift_sort_keys(ptr(self.key), n, B * self.index.H * self.index.W, _md.NO_SPIN[0], ptr(self.skey), ptr(self.order),
+                                      ptr(ws), ws.numel(), stream()), "lift_sort_keys")
+        return self.skey, self.order
+
+
+class _LiftAtFn(torch.autograd.Function):
+    """``_LiftFn`` at selected keys: the gather reads ``sel.key`` instead of the points' own pixels; the backward sorts the selection
+    (once) and scatters through the same kernel into the same joint gradient buffer, and files the same per-channel sum."""
+
+    @staticmethod
+    def forward(ctx, seg, index: PixelIndex, sel: SelectedKeys):
+        _lib.require_cuda(seg, "seg")
+        L = _lib.lib()
+        seg = seg.to(F32)
+        B, C, H, W = seg.shape
+        assert (H, W) == (index.H, index.W) and sel.index is index
+        out = torch.empty((index.n, C), dtype=F32, device=seg.device)
+        check(L.mm_lift_gather_key(ptr(seg), seg.stride(0), seg.stride(2), seg.stride(3), seg.stride(1), ptr(sel.key), index.n, C, H, W,
+                                   ptr(out), stream()), "lift_gather")
+        ctx.index, ctx.sel, ctx.shape, ctx.slice = index, sel, seg.shape, _map_slice(seg)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        skey, order = ctx.sel.sorted(ctx.shape[0])
+        return _scatter(ctx, dout, skey, order, True), None, None
+
+
+def lift_at(seg, index: PixelIndex, sel_key):
+    """seg [B,C,H,W] (any strides) -> [N_points, C]: row i is the map at pixel ``sel_key[i]`` (int32 keys ``(b*H + y)*W + x`` inside
+    the map, or a :class:`SelectedKeys` that already wraps them) instead of at point i's own pixel.  The gradient of ``seg`` is the
+    sum of the row gradients per chosen pixel, in ascending point order - the selection is a constant.  The backward STORES into
+    the slice of the joint gradient buffer that ``lift(seg, index)`` would fill: lift a map either at its points or at selected
+    keys, and only once per batch."""
+    if not isinstance(sel_key, SelectedKeys):
+        sel_key = SelectedKeys(index, sel_key)
+    return _LiftAtFn.apply(seg, index, sel_key)
 
 
 def pop_colsum(index, dmap):

@@ -6,7 +6,9 @@ in the reference; ``cross_entropy`` (weighted, ignore_index -100, weighted-mean 
 errors per class with the segmented radix sort of csrc/lovasz.hip; ``target_entropy`` (entropy minimisation and its diversity guard on
 unlabelled rows) runs on the row kernels of csrc/infomax.hip; ``coral`` (Deep CORAL / LogCORAL alignment of the source and the target
 rows' covariances) on those of csrc/coral.hip; ``adversarial`` (a point discriminator on the softmax or self-information of the
-source and the target rows, AdaptSegNet / AdvEnt) on those of csrc/adv.hip; ``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
+source and the target rows, AdaptSegNet / AdvEnt) on those of csrc/adv.hip; ``cross_modal_dense`` (the cross-modal KL pair against
+the best pixel of a window round each point's own, the sparse-to-dense matching of DsCML) on the window search of csrc/xmdense.hip;
+``cross_entropy_pair`` / ``cross_entropy_soft_pair`` take a weight per
 tail row (``pselab.agreement_weights``) through a compile-time flag of the same kernels.
 """
 from __future__ import annotations
@@ -655,6 +657,74 @@ def kl_to_detached(pred, target):
 def cross_modal_loss(gt_for_2d, prediction_avg, gt_for_3d, prediction_3d):
     """train.py:157-184: each branch's aux head mimics the other branch's detached main head."""
     return kl_to_detached(prediction_avg, gt_for_2d), kl_to_detached(prediction_3d, gt_for_3d)
+
+
+XM_WINDOW_MAX = 3  # the largest window radius of mm_xm_search: 7 x 7 pixels
+
+
+def _window_search(seg, index, rows, radius, split, direction, counts):
+    """``(sel, klmin)`` of one ``mm_xm_search`` call over the detached map ``seg`` [B, C, H, W] (any strides) and ``rows`` [N, C]."""
+    L = _lib.lib()
+    seg = seg.detach()
+    if seg.dtype != F32:
+        seg = seg.float()
+    rows, ld = _lib.row_pitched(rows.detach())
+    B, C, H, W = seg.shape
+    sel = torch.empty(max(index.n, 1), dtype=torch.int32, device=seg.device)
+    klmin = torch.empty(index.n, dtype=F32, device=seg.device)
+    ws = _lib.workspace.get(int(L.mm_xm_search_ws_bytes()), seg.device)
+    check(L.mm_xm_search(ptr(seg), seg.stride(0), seg.stride(2), seg.stride(3), seg.stride(1), B, H, W, C, ptr(index.key), ptr(rows), ld,
+                         index.n, split, radius, direction, ptr(sel), ptr(klmin), ptr(counts), ptr(ws), ws.numel(), stream()), "xm_search")
+    return sel, klmin
+
+
+def cross_modal_dense(gt_for_2d, map_avg, map_main, prediction_3d, index, radius, split=None):
+    """The cross-modal KL pair of :func:`cross_modal_loss` with each point matched against the DENSE 2D prediction in the
+    ``(2 radius + 1)^2`` pixel window round its own pixel instead of against that one pixel (the sparse-to-dense matching of DsCML,
+    Peng et al., ICCV 2021, as a hard minimum).  ``gt_for_2d`` [N, C]: the 3D main head's rows (teacher of the 2D term);
+    ``map_avg`` / ``map_main`` [B, C, H, W]: the dense logits of the 2D aux and main head (``seg_logit_avg_2d``, ``seg_logit_2d``;
+    any strides, e.g. the halves of one NHWC buffer); ``prediction_3d`` [N, C]: the 3D aux head's rows; ``index``: the batch's
+    ``lifting.PixelIndex``.  The candidates of point i are the pixels of its window inside its own image, the centre first, then
+    row-major.  ``j*(i) = argmin_j KL(softmax(gt_for_2d_i) || softmax(map_avg_j))`` and
+    ``k*(i) = argmin_j KL(softmax(map_main_j) || softmax(prediction_3d_i))``: the smallest value, the earliest among equal ones, a
+    NaN is skipped, nothing left keeps the centre.  The selection is a constant of the gradient (the sub-gradient of a minimum).
+
+    Returns ``(pairs, info)``.  ``pairs``: one ``(loss_avg, loss_3d)`` per row range - ``split=None``: all rows; ``split=P``: rows
+    ``[0, P)``, then rows ``[P, N)`` - with ``loss_avg = kl_to_detached(map_avg[j*], gt_for_2d)`` and ``loss_3d =
+    kl_to_detached(prediction_3d, map_main[k*])`` over the range's rows; an empty range gives 0 and no gradient.  ``map_avg`` is
+    lifted ONCE for all ranges (``lifting.lift_at``: its backward stores into the gradient slot the plain ``lift`` of that map would
+    fill - do not also back-propagate through that one).  ``info``: ``sel_2d`` / ``sel_3d`` (int32 [N] pixel keys), ``klmin_2d`` /
+    ``klmin_3d`` (fp32 [N], the matched rows' KL), ``moved`` / ``shift`` (int64 [2, 2]: per term 2D / 3D and per range, the rows
+    whose match left the centre and the sum of their Chebyshev displacements), all on the device.  ``radius`` 0 is the plain pair.
+    Two launches per search, no host read; bit-stable run to run."""
+    from . import lifting
+
+    who = "cross_modal_dense"
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= XM_WINDOW_MAX:
+        raise ValueError(f"{who}: radius must be an integer in [0, {XM_WINDOW_MAX}], not {radius!r}")
+    N = index.n
+    for name, t in (("gt_for_2d", gt_for_2d), ("prediction_3d", prediction_3d)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != N or t.shape[1] != map_avg.shape[1]:
+            raise ValueError(f"{who}: {name} must be [{N}, {map_avg.shape[1]}] (a row per point of the index, a column per class)")
+    if tuple(map_avg.shape) != tuple(map_main.shape) or tuple(map_avg.shape[2:]) != (index.H, index.W):
+        raise ValueError(f"{who}: the maps are {tuple(map_avg.shape)} and {tuple(map_main.shape)}, the index has {index.H} x {index.W} pixels")
+    if split is not None and (isinstance(split, bool) or not isinstance(split, int) or not 0 <= split <= N):
+        raise ValueError(f"{who}: split {split!r} outside [0, {N}]")
+    _lib.require_cuda(map_avg, "map_avg")
+    P = N if split is None else split
+    counts = torch.empty((2, 4), dtype=torch.int64, device=map_avg.device)
+    sel_2d, kl_2d = _window_search(map_avg, index, gt_for_2d, radius, P, 0, counts[0])
+    sel_3d, kl_3d = _window_search(map_main, index, prediction_3d, radius, P, 1, counts[1])
+    matched_avg = lifting.lift_at(map_avg, index, sel_2d)
+    matched_main = lifting.lift_at(map_main.detach(), index, sel_3d)
+    pairs = []
+    for lo, hi in ((0, N),) if split is None else ((0, P), (P, N)):
+        if hi == lo:
+            zero = torch.zeros((), dtype=F32, device=map_avg.device)
+            pairs.append((zero, zero))
+        else:
+            pairs.append((kl_to_detached(matched_avg[lo:hi], gt_for_2d[lo:hi]), kl_to_detached(prediction_3d[lo:hi], matched_main[lo:hi])))
+    return pairs, dict(sel_2d=sel_2d[:N], sel_3d=sel_3d[:N], klmin_2d=kl_2d, klmin_3d=kl_3d, moved=counts[:, :2], shift=counts[:, 2:])
 
 
 # ---------------------------------------------------------------------------------------------- registry (reference API)

@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, adversarial, coral, domains, fda, infomax
+from . import _lib, adversarial, coral, domains, fda, infomax, xmdense
 from .ddp import GradAllReducer, ranks_share_a_gpu
 from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
@@ -127,6 +127,8 @@ class TrainModel(nn.Module):
         self.adversary = adversarial.OutputAdversary(train_kwargs)
         # the source images in the target images' style before the 2D network sees them (``fda_beta``, ``fda_image_norm``): fda.InputStyle, forwarded too
         self.input_style = fda.InputStyle(train_kwargs)
+        # the cross-modal KL terms against the best pixel of a window round each point's own (``xm_window``): xmdense.DenseMatching, forwarded too
+        self.dense_xm = xmdense.DenseMatching(train_kwargs)
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -228,7 +230,10 @@ class TrainModel(nn.Module):
         src, trg = batch["source"], batch["target"]
         n2d, n3d = self.modules_name[0], self.modules_name[1]
         st, te, al, adv = self.selftrain, self.target_entropy, self.alignment, self.adversary
+        dx = self.dense_xm if stage == "train" and self.dense_xm.active else None
         te.begin_step(self)
+        if dx is not None:
+            dx.begin_step()
         styled = stage == "train" and self.input_style.active
         if styled:
             src = self.input_style.style(src, trg)  # a shallow copy with the styled images: the caller's batch stays as it is
@@ -323,8 +328,11 @@ class TrainModel(nn.Module):
                 seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
                 if pseudo is not None:
                     _, _, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo)
-            xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
-            xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
+            if dx is not None:  # ONE matched lift of the aux map over all rows: the plain lifted a2d takes no part in the loss
+                (xs2d, xs3d), (xt2d, xt3d) = dx.terms(l3d, a3d, aux2d, p2d, both, P)
+            else:
+                xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
+                xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
             im = te.terms(l2d, l3d, P)
             ca = al.terms(l2d, l3d, P)
             ad = adv.terms(l2d, l3d, P) if adv.active else None
@@ -336,13 +344,19 @@ class TrainModel(nn.Module):
             p3d, _, aux3d = self(src, model_name=n3d)
             seg2d = self.loss("segmentation", pred=p2d["seg_logit"], gt=src["seg_label"])
             seg3d = self.loss("segmentation", pred=p3d["seg_logit"], gt=src["seg_label"])
-            xs2d, xs3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
-                                               aux3d["seg_logit_point"])
+            if dx is not None:
+                ((xs2d, xs3d),) = dx.terms(p3d["seg_logit"], aux3d["seg_logit_point"], aux2d, p2d, src)
+            else:
+                xs2d, xs3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
+                                                   aux3d["seg_logit_point"])
             src2d, src3d = p2d["seg_logit"], p3d["seg_logit"]
             p2d, _, _, aux2d = self(trg, model_name=n2d)
             p3d, _, aux3d = self(trg, model_name=n3d)
-            xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
-                                               aux3d["seg_logit_point"])
+            if dx is not None:
+                ((xt2d, xt3d),) = dx.terms(p3d["seg_logit"], aux3d["seg_logit_point"], aux2d, p2d, trg)
+            else:
+                xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
+                                                   aux3d["seg_logit_point"])
             if pseudo is not None:
                 _, _, pl2d, pl3d = st.losses(p2d["seg_logit"], p3d["seg_logit"], 0, pseudo)
             im = te.terms(p2d["seg_logit"], p3d["seg_logit"], 0)
@@ -354,6 +368,8 @@ class TrainModel(nn.Module):
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
             f"{stage}/xm_loss_src_3d": xs3d, f"{stage}/xm_loss_tgt_3d": xt3d,
         }
+        if dx is not None:
+            dx.log(self.last_logs, stage)
         loss_2d = seg2d + self.lambda_xm_src * xs2d + self.lambda_xm_trg * xt2d
         loss_3d = seg3d + self.lambda_xm_src * xs3d + self.lambda_xm_trg * xt3d
         if pseudo is not None:
@@ -690,7 +706,7 @@ class TrainModel(nn.Module):
 
 
 for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED), ("alignment", coral.FORWARDED),
-                       ("adversary", adversarial.FORWARDED), ("input_style", fda.FORWARDED)):
+                       ("adversary", adversarial.FORWARDED), ("input_style", fda.FORWARDED), ("dense_xm", xmdense.FORWARDED)):
     for _name in _names:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
         setattr(TrainModel, _name, property(lambda self, n=_name, o=_owner: getattr(getattr(self, o), n),
                                             lambda self, value, n=_name, o=_owner: setattr(getattr(self, o), n, value)))
