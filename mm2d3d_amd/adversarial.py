@@ -5,9 +5,7 @@ import math
 import torch
 
 from .losses import ADV_HIDDEN, ADV_MODES, adversarial, adversarial_param_count
-
-FORWARDED = ("lambda_adv", "adv_input", "adv_hidden", "adv_lr", "adv_betas", "adv_seed",
-             "last_adversary")  # the options and the state the trainer forwards by name
+from .stepopts import NON_NEGATIVE, LogitTerm, number
 
 
 def initial_parameters(C, hidden, generator):
@@ -24,14 +22,7 @@ def initial_parameters(C, hidden, generator):
     return flat
 
 
-def _number(train_kwargs, name, default, ok, what):
-    v = train_kwargs.get(name, default)
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(float(v)):
-        raise ValueError(f"train_kwargs['{name}'] must be {what}, not {v!r}")
-    return float(v)
-
-
-class OutputAdversary:
+class OutputAdversary(LogitTerm):
     """With ``lambda_adv`` > 0 each main head gets a discriminator D on its per-point logits - a point-wise MLP (two hidden layers
     of ``adv_hidden`` = 16, 32 or 64 units, LeakyReLU 0.2) that tells source rows from target rows - and the head learns to fool
     it: loss_2d += lambda_adv * loss_g(l2d), the same for 3D, loss_g = the target rows' binary cross entropy against the label
@@ -56,15 +47,18 @@ class OutputAdversary:
     ``lambda_adv`` 0.0 (default): nothing is built, called or allocated, no log key appears, the step is launch for launch the
     step without the option.  The other options are validated whatever the weight is."""
 
+    FORWARDED = ("lambda_adv", "adv_input", "adv_hidden", "adv_lr", "adv_betas", "adv_seed", "last_adversary")
+    READS_SOURCE = True
+
     def __init__(self, train_kwargs):
-        self.lambda_adv = _number(train_kwargs, "lambda_adv", 0.0, lambda v: 0.0 <= v < math.inf, "a finite number >= 0")
+        self.lambda_adv = number(train_kwargs, "lambda_adv", 0.0, *NON_NEGATIVE)
         self.adv_input = train_kwargs.get("adv_input", "selfinfo")
         if not isinstance(self.adv_input, str) or self.adv_input not in ADV_MODES:
             raise ValueError(f"train_kwargs['adv_input'] must be \"selfinfo\" or \"softmax\", not {self.adv_input!r}")
         self.adv_hidden = train_kwargs.get("adv_hidden", 64)
         if isinstance(self.adv_hidden, bool) or not isinstance(self.adv_hidden, int) or self.adv_hidden not in ADV_HIDDEN:
             raise ValueError(f"train_kwargs['adv_hidden'] must be 16, 32 or 64, not {self.adv_hidden!r}")
-        self.adv_lr = _number(train_kwargs, "adv_lr", 1e-4, lambda v: 0.0 <= v < math.inf, "a finite number >= 0")
+        self.adv_lr = number(train_kwargs, "adv_lr", 1e-4, *NON_NEGATIVE)
         b = train_kwargs.get("adv_betas", (0.9, 0.99))
         if not isinstance(b, (tuple, list)) or len(b) != 2 or any(
                 isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) < 1.0 for v in b):

@@ -1,13 +1,10 @@
 """Correlation alignment of the source and the target batch in the two-domain step (train.py): everything
 ``train_kwargs["lambda_coral"]``, ``["coral"]`` and ``["coral_eps"]`` switch on, in one policy object."""
-import math
-
 from .losses import CORAL_MODES, coral
+from .stepopts import NON_NEGATIVE, POSITIVE, LogitTerm, number
 
-FORWARDED = ("lambda_coral", "coral", "coral_eps", "last_coral")  # the options and the state the trainer forwards by name
 
-
-class DomainAlignment:
+class DomainAlignment(LogitTerm):
     """With ``lambda_coral`` > 0 each main head also aligns the second-order statistics of its logits on the SOURCE rows with
     those on the TARGET rows - no extra forward, one ``losses.coral`` call per head on the [source | target] logits the step
     already holds: loss_2d += lambda_coral * coral(l2d, P), the same for 3D.  ``coral``: "log" (default; Deep LogCORAL, Morerio et
@@ -21,18 +18,15 @@ class DomainAlignment:
     entries and composes with all of them; validation, test and ``predict_step`` do not evaluate it.  ``lambda_coral`` 0.0
     (default): nothing is called or allocated, no log key appears, the step is launch for launch the step without the option."""
 
+    FORWARDED = ("lambda_coral", "coral", "coral_eps", "last_coral")
+    READS_SOURCE = True
+
     def __init__(self, train_kwargs):
-        v = train_kwargs.get("lambda_coral", 0.0)
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) < math.inf:
-            raise ValueError(f"train_kwargs['lambda_coral'] must be a finite number >= 0, not {v!r}")
-        self.lambda_coral = float(v)
+        self.lambda_coral = number(train_kwargs, "lambda_coral", 0.0, *NON_NEGATIVE)
         self.coral = train_kwargs.get("coral", "log")
         if not isinstance(self.coral, str) or self.coral not in CORAL_MODES:
             raise ValueError(f"train_kwargs['coral'] must be \"log\" or \"plain\", not {self.coral!r}")
-        e = train_kwargs.get("coral_eps", 1e-4)
-        if isinstance(e, bool) or not isinstance(e, (int, float)) or not 0.0 < float(e) < math.inf:
-            raise ValueError(f"train_kwargs['coral_eps'] must be a finite number > 0, not {e!r}")
-        self.coral_eps = float(e)
+        self.coral_eps = number(train_kwargs, "coral_eps", 1e-4, *POSITIVE)
         self.last_coral = None
 
     @property

@@ -7,18 +7,11 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
-
-FORWARDED = ("fda_beta", "fda_image_norm", "last_fda")  # the options and the state the trainer forwards by name
+from .stepopts import StepOption, number
 
 MAX_BAND, MAX_CHANNELS, MAX_SIDE = 32, 4, 2048  # csrc/fda.hip
 
 _NORM = {}  # (device index, mean, std) -> fp32 [2, C] on the device: written once, so that a step copies nothing from the host
-
-
-def _beta(beta, name):
-    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= float(beta) < 0.5:
-        raise ValueError(f"{name} must be a number in [0, 0.5), not {beta!r}")
-    return float(beta)
 
 
 def _image_norm(image_norm, name):
@@ -69,7 +62,9 @@ def fda_transfer(src, trg, beta, image_norm=None):
         raise ValueError(f"{who}: src has {C} channels, the kernels take 1 to {MAX_CHANNELS}")
     if H < 1 or W < 1 or H > MAX_SIDE or W > MAX_SIDE:
         raise ValueError(f"{who}: src images of {H} x {W}, the kernels take 1 to {MAX_SIDE} on a side")
-    band = band_of(H, W, _beta(beta, f"{who}: beta"))
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= float(beta) < 0.5:
+        raise ValueError(f"{who}: beta must be a number in [0, 0.5), not {beta!r}")
+    band = band_of(H, W, beta)
     if band > MAX_BAND or 2 * band + 1 > min(H, W):
         raise ValueError(f"{who}: beta {beta!r} gives a band of {band} at {H} x {W}, the kernels take 0 to {MAX_BAND}")
     norm = _image_norm(image_norm, f"{who}: image_norm")
@@ -97,7 +92,7 @@ def fda_transfer(src, trg, beta, image_norm=None):
     return dict(img=out, band=band, mse=mse)
 
 
-class InputStyle:
+class InputStyle(StepOption):
     """With ``fda_beta`` set, every TRAIN step styles its source camera images after its target images before the 2D network sees
     them: ``img = fda_transfer(source img, target img, fda_beta, fda_image_norm)["img"]``, in the joined pass and in the two-call
     path alike - source geometry and labels in the target's exposure, colour cast and tone.  ``fda_image_norm``: the loaders'
@@ -109,9 +104,10 @@ class InputStyle:
     styles its own batch.  Composes with every output-level option.  ``fda_beta`` None (default): nothing is called or
     allocated, no log key appears, the step is launch for launch the step without the option."""
 
+    FORWARDED = ("fda_beta", "fda_image_norm", "last_fda")
+
     def __init__(self, train_kwargs):
-        b = train_kwargs.get("fda_beta")
-        self.fda_beta = None if b is None else _beta(b, "train_kwargs['fda_beta']")
+        self.fda_beta = number(train_kwargs, "fda_beta", None, lambda v: 0.0 <= v < 0.5, "a number in [0, 0.5)")
         self.fda_image_norm = _image_norm(train_kwargs.get("fda_image_norm"), "train_kwargs['fda_image_norm']")
         self.last_fda = None
 
@@ -128,4 +124,5 @@ class InputStyle:
         return dict(src, img=self.last_fda["img"])
 
     def log(self, logs, stage):
-        logs[f"{stage}/fda_mse"] = self.last_fda["mse"].mean()
+        if self.active:
+            logs[f"{stage}/fda_mse"] = self.last_fda["mse"].mean()

@@ -1,15 +1,12 @@
 """Target-domain entropy and diversity terms of the two-domain step (train.py): everything ``train_kwargs["lambda_minent"]`` and
 ``["lambda_div"]`` switch on, in one policy object."""
-import math
-
 import torch
 
 from .losses import class_prior, target_entropy
+from .stepopts import NON_NEGATIVE, LogitTerm, number
 
-FORWARDED = ("lambda_minent", "lambda_div", "div_prior", "last_target_mass")  # the options and the state the trainer forwards by name
 
-
-class TargetEntropy:
+class TargetEntropy(LogitTerm):
     """With ``lambda_minent`` > 0 or ``lambda_div`` > 0 each main head also learns from its own predictions of the unlabelled TARGET
     rows - no teacher pass, no extra forward, one ``losses.target_entropy`` call per head: loss_2d += lambda_minent * ent2d +
     lambda_div * div2d, the same for 3D.  ``ent``: the mean softmax entropy of the target rows over ln C (entropy minimisation,
@@ -23,14 +20,11 @@ class TargetEntropy:
     with all of them; validation, test and ``predict_step`` do not evaluate them.  Both weights 0.0 (default): nothing is called
     or allocated, no log key appears, the step is launch for launch the step without the options."""
 
-    def __init__(self, train_kwargs):
-        def weight(name):
-            v = train_kwargs.get(name, 0.0)
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) < math.inf:
-                raise ValueError(f"train_kwargs['{name}'] must be a finite number >= 0, not {v!r}")
-            return float(v)
+    FORWARDED = ("lambda_minent", "lambda_div", "div_prior", "last_target_mass")
 
-        self.lambda_minent, self.lambda_div = weight("lambda_minent"), weight("lambda_div")
+    def __init__(self, train_kwargs):
+        self.lambda_minent = number(train_kwargs, "lambda_minent", 0.0, *NON_NEGATIVE)
+        self.lambda_div = number(train_kwargs, "lambda_div", 0.0, *NON_NEGATIVE)
         # normalised here once; a tuple, so that the loss call finds its device copy without a host read
         self.div_prior = class_prior(train_kwargs.get("div_prior"), "train_kwargs['div_prior']")
         self.last_target_mass = None

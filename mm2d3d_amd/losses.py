@@ -51,21 +51,25 @@ class _CrossEntropyFn(torch.autograd.Function):
         return d, None, None, None
 
 
-_WEIGHT_CACHE = {}  # (class weights, device) -> device tensor
+_UPLOADED = {"weight": {}, "prior": {}}  # kind -> {(values, device): device tensor}
+
+
+def _uploaded(kind, values, device, upload):
+    """A host sequence of numbers on ``device``, uploaded ONCE per device.  torch.tensor(list, device=cuda) is a pageable
+    host-to-device copy - the host waits until the stream has reached it, i.e. for the whole forward pass queued before the loss:
+    3.3 ms per call in the host profile of round 5, twice per step."""
+    cache, key = _UPLOADED[kind], (values, device)
+    hit = cache.get(key)
+    if hit is None:
+        if len(cache) > 64:
+            cache.clear()
+        hit = cache[key] = upload()
+    return hit
 
 
 def _device_weight(weight, device):
-    if isinstance(weight, (list, tuple)):
-        # the class weights of a config come as a Python list (config.yaml:45): uploaded ONCE per device.  torch.tensor(list,
-        # device=cuda) is a pageable host-to-device copy - the host waits until the stream has reached it, i.e. for the whole
-        # forward pass queued before the loss: 3.3 ms per call in the host profile of round 5, twice per step.
-        key = (tuple(float(v) for v in weight), device)
-        hit = _WEIGHT_CACHE.get(key)
-        if hit is None:
-            if len(_WEIGHT_CACHE) > 64:
-                _WEIGHT_CACHE.clear()
-            hit = _WEIGHT_CACHE[key] = torch.tensor(weight, dtype=F32, device=device)
-        weight = hit
+    if isinstance(weight, (list, tuple)):  # the class weights of a config come as a Python list (config.yaml:45)
+        weight = _uploaded("weight", tuple(float(v) for v in weight), device, lambda: torch.tensor(weight, dtype=F32, device=device))
     elif weight is not None:
         weight = weight.to(device=device, dtype=F32).contiguous()
     return weight
@@ -359,6 +363,20 @@ def lovasz_softmax(pred, gt, classes="present", ignore_index=-100):
     return _LovaszFn.apply(pred, gt, 1 if classes == "all" else 0, int(ignore_index))
 
 
+def _check_rows(who, x, name, first_row, width, columns):
+    """What the two-segment row losses ask of ``x`` [N, ``width``] (2 to 32 ``columns``, N * width < 2^31) and ``first_row``; the width."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"{who}: {name} must be [N, {width}]")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    if not 2 <= C <= 32:
+        raise ValueError(f"{who}: {C} {columns}, the row kernels take 2 to 32")
+    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
+        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
+    if N * C >= 1 << 31:
+        raise ValueError(f"{who}: {N} rows of {C} {columns}, N * {width} must stay below 2^31")
+    return C
+
+
 class _TargetEntropyFn(torch.autograd.Function):
     """Entropy and diversity of rows [first_row, N) of ``logits`` (csrc/infomax.hip): two forward launches leave both scalars, the
     class mass, the row count and ``aux`` (ln(mass / prior) per class, 1 / (n ln C)); ONE backward launch writes the whole gradient
@@ -399,9 +417,6 @@ class _TargetEntropyFn(torch.autograd.Function):
         return d, None, None
 
 
-_PRIOR_CACHE = {}  # (normalised prior, device) -> device tensor
-
-
 def class_prior(prior, who="target_entropy"):
     """``prior`` (None, a sequence or a 1-D tensor of positive finite numbers) as a tuple of floats that sums to 1, or None."""
     if prior is None:
@@ -416,17 +431,10 @@ def class_prior(prior, who="target_entropy"):
 
 
 def _device_prior(prior, device):
-    """A normalised prior (``class_prior``) on ``device``: uploaded once per device (as ``_device_weight``: a pageable upload makes
-    the host wait for the stream)."""
+    """A normalised prior (``class_prior``) on ``device``: uploaded once per device, rounded from float64."""
     if prior is None:
         return None
-    key = (prior, device)
-    hit = _PRIOR_CACHE.get(key)
-    if hit is None:
-        if len(_PRIOR_CACHE) > 64:
-            _PRIOR_CACHE.clear()
-        hit = _PRIOR_CACHE[key] = torch.tensor(prior, dtype=torch.float64).to(F32).to(device)
-    return hit
+    return _uploaded("prior", prior, device, lambda: torch.tensor(prior, dtype=torch.float64).to(F32).to(device))
 
 
 def target_entropy(pred, first_row=0, prior=None):
@@ -444,15 +452,7 @@ def target_entropy(pred, first_row=0, prior=None):
     parallelism each rank's own batch mean, as batch-norm statistics are, not reduced over ranks.  ``pred`` may be fp16, bf16 or a
     row-pitched view (``stride(1) == 1``), which is read in place.  Bit-stable run to run."""
     who = "target_entropy"
-    if not torch.is_tensor(pred) or pred.dim() != 2:
-        raise ValueError(f"{who}: pred must be [N, C]")
-    N, C = int(pred.shape[0]), int(pred.shape[1])
-    if not 2 <= C <= 32:
-        raise ValueError(f"{who}: {C} classes, the row kernels take 2 to 32")
-    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
-        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
-    if N * C >= 1 << 31:
-        raise ValueError(f"{who}: {N} rows of {C} classes, N * C must stay below 2^31")
+    C = _check_rows(who, pred, "pred", first_row, "C", "classes")
     prior = class_prior(prior, who)
     if prior is not None and len(prior) != C:
         raise ValueError(f"{who}: the prior has {len(prior)} entries for C = {C} classes")
@@ -522,15 +522,7 @@ def coral(x, first_row, mode="log", eps=1e-4):
         raise ValueError(f'{who}: mode must be "log" or "plain", not {mode!r}')
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < float(eps) < float("inf"):
         raise ValueError(f"{who}: eps must be a finite number > 0, not {eps!r}")
-    if not torch.is_tensor(x) or x.dim() != 2:
-        raise ValueError(f"{who}: x must be [N, d]")
-    N, d = int(x.shape[0]), int(x.shape[1])
-    if not 2 <= d <= 32:
-        raise ValueError(f"{who}: {d} columns, the row kernels take 2 to 32")
-    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
-        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
-    if N * d >= 1 << 31:
-        raise ValueError(f"{who}: {N} rows of {d} columns, N * d must stay below 2^31")
+    _check_rows(who, x, "x", first_row, "d", "columns")
     _lib.require_cuda(x, "x")
     loss, count, mean, cov = _CoralFn.apply(x, first_row, CORAL_MODES[mode], float(eps))
     return dict(loss=loss, count=count, mean=mean, cov=cov)
@@ -605,15 +597,7 @@ def adversarial(x, first_row, params, mode="selfinfo", hidden=64):
         raise ValueError(f'{who}: mode must be "selfinfo" or "softmax", not {mode!r}')
     if isinstance(hidden, bool) or not isinstance(hidden, int) or hidden not in ADV_HIDDEN:
         raise ValueError(f"{who}: hidden must be 16, 32 or 64, not {hidden!r}")
-    if not torch.is_tensor(x) or x.dim() != 2:
-        raise ValueError(f"{who}: x must be [N, C]")
-    N, C = int(x.shape[0]), int(x.shape[1])
-    if not 2 <= C <= 32:
-        raise ValueError(f"{who}: {C} classes, the row kernels take 2 to 32")
-    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row <= N:
-        raise ValueError(f"{who}: first_row {first_row!r} outside [0, {N}]")
-    if N * C >= 1 << 31:
-        raise ValueError(f"{who}: {N} rows of {C} classes, N * C must stay below 2^31")
+    C = _check_rows(who, x, "x", first_row, "C", "classes")
     need = adversarial_param_count(C, hidden)
     if not torch.is_tensor(params) or params.dtype != F32 or params.dim() != 1 or params.numel() != need or not params.is_contiguous():
         raise ValueError(f"{who}: params must be a flat contiguous float32 tensor of {need} elements for C = {C}, hidden = {hidden}")

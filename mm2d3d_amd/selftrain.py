@@ -6,10 +6,7 @@ import torch
 
 from . import gradsink, pselab
 from .losses import cross_entropy_pair, cross_entropy_soft_pair
-
-FORWARDED = ("lambda_pl", "pseudo_labels", "pseudo_label_source", "pl_threshold", "pl_threshold_momentum", "pl_threshold_warmup",
-             "pl_targets", "pl_temperature", "pl_adaptive", "last_teacher", "pl_agreement",
-             "last_agreement")  # the options and the state the trainer forwards by name
+from .stepopts import POSITIVE, StepOption, number
 
 
 class Target(NamedTuple):
@@ -36,7 +33,7 @@ def _as_teacher(model, ema):
             m.training = was
 
 
-class SelfTraining:
+class SelfTraining(StepOption):
     """Self-training (the second round: pselab.export_pseudo_labels -> the loaders' ``pselab_paths=`` -> here): with
     ``lambda_pl`` > 0 each main head also learns from the pseudo labels of the TARGET batch, loss_2d += lambda_pl * pl2d and
     loss_3d += lambda_pl * pl3d, logged as ``{stage}/pl_loss_tgt_2d`` / ``_3d``.  pl* = unweighted cross entropy of the head's
@@ -85,6 +82,10 @@ class SelfTraining:
     rows of this step, detached.  No state: nothing to checkpoint or to reduce.  ``last_agreement`` = dict(weight [n],
     mean_weight, mean_div), logged as ``train/pl_agree_w`` / ``train/pl_agree_div``; device tensors all."""
 
+    FORWARDED = ("lambda_pl", "pseudo_labels", "pseudo_label_source", "pl_threshold", "pl_threshold_momentum", "pl_threshold_warmup",
+                 "pl_targets", "pl_temperature", "pl_adaptive", "last_teacher", "pl_agreement",
+                 "last_agreement")
+
     def __init__(self, train_kwargs, ema_decay=None, overlap_metadata=False, overlap_branches=0):
         def option(name, default, ok, must):
             v = train_kwargs.get(name, default)
@@ -92,30 +93,26 @@ class SelfTraining:
                 raise ValueError(f"train_kwargs['{name}'] must be {must}, not {v!r}")
             return v
 
-        number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
         self.lambda_pl = float(option("lambda_pl", 0.0, lambda v: float(v) >= 0.0, ">= 0"))
         self.pseudo_labels = option("pseudo_labels", "own", lambda v: v in ("own", "ensemble"), "'own' or 'ensemble'")
         self.pseudo_label_source = option("pseudo_label_source", "batch", lambda v: v in ("batch", "teacher"), "'batch' or 'teacher'")
         self.pl_threshold = thr = option("pl_threshold", None, lambda v: v is None or (isinstance(v, str) and v in ("median", "adaptive"))
-                                         or (number(v) and 0.0 < v <= 1.0), "None, 'median', 'adaptive' or a number in (0, 1]")
+                                         or (isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 < v <= 1.0),
+                                         "None, 'median', 'adaptive' or a number in (0, 1]")
         if isinstance(thr, str) and thr == "adaptive" and self.pseudo_label_source != "teacher":
             raise ValueError("train_kwargs['pl_threshold'] = 'adaptive' needs pseudo_label_source='teacher': the thresholds follow "
                              "the teacher's predictions of every target batch")
-        self.pl_threshold_momentum = float(option("pl_threshold_momentum", 0.999, lambda v: number(v) and 0.0 <= v < 1.0, "a number in [0, 1)"))
+        self.pl_threshold_momentum = number(train_kwargs, "pl_threshold_momentum", 0.999, lambda v: 0.0 <= v < 1.0, "a number in [0, 1)")
         self.pl_threshold_warmup = bool(train_kwargs.get("pl_threshold_warmup", False))
         self.pl_targets = option("pl_targets", "hard", lambda v: v in ("hard", "soft"), "'hard' or 'soft'")
-        T = option("pl_temperature", 1.0, lambda v: number(v) and 0.0 < v < float("inf"), "a finite number > 0")
-        self.pl_temperature = float(T)
+        self.pl_temperature = number(train_kwargs, "pl_temperature", 1.0, *POSITIVE)
         if self.pl_targets == "hard" and self.pl_temperature != 1.0:
-            raise ValueError(f"train_kwargs['pl_temperature'] = {T!r} with pl_targets='hard': an arg-max has no temperature "
+            raise ValueError(f"train_kwargs['pl_temperature'] = {train_kwargs['pl_temperature']!r} with pl_targets='hard': an arg-max has no temperature "
                              "(it would be silently meaningless); use pl_targets='soft'")
         if self.pl_targets == "soft" and thr == "median":
             raise ValueError("train_kwargs['pl_threshold'] = 'median' is refused with pl_targets='soft': the refinement works on "
                              "labels; give a number in (0, 1] or None")
-        self.pl_agreement = option("pl_agreement", None, lambda v: v is None or (number(v) and 0.0 < v < float("inf")),
-                                   "None or a finite number > 0 (beta of w = exp(-beta * D))")
-        if self.pl_agreement is not None:
-            self.pl_agreement = float(self.pl_agreement)
+        self.pl_agreement = number(train_kwargs, "pl_agreement", None, POSITIVE[0], "None or a finite number > 0 (beta of w = exp(-beta * D))")
         # checked whatever lambda_pl is: a schedule that starts at 0 must not hide a configuration that cannot run later
         why = ("ema_decay is None (the teacher is the EMA of the weights)" if ema_decay is None else
                "overlap_metadata is on" if overlap_metadata else f"overlap_branches is {overlap_branches}" if overlap_branches != 0 else None)

@@ -7,16 +7,34 @@ logged keys ``train/loss_segmentation`` ...), and ``fit_step`` does what Lightni
 """
 from __future__ import annotations
 
+import collections
+import contextlib
+import gc
 import os
 
 import torch
 import torch.nn as nn
 
-from . import _lib, adversarial, coral, domains, fda, infomax, xmdense
+from . import _lib, adversarial, coral, domains, fda, infomax, nn2d, pselab, scn, selftrain, xmdense
+from . import conv2d as _c2d
+from .amp import GradScaler
+from .clip import clip_grad_norm_, clip_grad_value_, parse_clip
 from .ddp import GradAllReducer, ranks_share_a_gpu
+from .ema import WeightEMA
 from .losses import CrossEntropy, Loss, cross_modal_loss
 from .metrics import SegIoU
-from .selftrain import FORWARDED, SelfTraining
+from .scn import metadata as _md
+from .stepopts import LogitTerm
+
+# The optional parts of the training step (stepopts.StepOption), attribute name -> class: built in this order by the constructor,
+# forwarded as properties below the class, and asked in this order by every hook of the step, the optimisers and the checkpoint.
+OPTIONS = (("selftrain", selftrain.SelfTraining), ("target_entropy", infomax.TargetEntropy), ("alignment", coral.DomainAlignment),
+           ("adversary", adversarial.OutputAdversary), ("input_style", fda.InputStyle), ("dense_xm", xmdense.DenseMatching))
+
+# What the joined and the two-call pass hand the shared tail of the step.  pl*: the pseudo-label terms, or None; xm_*: the cross-modal
+# (2D, 3D) pair of the source and of the target rows; target_logits: (main 2D logits, main 3D logits, first target row) for a term on
+# the target rows alone; both_logits: the same for a term that reads the source rows too (None in the two-call pass when none is on).
+_Pass = collections.namedtuple("_Pass", "seg2d seg3d pl2d pl3d xm_src xm_trg target_logits both_logits")
 
 
 class TrainModel(nn.Module):
@@ -61,8 +79,6 @@ class TrainModel(nn.Module):
         # Absent: whatever nn2d.set_precision() selected (default 16).  `sparse_activations: "bf16" / "fp16"` additionally stores
         # the sparse rows of the 3D branch in 16 bits (BASELINE.json configs[4]); the reference's SparseConvNet is fp32-only, so
         # the default is fp32.
-        from . import nn2d, scn
-
         if "precision" in train_kwargs:
             nn2d.set_precision(train_kwargs["precision"])
         if "sparse_activations" in train_kwargs:
@@ -78,8 +94,6 @@ class TrainModel(nn.Module):
         # arguments through): None = off; "norm" clips ONE 2-norm over both networks' gradients (HybridOptim's param_groups is
         # the concatenation, train.py:587-592), "value" clamps every element.  On the reduced, unscaled gradients, on the device
         # (mm2d3d_amd/clip.py); ``last_grad_norm``: the norm before clipping of the last "norm" step, a device tensor.
-        from .clip import parse_clip
-
         self._clip = parse_clip((train_kwargs.get("gradient_clip_algorithm") or "norm", train_kwargs.get("gradient_clip_val")))
         self.last_grad_norm = None
         # The trainer's own C-ABI handle (include/mm2d3d.h mm_create: grid-barrier words, fault word and switches of the
@@ -116,19 +130,13 @@ class TrainModel(nn.Module):
         # keeps refilling them; what exactly keeps them from ever draining at that size was not found.
         # Never under data parallelism.
         self.overlap_branches = int(train_kwargs.get("overlap_branches", os.environ.get("MM_OVERLAP_BRANCHES", "0")))
-        # self-training (``lambda_pl``, ``pseudo_label*``, ``pl_*``): selftrain.SelfTraining owns options and state; forwarded below the class
-        self.selftrain = SelfTraining(train_kwargs, self.ema_decay, self.overlap_metadata, self.overlap_branches)
-        # entropy / diversity terms on the target rows (``lambda_minent``, ``lambda_div``, ``div_prior``): infomax.TargetEntropy, forwarded too
-        self.target_entropy = infomax.TargetEntropy(train_kwargs)
-        # correlation alignment of the source and the target rows' logits (``lambda_coral``, ``coral``, ``coral_eps``): coral.DomainAlignment, forwarded too
-        self.alignment = coral.DomainAlignment(train_kwargs)
-        # a point discriminator on each main head's logits and the adversarial term that fools it (``lambda_adv``, ``adv_*``):
-        # adversarial.OutputAdversary owns options, discriminators and their optimisers (NOT in self.optimizers); forwarded too
-        self.adversary = adversarial.OutputAdversary(train_kwargs)
-        # the source images in the target images' style before the 2D network sees them (``fda_beta``, ``fda_image_norm``): fda.InputStyle, forwarded too
-        self.input_style = fda.InputStyle(train_kwargs)
-        # the cross-modal KL terms against the best pixel of a window round each point's own (``xm_window``): xmdense.DenseMatching, forwarded too
-        self.dense_xm = xmdense.DenseMatching(train_kwargs)
+        # OPTIONS: one policy object per optional part of the step, documented on its class; each owns its ``train_kwargs`` options and
+        # its state (the adversary its discriminators' optimisers too: NOT in self.optimizers), forwarded by name below the class
+        for name, cls in OPTIONS:
+            extra = (self.ema_decay, self.overlap_metadata, self.overlap_branches) if name == "selftrain" else ()
+            setattr(self, name, cls(train_kwargs, *extra))
+        self._options = [getattr(self, name) for name, _ in OPTIONS]
+        self._logit_terms = [o for o in self._options if isinstance(o, LogitTerm)]
         self.gc_freeze = bool(train_kwargs.get("gc_freeze", True))
         self._side = None
         self._s3d = None
@@ -147,8 +155,6 @@ class TrainModel(nn.Module):
 
     def _use(self):
         """Context in which this trainer's operators launch through its own handle (created on first use, on the parameters' GPU)."""
-        import contextlib
-
         if self.handle is None:
             p = next(self.model.parameters(), None)
             if p is None or not p.is_cuda:
@@ -167,14 +173,13 @@ class TrainModel(nn.Module):
             self.optimizers.append(opt)
             self.schedulers.append(sched)
         self.reducer = GradAllReducer(self.optimizers)
-        self.adversary.check_reducer(self.reducer)  # the discriminators are not reduced over ranks
+        for option in self._options:
+            option.check_reducer(self.reducer)
         # the 2D trunk runs as two HIP graphs (mm2d3d_amd/graph2d.py); under an active data-parallel reducer only on request
         # (``ddp_graph``): its bucket hooks overlap more when the parameters' gradients complete one by one during backward
         n2d = self.model[self.modules_name[0]]
         n2d._mm_no_graph = bool(self.reducer.active) and not self.ddp_graph
         if self.reducer.active and self.ddp_graph:
-            from . import conv2d as _c2d
-
             _c2d.WGRAD_BATCH[0] = True  # the reducer switched the deferred slab sum off for its hooks' sake: the graphs have it captured
         if self.ddp_side_stream is None:
             self.ddp_side_stream = not ranks_share_a_gpu()
@@ -183,15 +188,11 @@ class TrainModel(nn.Module):
         # each rank's seed was
         self.reducer.sync_parameters(src=0)
         if self.ema_decay is not None:
-            from .ema import WeightEMA
-
             self.ema = WeightEMA(self.optimizers, self.model, float(self.ema_decay), warmup=self.ema_warmup)
         if self.gc_freeze:
             # Everything built so far (modules, parameters, optimiser state, torch itself) is long-lived.  Left in the collector's
             # oldest generation it is re-traversed by every full collection (87 ms measured for one pass here, during which the
             # GPU queue drains).  Frozen objects are skipped by the collector.
-            import gc
-
             gc.unfreeze()  # a previous trainer of this process may have frozen objects that are garbage by now
             gc.collect()
             gc.freeze()
@@ -228,163 +229,150 @@ class TrainModel(nn.Module):
 
     def _generic_step(self, batch, stage):
         src, trg = batch["source"], batch["target"]
-        n2d, n3d = self.modules_name[0], self.modules_name[1]
-        st, te, al, adv = self.selftrain, self.target_entropy, self.alignment, self.adversary
-        dx = self.dense_xm if stage == "train" and self.dense_xm.active else None
-        te.begin_step(self)
-        if dx is not None:
-            dx.begin_step()
-        styled = stage == "train" and self.input_style.active
-        if styled:
-            src = self.input_style.style(src, trg)  # a shallow copy with the styled images: the caller's batch stays as it is
+        st = self.selftrain
+        for option in self._options:
+            option.begin_step(self)
+        src = self.input_style.style(src, trg)  # styled: a shallow copy with the new images, the caller's batch stays as it is
         teacher = st.lambda_pl > 0 and st.pseudo_label_source == "teacher"
         pseudo = st.batch_targets(trg) if st.lambda_pl > 0 and not teacher else None
-        if self._can_join(src, trg):
-            pre = self._pipelined if self._pipelined is not None and self._matches(self._pipelined, batch) else None
-            self._pipelined = None
-            if pre is not None:  # joined one step ahead by prefetch(): its sparse metadata is already built (or queued)
-                both, B = pre["both"], pre["B"]
-                if styled:  # joined before the images were styled
-                    both = dict(both, img=torch.cat([src["img"], trg["img"]], 0))
-            else:
-                both, B = self._join(src, trg)
-            P = src["x"][0].shape[0]  # point rows [0, P) are the source's
-            if teacher:
-                # the teacher's 3D pass runs over the joined rows with the step's own sparse metadata: attached by prefetch(), else
-                # built here once through prepare(), which attaches it for the student's InputLayer to find
-                prep = getattr(self.model[n3d], "prepare", None)
-                if prep is not None and getattr(both["x"][0], "_mm_metadata", None) is None:
-                    with domains.split(B):
-                        prep(both)
-                pseudo = st.teacher_targets(self, {k: trg[k] for k in ("img", "depth", "img_indices")}, {"x": list(both["x"])}, P)
-            with domains.split(B):
-                dev = both["img"].device
-                step_start = torch.cuda.current_stream(dev).record_event()
-                prep = getattr(self.model[n3d], "prepare", None)
-                if prep is not None and self.overlap_metadata and self._side is None:
-                    self._side = torch.cuda.Stream(dev)
-                    from . import _lib
-
-                    _lib.bn2d_set_fused(_lib.bn2d_set_fused(0) & 2)  # no grid barrier beside the side stream
-                p2d, _, _, aux2d = self(both, model_name=n2d)
-                # the 2D branch is queued: build the voxel hash / rulebooks of the 3D branch on a side stream while the GPU
-                # works through it (the build's two host read-backs would otherwise drain the queue)
-                if prep is not None and self.overlap_metadata:
-                    prep(both, self._side, step_start)
-                if self.overlap_branches and not (self.reducer is not None and self.reducer.active):
-                    # the 3D branch (gathers, HBM-bound) on its own stream beside the 2D branch (MFMA / LDS-bound persistent
-                    # workgroups): autograd runs each branch's backward on the stream of its forward
-                    if self._s3d is None:
-                        self._s3d = torch.cuda.Stream(dev, priority=int(os.environ.get("MM_S3D_PRIO", "0")))
-                        # the single-launch BatchNorm2d kernels need every CU at once and would starve behind the other
-                        # stream's workgroups (csrc/bn2d.hip): three-kernel path while the branches share the GPU
-                        from . import _lib
-
-                        if self.overlap_branches == 1:
-                            _lib.bn2d_set_fused(0)
-                        # mode 2 (round 5): the 2D branch keeps its single-launch kernels (and its HIP graphs).  Beside them the 3D
-                        # branch launches nothing that waits across workgroups - three-kernel batch norms, merge sort / three-
-                        # kernel scans in whatever metadata it still has to build - so a grid barrier of the 2D branch can at
-                        # worst wait for the short kernels that hold CUs when it starts (csrc/fused_bn.h), never deadlock.
-                        _lib.bn3d_set_fused(0)
-                        if self.overlap_branches == 2:
-                            # ... and for good, not only around the forward call: a rulebook's destination-row CSR is built lazily
-                            # by the first BACKWARD that needs it (Rulebook.ensure_csr) - with rocPRIM's look-back scan that
-                            # is a spin-waiting kernel of the 3D stream beside the grid barriers of the 2D backward, the one
-                            # combination csrc/fused_bn.h rules out (the 10 s barrier bound fired once in a 49-test sequence
-                            # before this line existed).  Process-wide: metadata builds of this process stay spin-free.
-                            from .scn import metadata as _md0
-
-                            _md0.NO_SPIN[0] = 1
-                    main = torch.cuda.current_stream(dev)
-                    self._s3d.wait_event(step_start)
-                    md = getattr(both["x"][0], "_mm_metadata", None)
-                    from .scn import metadata as _md
-
-                    with torch.cuda.stream(self._s3d), _md.no_spin():
-                        for t in both["x"]:
-                            t.record_stream(self._s3d)
-                        if md is not None:
-                            for t in md.tensors():
-                                t.record_stream(self._s3d)
-                            for t in md.pending_tensors():
-                                t.record_stream(self._s3d)
-                        p3d, _, aux3d = self(both, model_name=n3d)
-                    main.wait_stream(self._s3d)
-                    for t in (p3d["seg_logit"], aux3d["seg_logit_point"]):
-                        t.record_stream(main)
-                else:
-                    p3d, _, aux3d = self(both, model_name=n3d)
-            l2d, a2d, l3d, a3d = p2d["seg_logit"], aux2d["seg_logit_avg"], p3d["seg_logit"], aux3d["seg_logit_point"]
-            single = self._single_cross_entropy() if pseudo is not None else None
-            if single is not None:
-                # one pass over each head's [source | target] logits: source labels with the entry's class weights, pseudo labels
-                # without; one backward launch writes the head's whole gradient
-                (rw, cw), gt = single, src["seg_label"]
-                seg2d, seg3d, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo, gt, cw)
-                seg2d, seg3d = rw * seg2d, rw * seg3d
-            else:
-                seg2d = self.loss("segmentation", pred=l2d[:P], gt=src["seg_label"])
-                seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
-                if pseudo is not None:
-                    _, _, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo)
-            if dx is not None:  # ONE matched lift of the aux map over all rows: the plain lifted a2d takes no part in the loss
-                (xs2d, xs3d), (xt2d, xt3d) = dx.terms(l3d, a3d, aux2d, p2d, both, P)
-            else:
-                xs2d, xs3d = self.cross_modal_loss(l3d[:P], a2d[:P], l2d[:P], a3d[:P])
-                xt2d, xt3d = self.cross_modal_loss(l3d[P:], a2d[P:], l2d[P:], a3d[P:])
-            im = te.terms(l2d, l3d, P)
-            ca = al.terms(l2d, l3d, P)
-            ad = adv.terms(l2d, l3d, P) if adv.active else None
-        else:
-            if teacher:
-                own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
-                pseudo = st.teacher_targets(self, own, own)
-            p2d, _, _, aux2d = self(src, model_name=n2d)
-            p3d, _, aux3d = self(src, model_name=n3d)
-            seg2d = self.loss("segmentation", pred=p2d["seg_logit"], gt=src["seg_label"])
-            seg3d = self.loss("segmentation", pred=p3d["seg_logit"], gt=src["seg_label"])
-            if dx is not None:
-                ((xs2d, xs3d),) = dx.terms(p3d["seg_logit"], aux3d["seg_logit_point"], aux2d, p2d, src)
-            else:
-                xs2d, xs3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
-                                                   aux3d["seg_logit_point"])
-            src2d, src3d = p2d["seg_logit"], p3d["seg_logit"]
-            p2d, _, _, aux2d = self(trg, model_name=n2d)
-            p3d, _, aux3d = self(trg, model_name=n3d)
-            if dx is not None:
-                ((xt2d, xt3d),) = dx.terms(p3d["seg_logit"], aux3d["seg_logit_point"], aux2d, p2d, trg)
-            else:
-                xt2d, xt3d = self.cross_modal_loss(p3d["seg_logit"], aux2d["seg_logit_avg"], p2d["seg_logit"],
-                                                   aux3d["seg_logit_point"])
-            if pseudo is not None:
-                _, _, pl2d, pl3d = st.losses(p2d["seg_logit"], p3d["seg_logit"], 0, pseudo)
-            im = te.terms(p2d["seg_logit"], p3d["seg_logit"], 0)
-            # the two calls' logits side by side, as the joined pass has them: the source's rows first
-            ca = al.terms(torch.cat((src2d, p2d["seg_logit"])), torch.cat((src3d, p3d["seg_logit"])), int(src2d.shape[0])) if al.active else None
-            ad = adv.terms(torch.cat((src2d, p2d["seg_logit"])), torch.cat((src3d, p3d["seg_logit"])), int(src2d.shape[0])) if adv.active else None
+        run = self._joined_pass if self._can_join(src, trg) else self._two_call_pass
+        r = run(batch, src, trg, pseudo, teacher)
+        found = [(term, term.terms(*(r.both_logits if term.READS_SOURCE else r.target_logits))) for term in self._logit_terms if term.active]
+        (xs2d, xs3d), (xt2d, xt3d) = r.xm_src, r.xm_trg
         self.last_logs = {
-            f"{stage}/loss_segmentation": seg2d, f"{stage}/loss_segmentation_3d": seg3d,
+            f"{stage}/loss_segmentation": r.seg2d, f"{stage}/loss_segmentation_3d": r.seg3d,
             f"{stage}/xm_loss_src_2d": xs2d, f"{stage}/xm_loss_tgt_2d": xt2d,
             f"{stage}/xm_loss_src_3d": xs3d, f"{stage}/xm_loss_tgt_3d": xt3d,
         }
-        if dx is not None:
-            dx.log(self.last_logs, stage)
-        loss_2d = seg2d + self.lambda_xm_src * xs2d + self.lambda_xm_trg * xt2d
-        loss_3d = seg3d + self.lambda_xm_src * xs3d + self.lambda_xm_trg * xt3d
-        if pseudo is not None:
-            loss_2d = loss_2d + st.lambda_pl * pl2d
-            loss_3d = loss_3d + st.lambda_pl * pl3d
-            st.log(self.last_logs, stage, pl2d, pl3d, trg["x"][0].shape[0])
-        if im is not None:
-            loss_2d, loss_3d = te.add(self.last_logs, stage, loss_2d, loss_3d, im)
-        if ca is not None:
-            loss_2d, loss_3d = al.add(self.last_logs, stage, loss_2d, loss_3d, ca)
-        if ad is not None:
-            loss_2d, loss_3d = adv.add(self.last_logs, stage, loss_2d, loss_3d, ad)
-        if styled:
-            self.input_style.log(self.last_logs, stage)
+        self.dense_xm.log(self.last_logs, stage)
+        loss_2d = r.seg2d + self.lambda_xm_src * xs2d + self.lambda_xm_trg * xt2d
+        loss_3d = r.seg3d + self.lambda_xm_src * xs3d + self.lambda_xm_trg * xt3d
+        if r.pl2d is not None:
+            loss_2d, loss_3d = loss_2d + st.lambda_pl * r.pl2d, loss_3d + st.lambda_pl * r.pl3d
+            st.log(self.last_logs, stage, r.pl2d, r.pl3d, trg["x"][0].shape[0])
+        for term, values in found:
+            if values is not None:
+                loss_2d, loss_3d = term.add(self.last_logs, stage, loss_2d, loss_3d, values)
+        self.input_style.log(self.last_logs, stage)
         return loss_2d + loss_3d
+
+    def _joined_pass(self, batch, src, trg, pseudo, teacher):
+        """One pass per network over [source scenes | target scenes]."""
+        n2d, n3d = self.modules_name[0], self.modules_name[1]
+        st = self.selftrain
+        pre = self._pipelined if self._pipelined is not None and self._matches(self._pipelined, batch) else None
+        self._pipelined = None
+        if pre is not None:  # joined one step ahead by prefetch(): its sparse metadata is already built (or queued)
+            both, B = pre["both"], pre["B"]
+            if src is not batch["source"]:  # joined before the images were styled
+                both = dict(both, img=torch.cat([src["img"], trg["img"]], 0))
+        else:
+            both, B = self._join(src, trg)
+        P = src["x"][0].shape[0]  # point rows [0, P) are the source's
+        prep = getattr(self.model[n3d], "prepare", None)
+        if teacher:
+            # the teacher's 3D pass runs over the joined rows with the step's own sparse metadata: attached by prefetch(), else
+            # built here once through prepare(), which attaches it for the student's InputLayer to find
+            if prep is not None and getattr(both["x"][0], "_mm_metadata", None) is None:
+                with domains.split(B):
+                    prep(both)
+            pseudo = st.teacher_targets(self, {k: trg[k] for k in ("img", "depth", "img_indices")}, {"x": list(both["x"])}, P)
+        with domains.split(B):
+            dev = both["img"].device
+            step_start = torch.cuda.current_stream(dev).record_event()
+            if prep is not None and self.overlap_metadata and self._side is None:
+                self._side = torch.cuda.Stream(dev)
+                _lib.bn2d_set_fused(_lib.bn2d_set_fused(0) & 2)  # no grid barrier beside the side stream
+            p2d, _, _, aux2d = self(both, model_name=n2d)
+            # the 2D branch is queued: build the voxel hash / rulebooks of the 3D branch on a side stream while the GPU
+            # works through it (the build's two host read-backs would otherwise drain the queue)
+            if prep is not None and self.overlap_metadata:
+                prep(both, self._side, step_start)
+            p3d, aux3d = self._joined_3d(both, n3d, dev, step_start)
+        l2d, l3d, a3d = p2d["seg_logit"], p3d["seg_logit"], aux3d["seg_logit_point"]
+        single = self._single_cross_entropy() if pseudo is not None else None
+        pl2d = pl3d = None
+        if single is not None:
+            # one pass over each head's [source | target] logits: source labels with the entry's class weights, pseudo labels
+            # without; one backward launch writes the head's whole gradient
+            (rw, cw), gt = single, src["seg_label"]
+            seg2d, seg3d, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo, gt, cw)
+            seg2d, seg3d = rw * seg2d, rw * seg3d
+        else:
+            seg2d = self.loss("segmentation", pred=l2d[:P], gt=src["seg_label"])
+            seg3d = self.loss("segmentation", pred=l3d[:P], gt=src["seg_label"])
+            if pseudo is not None:
+                _, _, pl2d, pl3d = st.losses(l2d, l3d, P, pseudo)
+        # with a window, ONE matched lift of the aux map over all rows: the plain lifted aux rows take no part in the loss
+        xm_src, xm_trg = self.dense_xm.terms(l3d, a3d, aux2d, p2d, both, P)
+        return _Pass(seg2d, seg3d, pl2d, pl3d, xm_src, xm_trg, (l2d, l3d, P), (l2d, l3d, P))
+
+    def _joined_3d(self, both, n3d, dev, step_start):
+        """The 3D branch of the joined pass, beside the 2D branch with ``overlap_branches``: its main and aux outputs."""
+        if not self.overlap_branches or (self.reducer is not None and self.reducer.active):
+            p3d, _, aux3d = self(both, model_name=n3d)
+            return p3d, aux3d
+        # the 3D branch (gathers, HBM-bound) on its own stream beside the 2D branch (MFMA / LDS-bound persistent
+        # workgroups): autograd runs each branch's backward on the stream of its forward
+        if self._s3d is None:
+            self._s3d = torch.cuda.Stream(dev, priority=int(os.environ.get("MM_S3D_PRIO", "0")))
+            # the single-launch BatchNorm2d kernels need every CU at once and would starve behind the other
+            # stream's workgroups (csrc/bn2d.hip): three-kernel path while the branches share the GPU
+            if self.overlap_branches == 1:
+                _lib.bn2d_set_fused(0)
+            # mode 2 (round 5): the 2D branch keeps its single-launch kernels (and its HIP graphs).  Beside them the 3D
+            # branch launches nothing that waits across workgroups - three-kernel batch norms, merge sort / three-
+            # kernel scans in whatever metadata it still has to build - so a grid barrier of the 2D branch can at
+            # worst wait for the short kernels that hold CUs when it starts (csrc/fused_bn.h), never deadlock.
+            _lib.bn3d_set_fused(0)
+            if self.overlap_branches == 2:
+                # ... and for good, not only around the forward call: a rulebook's destination-row CSR is built lazily
+                # by the first BACKWARD that needs it (Rulebook.ensure_csr) - with rocPRIM's look-back scan that
+                # is a spin-waiting kernel of the 3D stream beside the grid barriers of the 2D backward, the one
+                # combination csrc/fused_bn.h rules out (the 10 s barrier bound fired once in a 49-test sequence
+                # before this line existed).  Process-wide: metadata builds of this process stay spin-free.
+                _md.NO_SPIN[0] = 1
+        main = torch.cuda.current_stream(dev)
+        self._s3d.wait_event(step_start)
+        md = getattr(both["x"][0], "_mm_metadata", None)
+        with torch.cuda.stream(self._s3d), _md.no_spin():
+            for t in both["x"]:
+                t.record_stream(self._s3d)
+            if md is not None:
+                for t in md.tensors():
+                    t.record_stream(self._s3d)
+                for t in md.pending_tensors():
+                    t.record_stream(self._s3d)
+            p3d, _, aux3d = self(both, model_name=n3d)
+        main.wait_stream(self._s3d)
+        for t in (p3d["seg_logit"], aux3d["seg_logit_point"]):
+            t.record_stream(main)
+        return p3d, aux3d
+
+    def _two_call_pass(self, batch, src, trg, pseudo, teacher):
+        """The reference's literal sequence: both networks over the source batch, then over the target batch."""
+        n2d, n3d = self.modules_name[0], self.modules_name[1]
+        st = self.selftrain
+        if teacher:
+            own = dict(trg, x=list(trg["x"]))  # the 3D net gates x[1] in place: the student must see the batch's features
+            pseudo = st.teacher_targets(self, own, own)
+        p2d, _, _, aux2d = self(src, model_name=n2d)
+        p3d, _, aux3d = self(src, model_name=n3d)
+        seg2d = self.loss("segmentation", pred=p2d["seg_logit"], gt=src["seg_label"])
+        seg3d = self.loss("segmentation", pred=p3d["seg_logit"], gt=src["seg_label"])
+        (xm_src,) = self.dense_xm.terms(p3d["seg_logit"], aux3d["seg_logit_point"], aux2d, p2d, src)
+        src2d, src3d = p2d["seg_logit"], p3d["seg_logit"]
+        p2d, _, _, aux2d = self(trg, model_name=n2d)
+        p3d, _, aux3d = self(trg, model_name=n3d)
+        (xm_trg,) = self.dense_xm.terms(p3d["seg_logit"], aux3d["seg_logit_point"], aux2d, p2d, trg)
+        trg2d, trg3d = p2d["seg_logit"], p3d["seg_logit"]
+        pl2d = pl3d = both = None
+        if pseudo is not None:
+            _, _, pl2d, pl3d = st.losses(trg2d, trg3d, 0, pseudo)
+        if any(term.active and term.READS_SOURCE for term in self._logit_terms):
+            # the two calls' logits side by side, as the joined pass has them: the source's rows first
+            both = (torch.cat((src2d, trg2d)), torch.cat((src3d, trg3d)), int(src2d.shape[0]))
+        return _Pass(seg2d, seg3d, pl2d, pl3d, xm_src, xm_trg, (trg2d, trg3d, 0), both)
 
     def training_step(self, batch, batch_idx=0):
         with self._use():
@@ -436,8 +424,6 @@ class TrainModel(nn.Module):
             pre["phase"] = 2
 
     def _rulebooks_on_side_stream(self, md):
-        from .scn import metadata as _md
-
         dev = md.device
         main = torch.cuda.current_stream(dev)
         if self._meta_stream is None:
@@ -477,8 +463,6 @@ class TrainModel(nn.Module):
 
     def _teacher(self):
         """``ema_eval``: the context in which the model computes with the teacher's weights (built with the optimisers)."""
-        import contextlib
-
         if not self.ema_eval or self.ema_decay is None:
             return contextlib.nullcontext()
         if self.ema is None:
@@ -516,8 +500,6 @@ class TrainModel(nn.Module):
         confidence and the class of the 2D, the 3D and the softmax-average prediction - the labels ``test_step`` counts.
         Computes no loss, so the batch needs no labels beyond what the loaders put there.  Like ``validation_step`` it leaves
         the model in eval mode; no epoch-end hook follows it, so call ``trainer.model.train()`` before training goes on."""
-        from . import pselab
-
         with self._use(), self._teacher():
             self.model.eval()
             p2d, _, _, _ = self(batch, model_name=self.modules_name[0])
@@ -561,8 +543,8 @@ class TrainModel(nn.Module):
                 **({"ema": self.ema.state_dict(),
                     "ema_state_dict": {self._ckpt_key(k): v for k, v in self.ema.teacher_state_dict().items()}}
                    if self.ema is not None else {}),
-                **self.selftrain.state_dict(),  # "pl_adaptive": the self-adaptive pseudo-label thresholds, once built
-                **self.adversary.state_dict(),  # "adversary": the two discriminators and their optimisers, once built
+                # the options' state, once built: "pl_adaptive" (the self-adaptive thresholds), "adversary" (discriminators and optimisers)
+                **{k: v for option in self._options for k, v in option.state_dict().items()},
                 # Lightning's key for the GradScaler of a ``precision: 16`` run
                 **({"native_amp_scaling_state": self.scaler.state_dict()} if self.scaler is not None else {})}
 
@@ -590,8 +572,6 @@ class TrainModel(nn.Module):
         states = ckpt.get("optimizer_states", [])
         if states and len(states) != len(self.optimizers):
             raise ValueError(f"checkpoint holds {len(states)} optimizer states, the trainer has {len(self.optimizers)}")
-        from . import conv2d as _c2d
-
         _c2d.PARAM_EPOCH[0] += 1  # weights changed under the packed bf16 copies
         for o, sd in zip(self.optimizers, ckpt.get("optimizer_states", [])):
             o.load_state_dict(sd)
@@ -604,8 +584,9 @@ class TrainModel(nn.Module):
                 self.ema.load_state_dict(ckpt["ema"])
             else:
                 self.ema.reset()  # a checkpoint without a teacher: it starts from the loaded weights
-        self.selftrain.load_state_dict(ckpt, next((p.device for p in self.model.parameters() if p.is_cuda), None))
-        self.adversary.load_state_dict(ckpt, next((p.device for p in self.model.parameters() if p.is_cuda), None))
+        device = next((p.device for p in self.model.parameters() if p.is_cuda), None)
+        for option in self._options:
+            option.load_state_dict(ckpt, device)
         # the loss scale resumes where it was; the scaler itself is rebuilt by the next fit_step (its device step counters start
         # from the optimisers' restored step counts)
         self._scaler_state = ckpt.get("native_amp_scaling_state")
@@ -654,8 +635,6 @@ class TrainModel(nn.Module):
         self._pipelined = nxt
         self._prefetch_rulebooks()
         if self._scaler_cfg and self.scaler is None:
-            from .amp import GradScaler
-
             self.scaler = GradScaler(loss.device, **(self._scaler_cfg if isinstance(self._scaler_cfg, dict) else {}))
             if getattr(self, "_scaler_state", None):
                 self.scaler.load_state_dict(self._scaler_state)
@@ -685,8 +664,6 @@ class TrainModel(nn.Module):
                 self.last_grad_norm = self.scaler.last_grad_norm
         else:
             if self._clip is not None:
-                from .clip import clip_grad_norm_, clip_grad_value_
-
                 if self._clip[0] == "norm":
                     self.last_grad_norm = clip_grad_norm_(self.optimizers, self._clip[1], grad_scale=self.reducer.grad_scale)
                 else:
@@ -705,8 +682,7 @@ class TrainModel(nn.Module):
         return loss
 
 
-for _owner, _names in (("selftrain", FORWARDED), ("target_entropy", infomax.FORWARDED), ("alignment", coral.FORWARDED),
-                       ("adversary", adversarial.FORWARDED), ("input_style", fda.FORWARDED), ("dense_xm", xmdense.FORWARDED)):
-    for _name in _names:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
+for _owner, _cls in OPTIONS:
+    for _name in _cls.FORWARDED:  # trainer.lambda_pl, ..., trainer.last_target_mass: read and assigned on the policy object
         setattr(TrainModel, _name, property(lambda self, n=_name, o=_owner: getattr(getattr(self, o), n),
                                             lambda self, value, n=_name, o=_owner: setattr(getattr(self, o), n, value)))

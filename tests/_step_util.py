@@ -87,6 +87,15 @@ def _alone_logits(tm, dev):
     return l2, l3
 
 
+def _hook_logits(tm, keep=lambda t: t.detach().clone()):
+    """The main heads' logits of every forward of the two networks, in call order, kept on the device as they were (or as ``keep``
+    makes them)."""
+    seen = {"2d_net": [], "3d_net": []}
+    for name in seen:
+        tm.model[name].register_forward_hook(lambda m, i, out, name=name: seen[name].append(keep(out[0]["seg_logit"])))
+    return seen
+
+
 _BUILT = []  # the trainers of the running test
 
 

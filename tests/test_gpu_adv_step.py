@@ -28,14 +28,6 @@ def _trainer(n2, n3, **kw):
     return _BUILT[-1]
 
 
-def _hook_logits(tm):
-    """The main heads' logits of every forward of the two networks, in call order, kept on the device as they were."""
-    seen = {"2d_net": [], "3d_net": []}
-    for name in seen:
-        tm.model[name].register_forward_hook(lambda m, i, out, name=name: seen[name].append(out[0]["seg_logit"].detach().clone()))
-    return seen
-
-
 def _initial(C, H, seed, dev):
     """The two discriminators' parameters as the policy object draws them: one private stream, the 2D head's first."""
     from mm2d3d_amd.adversarial import initial_parameters
@@ -109,7 +101,7 @@ def test_step_adds_the_weighted_terms_and_steps_the_discriminators(mode, joint):
     n2, n3 = T._nets(dev)
     off = _trainer(copy.deepcopy(n2), copy.deepcopy(n3), joint_domains=joint)
     tm = _trainer(n2, n3, joint_domains=joint, lambda_adv=lam, adv_input=mode, adv_hidden=H, adv_lr=lr, adv_betas=betas, adv_seed=seed)
-    seen = _hook_logits(tm)
+    seen = T._hook_logits(tm)
     batch = T._batch(dev)
     P = int(batch["source"]["x"][0].shape[0])
     loss = tm.fit_step(batch)

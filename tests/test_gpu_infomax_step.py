@@ -31,11 +31,8 @@ def _close(got, ref):
 
 
 def _hook_logits(tm):
-    """The main heads' logits of every forward of the two networks, in call order."""
-    seen = {"2d_net": [], "3d_net": []}
-    for name in seen:
-        tm.model[name].register_forward_hook(lambda m, i, out, name=name: seen[name].append(out[0]["seg_logit"].detach().float().cpu().numpy()))
-    return seen
+    """The main heads' logits of every forward of the two networks, in call order, as float32 arrays on the host."""
+    return T._hook_logits(tm, lambda t: t.detach().float().cpu().numpy())
 
 
 def test_both_weights_zero_is_the_step_without_the_options():

@@ -3,19 +3,23 @@
     python tools/selftrain_bits.py dump OUT.npz [--only SUBSTRING[,SUBSTRING...]] [--skip SUBSTRING[,SUBSTRING...]]
     python tools/selftrain_bits.py compare A.npz B.npz
 
-``dump`` runs every self-training option combination for three ``fit_step`` calls at the shapes of tests/test_gpu_teacher_step.py
+``dump`` runs every self-training option combination, and every other optional term of the step alone and all of them together
+(``lambda_coral``, ``lambda_adv``, ``fda_beta``, ``xm_window``), for three ``fit_step`` calls at the shapes of tests/test_gpu_teacher_step.py
 (1 + 1 synthetic nuScenes scenes, 48x64 images, 6 classes, fp16, dropout 0, ``ema_decay`` 0.9, heads scaled by 4; fresh nets from
-seed 0 per case) and stores, as raw bytes: per step the loss, every ``last_logs`` value and every tensor of ``last_teacher``; after
-the last step every entry of the checkpoint's "state_dict" and "ema_state_dict" and the state of ``pl_adaptive``.  Then the
+seed 0 per case) and stores, as raw bytes: per step the loss, every ``last_logs`` value and every tensor of the ``LAST`` dicts
+(``last_teacher`` ... ``last_match``); after the last step every entry of the checkpoint's "state_dict" and "ema_state_dict", the
+state of ``pl_adaptive`` and the discriminators' parameters of the checkpoint's "adversary".  Then the
 ``direct/`` group: the row kernels called through ``pselab.predict``, ``pselab.teacher_labels``, ``AdaptiveThreshold.update``,
 ``losses.cross_entropy_soft_pair`` and ``losses.target_entropy`` at sizes the tiny step never reaches (``DIRECT_SIZES``: a tile and a
 row, the class maximum, more tiles than workgroups of both tile sizes), contiguous and as row-pitched views, every output and
-gradient as raw bytes.  It uses only ``train_kwargs``, ``fit_step``, ``last_logs``, ``last_teacher``,
+gradient as raw bytes.  It uses only ``train_kwargs``, ``fit_step``, ``last_logs``, the ``last_*`` attributes,
 ``pl_adaptive.state_dict()``, ``checkpoint()``, ``load_checkpoint()`` and those public functions, so the same file runs in either
 checkout (it imports the package of the checkout whose ``tools/`` it lies in: copy it there).  The ``agreement/`` cases and the
 ``agreement`` direct calls (``pl_agreement``, ``pselab.agreement_weights``, the pairs' row weights) exist from the commit that added
 them on: against an older checkout dump both sides with ``--skip agreement``.  ``compare`` demands equal key lists
-and equal bytes, prints the number of arrays and the total bytes, and exits 1 on any difference.  One process per dump.
+and equal bytes, prints the number of arrays and the total bytes, and exits 1 on any difference.  One process per dump; every case
+leaves its captured 2D trunk behind (some GiB of the device each), so all cases do not fit one process: dump them in groups chosen
+with ``--only`` / ``--skip`` (``batch/``, ``teacher/``, ...), one process and one file per group, and compare group by group.
 """
 import argparse
 import gc
@@ -38,6 +42,7 @@ ADAPTIVE = dict(pl_threshold_momentum=0.5, pl_threshold_warmup=True)  # the thre
 PRIOR = [0.3, 0.1, 0.2, 0.1, 0.2, 0.1]
 AGREEMENT_BETA = 0.5
 DIRECT_SIZES = ((129, 5), (1000, 32), (131201, 6), (300001, 6))  # (N, C)
+LAST = ("last_teacher", "last_agreement", "last_coral", "last_adversary", "last_fda", "last_match")  # trainer attributes: dicts or None
 
 
 def cases():
@@ -76,6 +81,18 @@ def cases():
     add("agreement/batch/hard/own/joined", dict(lambda_pl=1.0, **agree), extras="labels")
     add("agreement/batch/soft/own/thr_0.9/T_2.0", dict(lambda_pl=1.0, **agree, pl_targets="soft", pl_threshold=0.9, pl_temperature=2.0),
         extras="logits")
+    for (call, ckw), mode in itertools.product(calls.items(), ("log", "plain")):  # CORAL / LogCORAL of the two domains' logits
+        add(f"coral/{mode}/{call}", dict(lambda_coral=0.5, coral=mode, **ckw))
+    for (call, ckw), mode in itertools.product(calls.items(), ("selfinfo", "softmax")):  # the output adversary and its discriminators
+        add(f"adv/{mode}/{call}", dict(lambda_adv=0.1, adv_input=mode, adv_lr=1e-2, **ckw))
+    add("adv/selfinfo/joined/checkpoint_round_trip", dict(lambda_adv=0.1, adv_lr=1e-2), resume=True)
+    for (call, ckw), r in itertools.product(calls.items(), (1, 2)):  # the dense cross-modal window
+        add(f"xm_window/{r}/{call}", dict(xm_window=r, **ckw))
+    everything = dict(lambda_pl=1.0, lambda_minent=0.1, lambda_coral=0.5, lambda_adv=0.1, adv_lr=1e-2, fda_beta=0.05, xm_window=2)
+    for call, ckw in calls.items():
+        add(f"fda/{call}", dict(fda_beta=0.05, **ckw))  # a band of 2 at 48 x 64
+        add(f"everything/{call}", dict(everything, **ckw), extras="labels")
+    add("everything/joined/prefetched", dict(everything), extras="labels", prefetch=True)
     return out
 
 
@@ -255,11 +272,10 @@ def dump(path, only=None, skip=None):
             put(f"{name}/step{s}/loss", _raw(loss))
             for k, v in tm.last_logs.items():
                 put(f"{name}/step{s}/logs/{k}", _raw(v))
-            for k, v in (tm.last_teacher or {}).items():
-                if torch.is_tensor(v):
-                    put(f"{name}/step{s}/last_teacher/{k}", _raw(v))
-            for k, v in (getattr(tm, "last_agreement", None) or {}).items():
-                put(f"{name}/step{s}/last_agreement/{k}", _raw(v))
+            for attr in LAST:  # an attribute the checkout does not know yet counts as None
+                for k, v in (getattr(tm, attr, None) or {}).items():
+                    if torch.is_tensor(v):
+                        put(f"{name}/step{s}/{attr}/{k}", _raw(v))
         ckpt = tm.checkpoint()
         for part in ("state_dict", "ema_state_dict"):
             for k, v in ckpt[part].items():
@@ -267,6 +283,8 @@ def dump(path, only=None, skip=None):
         if tm.pl_adaptive is not None:
             for k, v in tm.pl_adaptive.state_dict().items():
                 put(f"{name}/pl_adaptive/{k}", _raw(v) if torch.is_tensor(v) else np.array([v], dtype=np.int64).view(np.uint8))
+        for i, p in enumerate((ckpt.get("adversary") or {}).get("params", ())):
+            put(f"{name}/adversary/params{i}", _raw(p))
         torch.cuda.synchronize()
         print(f"{name}: loss {float(loss.detach()):.6f}, {len(tm.last_logs)} logged keys, "
               f"last_teacher {sorted(tm.last_teacher) if tm.last_teacher else None}", flush=True)
