@@ -255,7 +255,8 @@ size_t mm_spconv_ws_bytes(int64_t n_rules, int Cin, int Cout, int K);
  *   weight element (k,ci,co) = W[kk*w_kstride + ci*s_ci + co*s_co], kk = kflip ? K-1-k : k.
  *   mode (fp32 rows): MM_SPCONV_DEFAULT = fp32-faithful three-term split-bf16 products on the matrix-rate-bound widths;
  *   MM_SPCONV_FP32 = plain fp32 engines everywhere; MM_SPCONV_TWO_TERMS = two terms (faster; fails the gradient parity bar:
- *   diagnostics only); | MM_SPCONV_DW_NARROW: the weight gradient keeps its <= 4 x 4 channel tiles. */
+ *   diagnostics only); | MM_SPCONV_DW_NARROW: the weight gradient keeps its <= 4 x 4 channel tiles (same slabs, so the same
+ *   sums bit for bit as with the default tiles). */
 #define MM_SPCONV_DEFAULT 0
 #define MM_SPCONV_FP32 1
 #define MM_SPCONV_TWO_TERMS 2
@@ -319,7 +320,9 @@ int mm_spconv_os_apply_bf16(const void* in, int ld_in, int Cin, void* out, int l
                             const int32_t* dst, const int32_t* nbrp, const uint32_t* tmask, int64_t n_tiles, int tile_rows,
                             mm_stream_t stream);
 /* dW[k][ci][co] (+)= sum over the rules of bucket k of in[src][ci] * dout[dst][co]; in / dout bf16 rows, dW fp32;
- * workspace of mm_spconv_dw_ws_bytes */
+ * workspace of mm_spconv_dw_ws_bytes.  Cin, Cout multiples of 16; unless mode has MM_SPCONV_DW16_ELEM the rows are read 16 bytes
+ * at a time: in / dout 16-B aligned, ld_in / ld_do multiples of 8, else MM_ERR_ARG before any launch (_f16 and
+ * mm_spconv_dw_partial with 16-bit rows alike).  Every row kind: ld_in >= Cin, ld_do >= Cout. */
 int mm_spconv_dw_bf16(const void* in, int ld_in, int Cin, const void* dout, int ld_do, int Cout, const int32_t* src,
                       const int32_t* dst, const int32_t* offsets_host, int K, float* dW, int accumulate, int mode, void* ws,
                       size_t ws_bytes, mm_stream_t stream);

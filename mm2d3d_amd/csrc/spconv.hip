@@ -1248,12 +1248,19 @@ int dw_partial(int bf, int mode, const void* in, int ld_in, int Cin, const void*
   MM_CHECK_ARG(K > 0 && K <= MAXK && Cin > 0 && Cout > 0, "spconv_dw: bad shape");
   MM_CHECK_ARG(bf >= 0 && bf <= 2, "spconv_dw: row kind must be 0 (fp32), 1 (bf16) or 2 (fp16)");
   MM_CHECK_ARG(!bf || (Cin % 16 == 0 && Cout % 16 == 0), "spconv_dw (16-bit rows): channels must be multiples of 16");
+  MM_CHECK_ARG(ld_in >= Cin && ld_do >= Cout, "spconv_dw: a row pitch is smaller than its channel count");
+  // k_dw_tr16 gathers whole 16-bit rows with 16-byte loads (the element gathers of MM_SPCONV_DW16_ELEM take any 2-byte address)
+  MM_CHECK_ARG(!bf || (mode & 8) || (ld_in % 8 == 0 && ld_do % 8 == 0 && (((uintptr_t)in | (uintptr_t)dout) % 16) == 0),
+               "spconv_dw (16-bit rows): rows must be 16-B aligned, pitches multiples of 8");
   KSeg& seg = *seg_out;
   const bool mfma_ok = (Cin % 16 == 0) && (Cout % 16 == 0);
   const int nt = bf ? -bf : (mfma_ok && Cin >= split_min_cin(true) ? split_terms(mode) : 0);  // matrix-rate-bound widths, as in mm_spconv_apply
   // the wide tiles exist for the split kernels (they save 4-byte gathers); 16-bit rows are gathered whole (k_dw_tr16): <= 4 x 4 there
-  const bool wide_ok = nt > 0 && !(mode & 4) && offsets_host[K] >= DW_WIDE_MIN_RULES;
-  const int chunk = dw_chunk(offsets_host[K], Cin, Cout, wide_ok);
+  const bool wide_rules = nt > 0 && offsets_host[K] >= DW_WIDE_MIN_RULES;
+  const bool wide_ok = wide_rules && !(mode & 4);
+  // the slabs are cut for the default tiles whether or not MM_SPCONV_DW_NARROW keeps the <= 4 x 4 ones: the same slab sums, bit for
+  // bit, under either tile shape (cut for the narrow tiles they were other slabs, and the lever changed the rounding it was to time)
+  const int chunk = dw_chunk(offsets_host[K], Cin, Cout, wide_rules);
   int nb = make_seg(offsets_host, K, chunk, &seg);
   const int ne = Cin * Cout;
   if ((size_t)(nb > 0 ? nb : 1) * ne * sizeof(float) > ws_bytes) {

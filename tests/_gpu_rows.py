@@ -1,5 +1,5 @@
 """Device operands of the tests that call the C ABI directly (test_gpu_point_rows.py, test_gpu_loss_rows.py,
-test_gpu_lift_index.py, test_gpu_bn_rows.py, test_gpu_misc2d.py): pitched views into wider buffers whose padding is NaN for inputs and a sentinel, which
+test_gpu_lift_index.py, test_gpu_bn_rows.py, test_gpu_misc2d.py, test_gpu_spconv_rows.py): pitched views into wider buffers whose padding is NaN for inputs and a sentinel, which
 must survive, for outputs.  No tests here; importing this needs no GPU."""
 import numpy as np
 import torch
